@@ -10,7 +10,13 @@ default --steps 201 is exactly one whole `-p Y --iter-max 200` run.  Graph, posi
 streams are resident in HBM before the timed region starts.
 
     python bench.py --gpus 1 --steps 201 --warmup 3
+    python bench.py --gpus 1 --steps 201 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the --steps steps and prints the result line.  --full adds what else the benchmark
+measures: N = 1 the quality / bubbles / reference_streams / layout_2d legs, the CLI's wall clocks and the CPU baseline;
+N > 1 the instrumented pass, merge windows of 4, the sharded `-p L` leg and the same workload on one GPU.
+--dump-outputs DIR writes what the timed run computed (positions and the sort order, float64) as DIR/<name>.npy.
 
 N>1: BASELINE configs[4] — windows(N=1e7, P=1024, W=97656, seed=3), 1e8 steps, -p Y --iter-max 100 — with the paths
 sharded over the ranks (gfs_rank below the C ABI, gfasort_amd/distributed.py RankDriver) and ONE RCCL all-reduce per
@@ -31,6 +37,20 @@ sys.path.insert(0, ROOT)
 ALGO_BYTES_1D = 64          # 2 step records x16 B + 2 position reads x8 B + 2 writes x8 B
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
 ATOMIC_UNIT_PEAK = 23.6e9   # 64-B f64 atomic requests/s the memory side executes, whole chip, measured (profiles/r01/ubench_scattered_ops.log)
+DUMP_BUDGET_BYTES = 60_000_000   # --dump-outputs: all files together stay below 64 MB
+
+
+def dump_outputs(d, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write each 1-D array as d/<name>.npy in float64.  Above the budget in all (N > 1: 10M nodes), every array keeps the
+    same fixed, seeded sample of its entries, in index order, so that two runs stay comparable entry for entry."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64).ravel() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget:
+            keep = a.size * budget // total
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def build_workload(world=1):
@@ -316,14 +336,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=201)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, everything else the benchmark measures (extra legs, CLI wall clocks, CPU "
+                         "baseline; N>1: instrumented pass, merge windows of 4, sharded -p L leg, one-GPU comparison)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the positions and the sort order the timed run computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CLI wall clocks and the CPU baseline")
     ap.add_argument("--priming", action="store_true",
                     help="profiling runs only: after the warm-up steps, one untimed launch of the timed shape (both dispatches of the fused "
                          "kernel are then of one shape and its rocprofv3 --stats average is the timed launch's duration); disclosed in "
                          "config.untimed_priming_launch.  Default: the warm-up is exactly the --warmup steps")
     ap.add_argument("--leg", default="", help="internal: run ONE extra leg in this process and print its JSON")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="only the timed region: skip the quality / bubbles / reference_streams / layout_2d legs (PMC passes)")
+                    help="--full: skip the quality / bubbles / reference_streams / layout_2d legs")
     ap.add_argument("--streams", type=int, default=0)
     ap.add_argument("--flags", type=int, default=0)
     ap.add_argument("--bundle", type=int, default=0, help="sampling bundle: 0 = library auto policy, 1 = reference streams")
@@ -337,6 +362,8 @@ def main():
     ap.add_argument("--no-fuse", action="store_true",
                     help="one kernel launch per iteration instead of one fused persistent launch per merge window")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.leg:
         # One extra leg per child process: the parent's rocprofv3 --stats then holds the timed region's kernels only
@@ -422,6 +449,11 @@ def main():
     elapsed = time.perf_counter() - t0
 
     st1 = runner.stats()
+    if args.dump_outputs:
+        runner.finish()                                             # N > 1: complete the replicas (collective)
+        if rank == 0:
+            x = runner.positions_numpy()
+            dump_outputs(args.dump_outputs, {"positions": x, "order": hip.sort_order(x)})
     local_updates = st1.term_updates - st0.term_updates
     local_kernel_ms = st1.kernel_ms - st0.kernel_ms
     multi = None
@@ -432,12 +464,14 @@ def main():
         u = torch.tensor([float(local_updates)], dtype=torch.float64, device="cuda")
         dist.all_reduce(u, op=dist.ReduceOp.SUM)
         total_updates = int(u.item())
-        # a short instrumented pass after the timed region: where a window's time goes (HIP events on rank 0's stream)
-        runner.profile = True
-        runner.run_range([s % n_sched for s in range(min(args.steps, 24))])
-        tm = runner.collect_timing()
-        runner.profile = False
-        sync_all()
+        tm = None
+        if args.full:
+            # a short instrumented pass after the timed region: where a window's time goes (HIP events on rank 0's stream)
+            runner.profile = True
+            runner.run_range([s % n_sched for s in range(min(args.steps, 24))])
+            tm = runner.collect_timing()
+            runner.profile = False
+            sync_all()
         info = runner.info
         # what actually carried the collective: the library torch.distributed reports, the communicator's size, the device every
         # rank bound (gathered, so that the record itself shows N distinct GPUs — or the rehearsal's shared one)
@@ -448,16 +482,18 @@ def main():
         multi = {"collective": {"torch_distributed_backend": str(dist.get_backend()), "world_size": int(dist.get_world_size()),
                                 "is_rccl": str(dist.get_backend()) == "nccl" and bool(getattr(torch.version, "hip", None)),
                                 "shared_device_rehearsal": bool(share), "ranks": devs},
-                 "merge_every": args.merge_every, "windows_profiled": tm["windows"],
-                 "compute_ms_per_window": tm["compute_ms"] / max(tm["windows"], 1),
-                 "exchange_ms_per_window": tm["exchange_ms"] / max(tm["windows"], 1),
-                 "exchange_bytes_per_window": tm["exchange_bytes_per_window"],
-                 "shared_slots": int(info.shared_slots), "n_nodes": g.n_nodes,
-                 "payload": "f64" if args.payload_f64 else "f32", "rank0_quota": int(info.quota),
-                 "note": "compute = this rank's kernels of the window + packing its moves; exchange = the all-reduce of "
-                         "[delta, touched] over the shared slots + applying it"}
+                 "merge_every": args.merge_every}
+        if tm is not None:
+            multi.update(windows_profiled=tm["windows"], compute_ms_per_window=tm["compute_ms"] / max(tm["windows"], 1),
+                         exchange_ms_per_window=tm["exchange_ms"] / max(tm["windows"], 1))
+        multi.update(exchange_bytes_per_window=runner.timing["exchange_bytes_per_window"],
+                     shared_slots=int(info.shared_slots), n_nodes=g.n_nodes,
+                     payload="f64" if args.payload_f64 else "f32", rank0_quota=int(info.quota))
+        if tm is not None:
+            multi["note"] = ("compute = this rank's kernels of the window + packing its moves; exchange = the all-reduce of "
+                             "[delta, touched] over the shared slots + applying it")
         # second measurement, same run: merge windows of 4 iterations (one fused launch + one exchange per window)
-        if args.merge_every == 1:
+        if args.full and args.merge_every == 1:
             from gfasort_amd.distributed import _Windows
             runner.windows = _Windows(p.iter_max, 4, True)
             runner.reset_streams()
@@ -484,7 +520,7 @@ def main():
             runner.windows = _Windows(p.iter_max, args.merge_every, True)
         # second leg: the layout step (`-p L --dimensions 2`) of the same graph, sharded the same way: coordinates of both ends
         # of the shared slots are exchanged per iteration (2 planes x 2 dims); a few iterations are enough for a rate
-        if not args.no_layout_leg:
+        if args.full and not args.no_layout_leg:
             from gfasort_amd import params as PP, sgd as SS
             pl = PP.LayoutSGDParams.from_graph(g, 2, 1)
             lay = RankDriver(g, pl, rank, world, dims=2, device_index=local_rank, streams_per_rank=args.streams,
@@ -509,7 +545,7 @@ def main():
             lay.close()
             sync_all()
         # the same workload on ONE GPU (rank 0's), so that the scaling of THIS workload can be read off this line
-        if rank == 0:
+        if args.full and rank == 0:
             ctx1 = hip.Context(g, device=local_rank)
             ctx1.setup_1d(p, hip.make_config(n_streams=args.streams, flags=args.flags | hip.F_BUNDLE(args.bundle), block_size=args.block))
             ctx1.init_positions()
@@ -589,11 +625,11 @@ def main():
         }
         if multi is not None:
             out["multi_gpu"] = multi
-        if world == 1 and not args.no_extra_legs:
+        if world == 1 and args.full and not args.no_extra_legs:
             legs = ["quality", "bubbles"] + (["reference_streams"] if int(st1.bundle) != 1 else []) + ["layout_2d"]
             for name in legs:
                 out[name] = run_leg(name, args)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             wc = wall_clock_legs(g)
             out["wall_clock_pY"], out["wall_clock_pL"] = wc["Y"], wc["L"]
             out["cpu_baseline"] = cpu_baseline(g, p)

@@ -1,5 +1,5 @@
 import os, sys
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gfasort_amd import graph as G, params as P, hip, sgd as S
 g = G.synth_windows(1_000_000, 64, 156_250, 2)
 ctx = hip.Context(g)

@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline $@"      # the driver runs: bench.py --gpus 1 --steps 20 --warmup 5
+ARGS="--steps 20 --warmup 5 --full --no-cpu-baseline $@"      # the headline command: bench.py --gpus 1 --steps 20 --warmup 5, plus the extra legs
 PARGS="$ARGS --no-extra-legs"                               # counter passes: the timed region only
 cd $ROOT
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py $ARGS > $OUT/bench_trace.json 2> $OUT/trace.err

@@ -1,6 +1,6 @@
 import os, sys
 import numpy as np
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from util import O, G, P, load, oracle_graph
 from gfasort_amd import hip, quality as Q, sgd as S
