@@ -337,6 +337,7 @@ struct gfs_ctx {
     uint32_t chain = 1;                // longest run in trips (sgd_device.h run_trips); 1 = a run is one trip
     bool lds_tables = true, atomic_loads = true;
     size_t lds_bytes = 0;
+    int32_t kshift_override = -1;      // test hook gfs_ctx_debug_kshift: >= 0 replaces the crowding onset of fill_kargs
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     size_t events_used = 0;
@@ -878,6 +879,7 @@ static void fill_kargs(const gfs_ctx *c, gfs::KArgs &a) {
         int lg = 0; while ((per >> (lg + 1)) != 0) ++lg;               // floor(log2(max(per, 1)))
         a.kshift = lg + 2;
     }
+    if (c->kshift_override >= 0) a.kshift = c->kshift_override;
 }
 
 static int next_event_pair(gfs_ctx *c, std::pair<hipEvent_t, hipEvent_t> *&ev) {
@@ -1097,6 +1099,28 @@ int gfs_ctx_trace(gfs_ctx *c, gfs_term *out, uint64_t n_terms, uint64_t *counts,
         std::vector<uint32_t> tmp(c->n_streams);
         HIPCHK(hipMemcpy(tmp.data(), c->d_trace_cnt, tmp.size() * 4, hipMemcpyDeviceToHost));
         for (uint64_t t = 0; t < c->n_streams; ++t) counts[t] = tmp[t];
+    }
+    return GFS_OK;
+}
+
+// ---- test hooks ----
+int gfs_ctx_debug_step_records(const gfs_ctx *c, uint32_t *out, uint64_t n_words) {
+    if (!c || !out) return fail(GFS_E_ARG, "null argument");
+    if (n_words != 4 * (c->n_steps + 1)) return fail(GFS_E_ARG, "step records length mismatch");
+    if (!c->d_step_rec) return fail(GFS_E_STATE, "no step records");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, c->d_step_rec, (c->n_steps + 1) * sizeof(uint4), hipMemcpyDeviceToHost));
+    return GFS_OK;
+}
+int gfs_ctx_debug_kshift(gfs_ctx *c, int32_t set, int32_t *kshift_out) {
+    if (!c) return fail(GFS_E_ARG, "ctx is null");
+    if (set >= -1) c->kshift_override = set;                              // (set < -1: a query only)
+    if (kshift_out) {
+        if (!c->configured || !c->n_streams) return fail(GFS_E_STATE, "context not set up");
+        gfs::KArgs a{};
+        fill_kargs(c, a);
+        *kshift_out = a.kshift;
     }
     return GFS_OK;
 }

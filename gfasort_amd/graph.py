@@ -53,7 +53,7 @@ class FlatGraph:
         lens = np.where(self.step_node == NO_NODE, 0,
                         self.node_len[np.minimum(self.step_node, max(self.n_nodes - 1, 0))]
                         if self.n_nodes else 0).astype(np.uint64)
-        csum = np.concatenate([[0], np.cumsum(lens, dtype=np.uint64)])
+        csum = np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(lens, dtype=np.uint64)])   # (not [0]: int64 + uint64 is f64)
         first = self.path_first_step.astype(np.int64)
         path_of_step = np.repeat(np.arange(self.n_paths), np.diff(first))
         pos = csum[:-1] - csum[first[:-1]][path_of_step] if self.n_steps else csum[:-1]

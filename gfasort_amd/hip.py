@@ -98,6 +98,7 @@ EXPORTS = [
     "gfs_rank_positions_changed", "gfs_rank_get_positions", "gfs_rank_exchange_count", "gfs_rank_exchange_buffer",
     "gfs_rank_bind_exchange_buffer", "gfs_rank_window_begin", "gfs_rank_window_end", "gfs_rank_finish_begin",
     "gfs_rank_finish_buffer", "gfs_rank_finish_end", "gfs_rank_run",
+    "gfs_ctx_debug_step_records", "gfs_ctx_debug_kshift",
 ]
 
 _lib = None
@@ -140,6 +141,8 @@ def lib():
         L.gfs_ctx_sort_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.gfs_ctx_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
         L.gfs_ctx_node_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.gfs_ctx_debug_step_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.gfs_ctx_debug_kshift.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.gfs_ctx_setup_1d.argtypes = [C.c_void_p] + [C.c_void_p] * 4
         L.gfs_ctx_setup_nd.argtypes = [C.c_void_p] + [C.c_void_p] * 4
         L.gfs_sort_order.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -496,6 +499,20 @@ class Context:
         counts = np.zeros(T, dtype=np.uint64)
         check(lib().gfs_ctx_trace(self._h, _ptr(out), T * k, _ptr(counts), T))
         return out.reshape(T, k), counts
+
+    # ---- test hooks ----
+    def step_records(self):
+        """The device step records, padding record included: uint32 array of shape (n_steps + 1, 4)."""
+        out = np.zeros((self.graph.n_steps + 1, 4), dtype=np.uint32)
+        check(lib().gfs_ctx_debug_step_records(self._h, _ptr(out), C.c_uint64(out.size)))
+        return out
+
+    def kshift(self, set=None):
+        """Crowding onset the kernels are handed (needs a set-up context).  set: an int >= 0 overrides it for every
+        later launch of this context, -1 restores the policy; None leaves it as it is."""
+        v = C.c_int32(0)
+        check(lib().gfs_ctx_debug_kshift(self._h, C.c_int32(-2 if set is None else int(set)), C.byref(v)))
+        return int(v.value)
 
 
 # ---- one-shot entry points ---------------------------------------------------------------------

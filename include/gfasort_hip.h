@@ -235,6 +235,13 @@ int   gfs_ctx_stats(gfs_ctx *ctx, gfs_stats *out);               /* synchronises
 /* rank order of the context's current 1D positions, sorted on the device (rocPRIM radix sort)   */
 int   gfs_ctx_sort_order(gfs_ctx *ctx, uint64_t *order, uint64_t n_nodes);
 int   gfs_ctx_trace(gfs_ctx *ctx, gfs_term *out, uint64_t n_terms, uint64_t *counts, uint64_t n_streams);
+/* ---- test hooks (not part of the integration surface) ----
+ * the n_steps + 1 16-byte step records (the last one is the zeroed padding record) as 4 u32 words each;
+ * n_words must be 4 * (n_steps + 1) */
+int   gfs_ctx_debug_step_records(const gfs_ctx *ctx, uint32_t *out, uint64_t n_words);
+/* crowding onset: set >= 0 overrides the kshift of every later launch of this context, set = -1 restores the policy,
+ * set < -1 changes nothing; *kshift_out (nullable) receives the value the kernels are handed (the context must be set up) */
+int   gfs_ctx_debug_kshift(gfs_ctx *ctx, int32_t set, int32_t *kshift_out);
 
 /* ---- multi-device runs (no reference equivalent: the reference is one process, src/sgd.rs:413-593) ----
  * Paths are sharded over `world` ranks, one rank per GPU (one process per GPU, or one host thread per GPU); every rank

@@ -433,9 +433,13 @@ sample_pair(const pidx *pi, const int flat, const zipf_env *z, const iter_state 
 
 /* 1D term — sgd.rs:505-576.  xa/xb are the position slots; `atomic`: relaxed atomics like the
  * reference's AtomicU64 (threaded mode) or plain doubles (deterministic mode). */
+/* Crowding (product only, not in the reference: gfasort_amd/csrc/sgd_device.h crowd_shift): a term's mu is scaled by 2^-ck
+ * after the clamp, mu = ldexp(fmin(eta / d, 1), -ck).  ck = 0 everywhere the reference is restated. */
+static inline double crowd_mu(double mu, int ck) { return ck ? ldexp(mu, -ck) : mu; }
+
 static inline __attribute__((always_inline)) int
-term_1d(const pidx *pi, const int flat, const iter_state *it, uint64_t sa, uint64_t sb,
-        double *x, const int atomic, _Atomic uint64_t *delta_max, gfo_term *tr) {
+term_1d_ck(const pidx *pi, const int flat, const iter_state *it, const int ck, uint64_t sa, uint64_t sb,
+           double *x, const int atomic, _Atomic uint64_t *delta_max, gfo_term *tr) {
     double pos_a, pos_b; uint64_t i, j;
     if (flat) {
         pos_a = (double)pi->rec[sa].pos; pos_b = (double)pi->rec[sb].pos;
@@ -447,6 +451,7 @@ term_1d(const pidx *pi, const int flat, const iter_state *it, uint64_t sa, uint6
     double term_weight = 1.0 / term_dist;                             /* :518 */
     double mu = it->eta * term_weight;                                /* :519 */
     mu = fmin(mu, 1.0);                                               /* :520 f64::min ignores a NaN operand, like fmin */
+    mu = crowd_mu(mu, ck);
     if (flat) {
         uint32_t ni = pi->rec[sa].node, nj = pi->rec[sb].node;
         if (ni == GFO_NO_NODE || nj == GFO_NO_NODE) return 0;
@@ -490,12 +495,17 @@ term_1d(const pidx *pi, const int flat, const iter_state *it, uint64_t sa, uint6
     if (tr) { tr->i = (uint32_t)i; tr->j = (uint32_t)j; tr->d_ij = term_dist; }
     return 1;
 }
+static inline __attribute__((always_inline)) int
+term_1d(const pidx *pi, const int flat, const iter_state *it, uint64_t sa, uint64_t sb,
+        double *x, const int atomic, _Atomic uint64_t *delta_max, gfo_term *tr) {
+    return term_1d_ck(pi, flat, it, 0, sa, sb, x, atomic, delta_max, tr);
+}
 
 /* nD term — sgd.rs:1043-1149.  coords in Layout order [node][end][dim]. */
 #define GFO_MAX_DIMS 16
 static inline __attribute__((always_inline)) int
-term_nd(const pidx *pi, const int flat, const iter_state *it, uint64_t rng[4], uint64_t sa, uint64_t sb,
-        double *c, const uint64_t D, const int atomic, _Atomic uint64_t *delta_max, gfo_term *tr) {
+term_nd_ck(const pidx *pi, const int flat, const iter_state *it, const int ck, uint64_t rng[4], uint64_t sa, uint64_t sb,
+           double *c, const uint64_t D, const int atomic, _Atomic uint64_t *delta_max, gfo_term *tr) {
     double pos_a, pos_b, len_i, len_j; int rev_i, rev_j; int64_t li, lj;
     if (flat) {
         pos_a = (double)pi->rec[sa].pos; pos_b = (double)pi->rec[sb].pos;
@@ -520,7 +530,7 @@ term_nd(const pidx *pi, const int flat, const iter_state *it, uint64_t rng[4], u
     else                 { use_other_end_b = rev_j; }
     double term_dist = fabs(pos_a - pos_b);                           /* :1080 */
     if (term_dist == 0.0) return 0;
-    double mu = fmin(it->eta * (1.0 / term_dist), 1.0);               /* :1085-1086 */
+    double mu = crowd_mu(fmin(it->eta * (1.0 / term_dist), 1.0), ck); /* :1085-1086 */
     if (!flat) {
         li = hmap_get(pi, pi->step_to_handle[sa] & ~1ull);            /* :1089 */
         if (li < 0) return 0;
@@ -567,6 +577,11 @@ term_nd(const pidx *pi, const int flat, const iter_state *it, uint64_t rng[4], u
     if (tr) { tr->i = (uint32_t)idx_i; tr->j = (uint32_t)idx_j; tr->d_ij = term_dist; }
     return 1;
 }
+static inline __attribute__((always_inline)) int
+term_nd(const pidx *pi, const int flat, const iter_state *it, uint64_t rng[4], uint64_t sa, uint64_t sb,
+        double *c, const uint64_t D, const int atomic, _Atomic uint64_t *delta_max, gfo_term *tr) {
+    return term_nd_ck(pi, flat, it, 0, rng, sa, sb, c, D, atomic, delta_max, tr);
+}
 
 /* iteration constants: batch k uses etas[k]; cooling for k > floor(cooling_start*iter_max)
  * (sgd.rs:297, 383-396): eta/theta/cooling are switched when the checker moves to new_iter=k. */
@@ -603,6 +618,8 @@ struct gfo_state {
     uint8_t *lead_flips;                                      /* nD: the end flips every leader of the pass drew (bit 0: a, 1: b, 2: the second partner's b) */
     uint32_t *node_slot;                                     /* bundled mode: the product's internal node layout (line-aligned runs) */
     gfo_term *trace; uint64_t trace_per_stream;
+    int crowd_on; int64_t kshift;                             /* mirror of the product's crowding (gfo_state_set_crowding) */
+    uint8_t *crowd_a, *crowd_b;                               /* per dense node: gfo_node_crowding */
     uint64_t total_upd, total_att, iterations;
     double seconds;
 };
@@ -612,6 +629,7 @@ void gfo_state_destroy(gfo_state *s) {
     pidx_free(&s->pi);
     free(s->etas); free(s->zetas); free(s->rng); free(s->done); free(s->att); free(s->ntr);
     free(s->lead); free(s->lead_left); free(s->lead_cool); free(s->lead_colour); free(s->lead_seg); free(s->lead_p); free(s->lead_flips); free(s->node_slot);
+    free(s->crowd_a); free(s->crowd_b);
     free(s);
 }
 
@@ -725,6 +743,73 @@ int gfo_state_set_no_fused_trip(gfo_state *s, int on) {
     return 0;
 }
 
+/* Crowding statistics of the nodes, from the rule: a[n] = ceil(log2(steps on n)), b[n] = ceil(log2(the most
+ * visits to n inside any window of 64 consecutive steps of one path)), clamped to 63 and 7 as the product's step records
+ * keep them; 0 for a node no step visits.  Computed here with a sliding window per path, not as the product does it. */
+static uint8_t ceil_log2_u64(uint64_t v) { uint8_t k = 0; while (k < 64 && (1ull << k) < v) k++; return k; }
+int gfo_node_crowding(const gfo_graph *g, uint8_t *a, uint8_t *b) {
+    const uint64_t N = g->n_nodes;
+    uint64_t *cnt = (uint64_t *)calloc(N ? N : 1, 8);
+    uint32_t *win = (uint32_t *)calloc(N ? N : 1, 4), *rep = (uint32_t *)calloc(N ? N : 1, 4);
+    if (!cnt || !win || !rep) { free(cnt); free(win); free(rep); return -2; }
+    for (uint64_t p = 0; p < g->n_paths; p++) {
+        const uint64_t first = g->path_first_step[p], end = g->path_first_step[p + 1];
+        for (uint64_t s = first; s < end; s++) {                     /* window [max(first, s - 63), s] */
+            const uint32_t n = g->step_node[s];
+            if (s >= first + 64 && g->step_node[s - 64] != GFO_NO_NODE) win[g->step_node[s - 64]]--;
+            if (n == GFO_NO_NODE) continue;
+            cnt[n]++;
+            if (++win[n] > rep[n]) rep[n] = win[n];
+        }
+        for (uint64_t s = end > first + 64 ? end - 64 : first; s < end; s++)   /* empty the window */
+            if (g->step_node[s] != GFO_NO_NODE) win[g->step_node[s]]--;
+    }
+    for (uint64_t n = 0; n < N; n++) {
+        const uint8_t ea = ceil_log2_u64(cnt[n]), eb = ceil_log2_u64(rep[n]);
+        if (a) a[n] = ea > 63 ? 63 : ea;
+        if (b) b[n] = eb > 7 ? 7 : eb;
+    }
+    free(cnt); free(win); free(rep);
+    return 0;
+}
+
+int gfo_state_set_crowding(gfo_state *s, int64_t kshift) {
+    if (!s) return -1;
+    s->crowd_on = kshift >= 0;
+    s->kshift = kshift;
+    if (s->crowd_on && !s->crowd_a) {
+        const uint64_t S = s->pi.n_steps, P = s->pi.n_paths;
+        uint32_t *step_node = (uint32_t *)malloc((S ? S : 1) * 4);
+        uint64_t *first = (uint64_t *)malloc((P + 1) * 8);
+        s->crowd_a = (uint8_t *)malloc(s->pi.n_nodes ? s->pi.n_nodes : 1);
+        s->crowd_b = (uint8_t *)malloc(s->pi.n_nodes ? s->pi.n_nodes : 1);
+        int rc = step_node && first && s->crowd_a && s->crowd_b ? 0 : -2;
+        if (!rc) {
+            for (uint64_t t = 0; t < S; t++) step_node[t] = s->pi.rec[t].node;
+            for (uint64_t q = 0; q < P; q++) first[q] = s->pi.paths[q].first_step;
+            first[P] = S;
+            const gfo_graph g = { s->pi.n_nodes, S, P, s->pi.node_len, step_node, NULL, first };
+            rc = gfo_node_crowding(&g, s->crowd_a, s->crowd_b);
+        }
+        free(step_node); free(first);
+        if (rc) { free(s->crowd_a); free(s->crowd_b); s->crowd_a = s->crowd_b = NULL; s->crowd_on = 0; return rc; }
+    }
+    return 0;
+}
+/* the shift of a term between dense nodes i and j: reference streams (runs = 0) max(a_i, a_j) - kshift, team kernels
+ * (runs = 1) max(b_i, b_j, a_i - kshift, a_j - kshift); never below 0.  An absent node has no exponents. */
+static inline int crowd_k(const gfo_state *s, uint32_t i, uint32_t j, int runs) {
+    if (!s->crowd_on) return 0;
+    const int64_t ai = i == GFO_NO_NODE ? 0 : s->crowd_a[i], aj = j == GFO_NO_NODE ? 0 : s->crowd_a[j];
+    int64_t k = (ai > aj ? ai : aj) - s->kshift;
+    if (runs) {
+        const int64_t bi = i == GFO_NO_NODE ? 0 : s->crowd_b[i], bj = j == GFO_NO_NODE ? 0 : s->crowd_b[j];
+        if (bi > k) k = bi;
+        if (bj > k) k = bj;
+    }
+    return k > 0 ? (int)k : 0;
+}
+
 /* nD term with the two end flips already drawn (team mode): same arithmetic as term_nd. */
 static int nd_prepare(const pidx *pi, uint64_t sa, uint64_t sb, int fa, int fb,
                       double *term_dist, uint64_t *idx_i, uint64_t *idx_j) {
@@ -744,11 +829,11 @@ static int nd_term_ok(const pidx *pi, uint64_t sa, uint64_t sb, int fa, int fb) 
     double td; uint64_t i, j;
     return nd_prepare(pi, sa, sb, fa, fb, &td, &i, &j);
 }
-static int term_nd_flips(const pidx *pi, const iter_state *it, int fa, int fb, uint64_t sa, uint64_t sb,
+static int term_nd_flips(const pidx *pi, const iter_state *it, int ck, int fa, int fb, uint64_t sa, uint64_t sb,
                          double *c, uint64_t D, gfo_term *tr) {
     double term_dist; uint64_t idx_i, idx_j;
     if (!nd_prepare(pi, sa, sb, fa, fb, &term_dist, &idx_i, &idx_j)) return 0;
-    double mu = fmin(it->eta * (1.0 / term_dist), 1.0);
+    double mu = crowd_mu(fmin(it->eta * (1.0 / term_dist), 1.0), ck);
     double *ci = c + idx_i * D, *cj = c + idx_j * D;
     double deltas[GFO_MAX_DIMS], mag_sq = 0.0;
     for (uint64_t d = 0; d < D; d++) { deltas[d] = ci[d] - cj[d]; mag_sq += deltas[d] * deltas[d]; }
@@ -883,7 +968,7 @@ static int fused_trip_1d(gfo_state *s, const iter_state *it, const leader_t *ld,
             r[l] = 0.0;
             if (!valid[l]) continue;
             const double xj = out[l] ? xp[l] : xo[l + sh];
-            const double mu = fmin(it->eta * (1.0 / td[l]), 1.0);                      /* :518-520 */
+            const double mu = crowd_mu(fmin(it->eta * (1.0 / td[l]), 1.0), crowd_k(s, node[l], pnode[l], 1));   /* :518-520 */
             double dx = xo[l] - xj;                                                    /* :543 */
             if (dx == 0.0) dx = 1e-9;                                                  /* :546-548 */
             const double mag = fabs(dx);                                               /* :551 */
@@ -944,7 +1029,7 @@ static int twin_trip_1d(gfo_state *s, const iter_state *it, const leader_t *ld, 
         *wave_done += nvalid < remaining ? nvalid : remaining;
         for (int l = 0; l < 64; l++) {
             if (!valid[l]) continue;
-            const double mu = fmin(it->eta * (1.0 / td[l]), 1.0);                      /* :518-520 */
+            const double mu = crowd_mu(fmin(it->eta * (1.0 / td[l]), 1.0), crowd_k(s, na[l], np[q][l], 1));   /* :518-520 */
             double dx = xa[l] - xp[q][l];                                              /* :543 */
             if (dx == 0.0) dx = 1e-9;                                                  /* :546-548 */
             const double mag = fabs(dx);                                               /* :551 */
@@ -1001,7 +1086,8 @@ static int twin_trip_nd(gfo_state *s, const iter_state *it, const leader_t *ld, 
         *wave_done += nvalid < remaining ? nvalid : remaining;
         for (int l = 0; l < 64; l++) {
             if (!valid[l]) continue;
-            const double mu = fmin(it->eta * (1.0 / td[q][l]), 1.0);                   /* sgd.rs:1085-1086 */
+            const double mu = crowd_mu(fmin(it->eta * (1.0 / td[q][l]), 1.0),
+                                       crowd_k(s, (uint32_t)(ia[l] >> 1), (uint32_t)(ip[q][l] >> 1), 1));   /* sgd.rs:1085-1086 */
             double deltas[GFO_MAX_DIMS], mag_sq = 0.0;
             for (uint64_t d = 0; d < D; d++) { deltas[d] = ca[l][d] - cp[q][l][d]; mag_sq += deltas[d] * deltas[d]; }   /* :1108-1113 */
             if (mag_sq == 0.0) { deltas[0] = 1e-9; mag_sq = 1e-18; }                   /* :1116-1119 */
@@ -1076,7 +1162,8 @@ static int fused_trip_nd(gfo_state *s, const iter_state *it, const leader_t *ld,
             for (uint64_t d = 0; d < D; d++) r[l][d] = 0.0;
             if (!valid[l]) continue;
             const double *cj = out[l] ? cp[l] : (fa != fb ? cb[l + sh] : ca[l + sh]);
-            const double mu = fmin(it->eta * (1.0 / td[l]), 1.0);                      /* :1085-1086 */
+            const double mu = crowd_mu(fmin(it->eta * (1.0 / td[l]), 1.0),
+                                       crowd_k(s, (uint32_t)(ia[l] >> 1), (uint32_t)(ij[l] >> 1), 1));   /* :1085-1086 */
             double deltas[GFO_MAX_DIMS], mag_sq = 0.0;
             for (uint64_t d = 0; d < D; d++) { deltas[d] = ca[l][d] - cj[d]; mag_sq += deltas[d] * deltas[d]; }   /* :1108-1113 */
             if (mag_sq == 0.0) { deltas[0] = 1e-9; mag_sq = 1e-18; }                   /* :1116-1119 */
@@ -1273,8 +1360,9 @@ static int run_iteration_bundled(gfo_state *s, uint64_t k, double *x) {
                     if (!valid[l]) continue;
                     if (rank++ >= remaining) continue;
                     gfo_term tr;
-                    if (s->D) (void)term_nd_flips(pi, &it, flips_a[l], flips_b[l], sa[l], sb[l], x, s->D, &tr);
-                    else (void)term_1d(pi, 1, &it, sa[l], sb[l], x, 0, NULL, &tr);
+                    const int ck = crowd_k(s, pi->rec[sa[l]].node, pi->rec[sb[l]].node, 1);
+                    if (s->D) (void)term_nd_flips(pi, &it, ck, flips_a[l], flips_b[l], sa[l], sb[l], x, s->D, &tr);
+                    else (void)term_1d_ck(pi, 1, &it, ck, sa[l], sb[l], x, 0, NULL, &tr);
                     uint64_t tg = wave_first + l;
                     s->done[tg]++;
                     if (s->trace && s->ntr[tg] < s->trace_per_stream) s->trace[tg * s->trace_per_stream + s->ntr[tg]++] = tr;
@@ -1312,8 +1400,9 @@ int gfo_state_run_iteration(gfo_state *s, uint64_t k, double *x) {
             uint64_t sa, sb;
             if (!sample_pair(&s->pi, 1, &s->z, &it, s->rng + 4 * t, &sa, &sb)) continue;
             gfo_term tr;
-            int ok = D ? term_nd(&s->pi, 1, &it, s->rng + 4 * t, sa, sb, x, D, 0, NULL, &tr)
-                       : term_1d(&s->pi, 1, &it, sa, sb, x, 0, NULL, &tr);
+            const int ck = crowd_k(s, s->pi.rec[sa].node, s->pi.rec[sb].node, 0);
+            int ok = D ? term_nd_ck(&s->pi, 1, &it, ck, s->rng + 4 * t, sa, sb, x, D, 0, NULL, &tr)
+                       : term_1d_ck(&s->pi, 1, &it, ck, sa, sb, x, 0, NULL, &tr);
             if (!ok) continue;
             s->done[t]++;
             if (s->trace && s->ntr[t] < s->trace_per_stream) s->trace[t * s->trace_per_stream + s->ntr[t]++] = tr;

@@ -134,6 +134,10 @@ int  gfo_state_set_partners(gfo_state *s, int partners, int no_twin);   /* partn
                                                                            in 1D: 2); no_twin: mirror of GFS_F_DBG_NO_TWIN_TRIP */
 /* bundled mode: the product's internal node layout (slot of dense node k), to mirror its line-aligned runs; NULL = identity */
 int  gfo_state_set_node_slots(gfo_state *s, const uint32_t *slot);
+/* mirror of the product's crowding (gfasort_amd/csrc/sgd_device.h crowd_shift; not in the reference): kshift >= 0 scales mu
+ * by 2^-k, k = max(a_i, a_j) - kshift for reference streams, max(b_i, b_j, a_i - kshift, a_j - kshift) in bundled mode, never
+ * below 0; kshift < 0: off (the default) */
+int  gfo_state_set_crowding(gfo_state *s, int64_t kshift);
 int  gfo_state_run_iteration(gfo_state *s, uint64_t k, double *x);
 void gfo_state_stats(const gfo_state *s, gfo_stats *st);
 void gfo_state_destroy(gfo_state *s);
@@ -146,6 +150,10 @@ int gfo_sgd_1d_threads(const gfo_graph *g, const gfo_params *p, const double *et
                        const double *zetas, int flat, double max_seconds, double *x, gfo_stats *st);
 int gfo_sgd_nd_threads(const gfo_graph *g, const gfo_params *p, const double *etas,
                        const double *zetas, int flat, double max_seconds, double *coords, gfo_stats *st);
+
+/* ---- crowding exponents per dense node (product only): a = ceil(log2(steps on the node)) <= 63, b = ceil(log2(most visits
+ * in any 64 consecutive steps of one path)) <= 7; a or b may be NULL ---- */
+int gfo_node_crowding(const gfo_graph *g, uint8_t *a, uint8_t *b);
 
 /* ---- quality metrics ---- */
 /* calculate_layout_stress (sgd.rs:1196-1283), seed 12345; coords in Layout order, dims>=1 */

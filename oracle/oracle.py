@@ -73,6 +73,8 @@ def lib():
         L.gfo_layout_stress.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
         L.gfo_stress_1d.restype = C.c_double
         L.gfo_stress_1d.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.gfo_node_crowding.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gfo_state_set_crowding.argtypes = [C.c_void_p, C.c_int64]
         _lib = L
     return _lib
 
@@ -242,7 +244,8 @@ class State:
     """Resumable deterministic run (gfo_state).  bundle > 1 mirrors the product's bundled sampler."""
 
     def __init__(self, g, p, dims=0, n_streams=1, stream_base=0, quota_total=0, attempt_factor=64,
-                 trace_per_stream=0, bundle=1, etas=None, zts=None, node_slots=None, one_colour=False, chain=1, fused_trip=True, partners=1, twin_trip=True, chunk=0):
+                 trace_per_stream=0, bundle=1, etas=None, zts=None, node_slots=None, one_colour=False, chain=1, fused_trip=True, partners=1, twin_trip=True, chunk=0,
+                 crowd_kshift=None):
         self.g, self.p = g, p
         self.trace = np.zeros(n_streams * trace_per_stream, dtype=TERM_DTYPE) if trace_per_stream else None
         self.h = C.c_void_p()
@@ -270,6 +273,10 @@ class State:
             # the product's internal node layout (hip.Context.node_layout()): its bundled sampler aligns runs to it
             slots = np.ascontiguousarray(node_slots, dtype=np.uint32)
             assert lib().gfo_state_set_node_slots(self.h, _ptr(slots)) == 0
+        if crowd_kshift is not None:
+            # the product's crowding rule (not the reference's): mu scaled by 2^-k, kshift as the product's KArgs.kshift
+            assert int(crowd_kshift) >= 0
+            assert lib().gfo_state_set_crowding(self.h, C.c_int64(int(crowd_kshift))) == 0
         self.n_streams, self.trace_per_stream = n_streams, trace_per_stream
 
     def run_iteration(self, k, x):
@@ -294,6 +301,16 @@ class State:
             self.close()
         except Exception:
             pass
+
+
+def node_crowding(g):
+    """Crowding exponents per dense node (product only): (a, b) as uint8 arrays, a = ceil(log2(steps on the node)),
+    b = ceil(log2(most visits within any 64 consecutive steps of a path))."""
+    n = len(g.node_len)
+    a = np.zeros(max(n, 1), dtype=np.uint8)
+    b = np.zeros(max(n, 1), dtype=np.uint8)
+    assert lib().gfo_node_crowding(g.ref, _ptr(a), _ptr(b)) == 0
+    return a[:n], b[:n]
 
 
 def layout_stress(g, dims, coords, samples=10000):

@@ -32,6 +32,19 @@ def test_parse_gfa_node_order_duplicates_and_absent_nodes():
     assert pos.tolist() == [0, 1, 5] and plen.tolist() == [5]         # absent node adds 0 bp (sgd.rs:52-54)
 
 
+def test_step_positions_stay_exact_past_2_to_the_53():
+    """u64 prefix sums end to end: a leading 0 of another integer type would promote the sum to f64."""
+    lens = np.array([0xFFFFFFFF] * 3 + [7], dtype=np.uint32)
+    steps = np.tile(np.arange(4, dtype=np.uint32), 1 << 20)
+    g = G.FlatGraph(node_len=lens, step_node=steps, step_is_rev=np.zeros(steps.size, dtype=np.uint8),
+                    path_first_step=np.array([0, steps.size], dtype=np.uint64), node_ids=np.arange(1, 5, dtype=np.uint64))
+    pos, plen = g.step_positions()
+    assert pos.dtype == np.uint64 and plen.dtype == np.uint64
+    per = 3 * 0xFFFFFFFF + 7
+    assert int(plen[0]) == per << 20 and int(plen[0]) > 1 << 53
+    assert int(pos[-1]) == (per << 20) - 7 and int(pos[-2]) == (per << 20) - 7 - 0xFFFFFFFF
+
+
 def test_parse_gfa_rejects_bad_ids():
     with pytest.raises(ValueError):
         G.parse_gfa("S\tabc\tA\n")

@@ -46,3 +46,114 @@ def gaussian_init(g, dims, seed):
     c0 = O.init_layout_dim0(og, dims).reshape(g.n_nodes, 2, dims)
     c[:, :, 0] = c0[:, :, 0]
     return np.ascontiguousarray(c.reshape(-1))
+
+
+# ---- graphs and a restatement for the crowding exponents and the 55-bit step positions (sgd_device.h crowd_shift) ----
+NO_NODE = 0xFFFFFFFF
+
+
+def graph_from_paths(paths, node_len, rev=None):
+    """FlatGraph from explicit paths (lists of dense node indices or NO_NODE)."""
+    steps = [n for pth in paths for n in pth]
+    first = np.concatenate([[0], np.cumsum([len(pth) for pth in paths])]).astype(np.uint64)
+    node_len = np.asarray(node_len, dtype=np.uint32)
+    is_rev = np.zeros(len(steps), dtype=np.uint8) if rev is None else np.asarray(rev, dtype=np.uint8)
+    return G.FlatGraph(node_len=node_len, step_node=np.asarray(steps, dtype=np.uint32), step_is_rev=is_rev,
+                       path_first_step=first, node_ids=np.arange(1, len(node_len) + 1, dtype=np.uint64),
+                       path_names=[f"p{i}" for i in range(len(paths))])
+
+
+def crowding_edge_graph(seed=5):
+    """One edge case of the crowding statistics per path.  Returns (graph, expected) with expected[name] = (node, cnt, rep)
+    for the named nodes.  Fillers are fresh nodes, visited once."""
+    rng = np.random.default_rng(seed)
+    nxt = [0]
+
+    def fresh(k=1):
+        out = list(range(nxt[0], nxt[0] + k))
+        nxt[0] += k
+        return out
+    named, paths = {}, []
+
+    def node(name):
+        named[name] = fresh()[0]
+        return named[name]
+    a63, a64 = node("dist63"), node("dist64")
+    paths.append(fresh(3) + [a63] + fresh(62) + [a63] + fresh(5) + [a64] + fresh(63) + [a64] + fresh(3))
+    paths.append([])                                                   # empty paths between non-empty ones
+    edge = node("path_edge")                                           # ends one path, starts the next
+    paths.append(fresh(10) + [edge])
+    paths.append([])
+    paths.append([edge] + fresh(10))
+    hole = node("no_node_window")                                      # NO_NODE steps inside a repeat window
+    paths.append(fresh(2) + [hole] + [NO_NODE] * 20 + [hole] + [NO_NODE] * 41 + [hole] + [NO_NODE] * 5 + fresh(2))
+    paths.append([NO_NODE] * 3)                                        # a path of absent nodes only
+    for name, c in (("cnt16", 16), ("cnt17", 17), ("cnt32", 32), ("cnt33", 33)):   # cnt 2^k and 2^k + 1, rep 1
+        n = node(name)
+        pth = []
+        for _ in range(c):
+            pth += [n] + fresh(64)
+        paths.append(pth)
+    for name, c in (("rep2", 2), ("rep4", 4), ("rep5", 5), ("rep8", 8), ("rep9", 9), ("rep64", 64)):   # rep 2^k, 2^k + 1
+        n = node(name)
+        gap = max(1, 64 // c - 1) if c < 64 else 0
+        pth = fresh(2)
+        for _ in range(c):
+            pth += [n] + fresh(gap)
+        paths.append(pth[:2] + pth[2:] + fresh(70))
+    hub = node("hub")                                                  # cnt > 2^16, spread over many paths
+    filler = fresh(3)
+    for _ in range(40):
+        pth = []
+        for _ in range(1700):
+            pth += [hub] + filler
+        paths.append(pth)
+    node_len = rng.integers(1, 17, nxt[0]).astype(np.uint32)
+    g = graph_from_paths(paths, node_len, rev=None)
+    g.step_is_rev = (rng.random(g.n_steps) < 0.3).astype(np.uint8)
+    expected = {"dist63": (2, 2), "dist64": (2, 1), "path_edge": (2, 1), "no_node_window": (3, 3),
+                "cnt16": (16, 1), "cnt17": (17, 1), "cnt32": (32, 1), "cnt33": (33, 1),
+                "rep2": (2, 2), "rep4": (4, 4), "rep5": (5, 5), "rep8": (8, 8), "rep9": (9, 9), "rep64": (64, 64),
+                "hub": (68000, 16)}
+    return g, {k: (named[k],) + v for k, v in expected.items()}
+
+
+def hub_graph(n=3000, n_paths=6, every=4, seed=3):
+    """A chain of n nodes that n_paths paths traverse, each stepping on one hub node after every `every`-th step."""
+    rng = np.random.default_rng(seed)
+    hub = n
+    paths = []
+    for _ in range(n_paths):
+        pth = []
+        for k in range(n):
+            pth.append(k)
+            if k % every == every - 1:
+                pth.append(hub)
+        paths.append(pth)
+    return graph_from_paths(paths, rng.integers(1, 17, n + 1))
+
+
+def np_crowding(g):
+    """Per dense node: cnt (steps on it), rep (most visits within the 63 steps before a step and the step itself, inside its
+    path), and the exponents a = ceil(log2 cnt) <= 63, b = ceil(log2 rep) <= 7 (0 for cnt, rep <= 1)."""
+    sn = g.step_node.astype(np.int64)
+    S = sn.shape[0]
+    present = sn != NO_NODE
+    cnt = np.bincount(sn[present], minlength=g.n_nodes)
+    first = g.path_first_step.astype(np.int64)
+    path_start = np.repeat(first[:-1], np.diff(first)) if S else np.zeros(0, np.int64)
+    c = np.ones(S, dtype=np.int64)
+    idx = np.arange(S)
+    for d in range(1, 64):
+        ok = idx - d >= path_start
+        same = np.zeros(S, dtype=bool)
+        same[d:] = sn[d:] == sn[:-d]
+        c += ok & same & present
+    rep = np.zeros(g.n_nodes, dtype=np.int64)
+    np.maximum.at(rep, sn[present], c[present])
+
+    def clog2(v, hi):
+        v = np.asarray(v, dtype=np.float64)
+        out = np.where(v <= 1, 0, np.ceil(np.log2(np.maximum(v, 1))))
+        return np.minimum(out, hi).astype(np.int64)
+    return cnt, rep, clog2(cnt, 63), clog2(rep, 7)
