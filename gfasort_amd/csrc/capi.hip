@@ -31,6 +31,7 @@ hipError_t warm_module_1d();
 hipError_t prepare_1d_fused(uint32_t bundle, bool lds_tables, int block, size_t lds, int *blocks_per_cu);
 hipError_t warm_module_nd();
 hipError_t warm_module_nd_team();
+hipError_t warm_module_nd_team_wide();
 int nd_team_waves(int dims);
 hipError_t launch_nd_team_fused(int dims, const KArgs &a, const IterConsts *d_its, uint32_t n_iters, bool lds_tables, uint32_t *pool,
                                 dim3 grid, dim3 block, size_t lds, hipStream_t st);
@@ -131,6 +132,7 @@ int gfs_warmup(int device) {
     lap("module index");
     HIPCHK(gfs::warm_module_nd());
     HIPCHK(gfs::warm_module_nd_team());
+    HIPCHK(gfs::warm_module_nd_team_wide());
     lap("modules nd");
     // ... and the copy paths in both directions (the first hipMemcpy of a process sets up its staging
     // buffers and DMA queues: ~0.13 s when it was left to the first upload)
@@ -419,8 +421,8 @@ static uint64_t auto_stream_count(const gfs_ctx *c, bool team) {
     // lanes per CU; 5 waves (96 VGPRs) spill 58 registers and are slower (profiles/r02/two_partners.log).  The fused launch
     // further bounds the count by the workgroups that are resident at once (setup_common).
     // The layout team kernels live on registers (a twin trip holds six records and three ends' coordinates): built for 3 waves
-    // per SIMD (165 VGPRs at D = 2, nothing spilled) = 768 lanes per CU, for 2 at D = 3 (176) = 512 (sgd_kernels_nd_team.hip
-    // nd_team_waves; round 2's kernel needed 203 and ran two).
+    // per SIMD (165 VGPRs at D = 2, nothing spilled) = 768 lanes per CU, for 2 from D = 3 up (176 at D = 3, 192-246 at D = 4..8)
+    // = 512 (sgd_nd_team.h nd_waves_for; round 2's kernel needed 203 and ran two).
     const uint64_t chip = (uint64_t)c->cu_count * ((team && c->dims == 0) ? 1024 : (team && c->dims >= 2) ? 256u * (unsigned)gfs::nd_team_waves(c->dims) : 976);
     // keep >= 8 updates per stream per batch on small graphs
     const uint64_t by_work = ((c->quota_total + 7) / 8 + 63) / 64 * 64;
@@ -450,8 +452,8 @@ static int choose_bundle(gfs_ctx *c, int dims) {
     const bool b_auto = b == 0;
     if (b > 1 && (T % 64 != 0 || (b != 4 && b != 8 && b != 16 && b != 32 && b != 64)))
         return fail(GFS_E_ARG, "bundled sampling needs n_streams % 64 == 0 and a bundle of 4, 8, 16, 32 or 64");
-    if (b > 1 && dims != 0 && (dims > 3 || b == 4))
-        return fail(GFS_E_UNSUPPORTED, "bundled layout kernels exist for 1..3 dimensions and bundles of 8..64");
+    if (b > 1 && dims != 0 && b == 4)
+        return fail(GFS_E_UNSUPPORTED, "bundled layout kernels exist for 1..8 dimensions and bundles of 8..64");
     if (b == 0) {
         // auto (measured: profiles/r03/policy_sweep.log — bubble graphs of 16k...300k nodes, three seeds per cell, the relative
         // error per octave of path distance against reference streams): on graphs of >= 16 384 nodes the widest bundle for
@@ -462,6 +464,8 @@ static int choose_bundle(gfs_ctx *c, int dims) {
         // graphs with 37-99 leader draws per iteration are in that table and are as good as those with thousands; the run
         // length, not the number of leaders, is what the quality follows (bounded below by a floor of 64 leaders, see K).
         // Smaller graphs run reference streams: DRB1 (5k nodes) converged visibly slower with bundles (round 1).
+        // Layouts of 4..8 dimensions keep reference streams: their team kernels (sgd_kernels_nd_team_wide.hip) are reached with an
+        // explicit GFS_F_BUNDLE; whether auto should pick them rests on their rates and quality and is not decided here.
         b = 1;
         if (T % 64 == 0 && dims <= 3 && c->n_nodes >= 16384) {
             for (uint32_t cand : {64u, 32u, 16u, 8u, 4u}) {
@@ -483,15 +487,15 @@ static int choose_bundle(gfs_ctx *c, int dims) {
     // profile of the 2-D layout is already below reference streams' at 16: profiles/r02/quality_probe_layout_k.log)
     const bool k_auto = k == 0;
     if (k == 0) k = dims ? 16 : 64;
-    // Two partners per leader (sgd_device.h Leader): the team kernels at B = 64 (1D; layouts of 2 and 3 dimensions), unless
+    // Two partners per leader (sgd_device.h Leader): the team kernels at B = 64 (1D; layouts of 2 and more dimensions), unless
     // GFS_F_ONE_PARTNER
-    c->partners = (b == 64 && (dims == 0 || dims == 2 || dims == 3) && !(c->cfg.flags & GFS_F_ONE_PARTNER)) ? 2u : 1u;
+    c->partners = (b == 64 && (dims == 0 || dims >= 2) && !(c->cfg.flags & GFS_F_ONE_PARTNER)) ? 2u : 1u;
     // ... auto: and short enough that an iteration still draws >= 64 leaders (a leader stands for up to 64 * K * partners
     // terms): at 16k nodes runs of 32 trips left 37 leaders per iteration and +6 % at path distance 1, runs of 16 (74 leaders)
     // +1 %; from 32k nodes up 37 leaders were within 3 % (same table).  Binds only below ~500k steps.
     // (only where the library picked the bundle as well: an explicit GFS_F_BUNDLE(64) keeps 64 / 16)
     if (k_auto && b_auto && b == 64) while (k > 1 && c->quota_total / (64ull * k * c->partners) < 64) k >>= 1;
-    c->chain = b == 64 ? k : 1;                       // (nD: team kernels exist for D <= 3; checked above)
+    c->chain = b == 64 ? k : 1;
     return GFS_OK;
 }
 
@@ -560,7 +564,7 @@ static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs
         const uint64_t resident = c->fused_resident_blocks * c->block;
         if (!c->cfg.n_streams && T > resident && resident >= 64) c->n_streams = T = resident;
     }
-    if ((dims == 2 || dims == 3) && c->bundle == 64) {
+    if (dims >= 2 && c->bundle == 64) {
         // the layout team kernel's fused launch (K2c): the same residency rule
         int per_cu = 0;
         HIPCHK(gfs::prepare_nd_team_fused(dims, c->bundle, c->lds_tables, (int)c->block, c->lds_bytes, &per_cu));
@@ -582,7 +586,7 @@ static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs
     }
     rc = seed_streams(c);
     if (rc) return rc;
-    if (((dims == 0 && c->bundle >= 16) || ((dims == 2 || dims == 3) && c->bundle == 64) || c->bundle == 1) && c->params.iter_max < (1u << 20)) {
+    if (((dims == 0 && c->bundle >= 16) || (dims >= 2 && c->bundle == 64) || c->bundle == 1) && c->params.iter_max < (1u << 20)) {
         // the whole schedule's per-iteration constants, for fused launches over consecutive iterations
         std::vector<gfs::IterConsts> all(c->params.iter_max + 1);
         for (uint64_t k = 0; k <= c->params.iter_max; ++k) iter_consts(c, k, all[k]);
@@ -928,7 +932,7 @@ int gfs_ctx_run_iteration(gfs_ctx *c, uint64_t k, void *hip_stream) {
 }
 
 // A range of iterations ks[0..n) (each in 0..=iter_max): ONE fused launch for the team kernels (sgd1d_team_fused_kernel; layouts of 2
-// and 3 dimensions: sgdnd_team_fused_kernel) and for reference streams (sgd1d_fused_kernel, sgdnd_fused_kernel); otherwise one launch per iteration.
+// and more dimensions at B = 64: sgdnd_team_fused_kernel) and for reference streams (sgd1d_fused_kernel, sgdnd_fused_kernel); otherwise one launch per iteration.
 int gfs_ctx_run_range(gfs_ctx *c, const uint64_t *ks, uint64_t n, void *hip_stream) {
     if (!c || (!ks && n)) return fail(GFS_E_ARG, "null argument");
     if (!c->configured) return fail(GFS_E_STATE, "context not set up");
@@ -946,7 +950,7 @@ int gfs_ctx_run_range(gfs_ctx *c, const uint64_t *ks, uint64_t n, void *hip_stre
     const bool pool_ok = n_waves <= 0xFFFFFFFFull &&
                          c->quota_total / (c->dims != 0 && c->bundle > 1 ? 1u : gfs::pool_slots((uint32_t)n_waves)) < (1ull << 31);
     const bool free_running = (c->cfg.flags & GFS_F_DBG_FREE_RUNNING) != 0;
-    const bool team_shape = (c->dims == 0 && c->bundle >= 16) || ((c->dims == 2 || c->dims == 3) && c->bundle == 64);   // K1c, K2c
+    const bool team_shape = (c->dims == 0 && c->bundle >= 16) || (c->dims >= 2 && c->bundle == 64);   // K1c, K2c
     const bool team_fusable = team_shape && (pool_ok || free_running) &&
                               (c->n_streams + c->block - 1) / c->block <= c->fused_resident_blocks;   // every workgroup resident
     const bool ref_fusable = c->bundle == 1 && pool_ok;

@@ -28,7 +28,8 @@ static void usage() {
         "Usage: gfasort_hip -i <in.gfa> -o <out.gfa> [-p PIPELINE] [--iter-max N] [-t N] [-v N]\n"
         "                   [--dimensions D] [--layout-out FILE] [--layout-iter N] [--streams N]\n"
         "                   [--io-threads N]   (host threads for GFA text passes; default: available CPUs, <= 16)\n"
-        "                   [--bundle auto|1|4|8|16|32|64]   (sampling bundle; 1 = reference streams)\n"
+        "                   [--bundle auto|1|4|8|16|32|64]   (sampling bundle; 1 = reference streams; 4: -p Y only;\n"
+        "                                   auto gives --dimensions 4..8 reference streams, 8..64 their team kernels)\n"
         "                   [--reference-sampler]   (= --bundle 1: every term sampled independently, as src/sgd.rs:444-497 does;\n"
         "                                            ~8x slower on large graphs.  The default on graphs of >= 16384 nodes samples RUNS of\n"
         "                                            terms; on graphs whose haplotypes differ by kilobases it needs a longer schedule\n"

@@ -99,13 +99,15 @@ typedef struct gfs_launch_config {
                                          of agent-scope relaxed atomic loads                 */
 #define GFS_F_NO_LDS_TABLES 2u        /* keep zeta/path tables in global memory              */
 /* Sampling bundle: n adjacent lanes share ONE sampled (step a, jump) drawn by an ordinary reference
- * stream and take n consecutive steps of the path with the same signed jump (nD, D <= 3: and the same
+ * stream and take n consecutive steps of the path with the same signed jump (nD: and the same
  * pair of end flips), so that record loads, position loads and atomics of a bundle coalesce into a
  * few 64-B requests (gfasort_amd/csrc/sgd_device.h).  n = 1: reference streams, every lane is a
  * reference worker thread.  n = 0 (default): the library picks — 1 for graphs of < 16384 nodes, else the widest
  * bundle (64, 32, ...) for which >= 95 % of the steps lie in paths of at least 4 n steps (measured basis:
- * profiles/r03/policy_sweep.log).  On graphs whose haplotypes disagree by kilobases the bundled sampler needs a longer
- * schedule than the reference's to reach the same quality (tests/test_gpu_quality.py). */
+ * profiles/r03/policy_sweep.log).  Layouts of 4..8 dimensions: auto keeps reference streams (n = 1) — their team kernels
+ * (n = 8..64) are new and measured on few graphs, and switching would change every existing run's output;
+ * an explicit n selects them.  n = 4 is for the 1D sort only.  On graphs whose haplotypes disagree by kilobases the
+ * bundled sampler needs a longer schedule than the reference's to reach the same quality (tests/test_gpu_quality.py). */
 #define GFS_F_BUNDLE(n) (((uint32_t)(n) & 0xFFu) << 16)  /* n in {0 = auto, 1, 4, 8, 16, 32, 64} */
 /* Long runs: with bundles of 64 a sampled (step a, jump) is expanded over k consecutive trips of its wave, i.e. over
  * 64*k consecutive steps (k adapts downwards on short paths).  k = 0 (default): 64 for the 1D sort, 16 for the layout
@@ -114,9 +116,10 @@ typedef struct gfs_launch_config {
 #define GFS_F_CHAIN(k) (((uint32_t)(k) & 0xFFu) << 24)   /* k in {0 = auto, 1, 2, 4, 8, 16, 32, 64} */
 #define GFS_F_NO_FUSE       4u        /* gfs_ctx_run / gfs_ctx_run_range: one launch per iteration even where
                                          a fused persistent launch is possible                        */
-#define GFS_F_ONE_PARTNER   0x10u     /* 1D team kernel at B = 64: one partner draw per leader (default: two — a sampled step a
-                                         with two independent draws of its partner b; where both are line-aligned long jumps
-                                         the two terms of a lane share the loads and the add of their a-side) */
+#define GFS_F_ONE_PARTNER   0x10u     /* team kernels at B = 64 (1D; layouts of 2..8 dimensions): one partner draw per leader
+                                         (default: two — a sampled step a with two independent draws of its partner b; where
+                                         both are line-aligned long jumps the two terms of a lane share the loads and the add
+                                         of their a-side) */
 #define GFS_F_DBG_NO_TWIN_TRIP 0x400u /* diagnostic: the two partners of a leader as two trips even where one would do   */
 #define GFS_F_DBG_FREE_RUNNING 0x20u   /* diagnostic: fused launches with a fixed quota per wave and iteration and no pacing
                                          (round 1's launch; the waves drift apart in the schedule) instead of work pools */
@@ -223,7 +226,7 @@ int   gfs_ctx_reset_streams(gfs_ctx *ctx);                       /* re-seed RNG 
  * k > floor(cooling_start*iter_max) (sgd.rs:297,383-396).  Asynchronous on hip_stream
  * (a hipStream_t, NULL = the default stream).                                               */
 int   gfs_ctx_run_iteration(gfs_ctx *ctx, uint64_t k, void *hip_stream);
-/* iterations ks[0..n): ONE fused persistent launch (the team kernels at their widest bundle: sorts, layouts of 2 and 3
+/* iterations ks[0..n): ONE fused persistent launch (the team kernels at their widest bundle: sorts, layouts of 2..8
  * dimensions; reference streams in any dimension) in which the waves walk the schedule and draw every iteration's exact
  * number of updates from a shared pool; otherwise (narrower bundles, traces, GFS_F_NO_FUSE, more streams than fit on the
  * device at once, an iteration of >= 2^31 updates per pool counter) n launches.  A range of ONE layout iteration is pooled
