@@ -28,6 +28,10 @@ hipError_t launch_1d_ref_fused(const KArgs &a, const IterConsts *d_its, uint32_t
 hipError_t launch_nd_ref_fused(int dims, const KArgs &a, const IterConsts *d_its, uint32_t n_iters, bool lds_tables, uint32_t *pool,
                                dim3 grid, dim3 block, size_t lds, hipStream_t st);
 hipError_t warm_module_1d();
+hipError_t launch_1d_phased_fused(const KArgs &a, const IterConsts *d_its, uint32_t n_iters, bool lds_tables, uint32_t *pool,
+                                  dim3 grid, dim3 block, size_t lds, hipStream_t st);
+hipError_t prepare_1d_phased_fused(bool lds_tables, int block, size_t lds, int *blocks_per_cu);
+hipError_t warm_module_1d_phased();
 hipError_t prepare_1d_fused(uint32_t bundle, bool lds_tables, int block, size_t lds, int *blocks_per_cu);
 hipError_t warm_module_nd();
 hipError_t warm_module_nd_team();
@@ -127,6 +131,7 @@ int gfs_warmup(int device) {
     lap("context");
     // code objects load on first use, one per translation unit: touch each now, and the allocator too
     HIPCHK(gfs::warm_module_1d());
+    HIPCHK(gfs::warm_module_1d_phased());
     lap("module 1d");
     HIPCHK(gfs::warm_module_index());
     lap("module index");
@@ -166,6 +171,28 @@ int gfs_sgd_schedule(const gfs_sgd_params *p, double *etas) {              // sg
         if (d < 0) d = -d;
         etas[t] = eta_max * std::exp(-lambda * (double)d);
     }
+    return GFS_OK;
+}
+
+// The default window of GFS_F_PHASED: around the reference's switch to the cooling phase (sgd.rs:297: cooling for
+// k > first_cooling = floor(cooling_start * iter_max)), scaled with iter_max.  [first_cooling + 1 + lo, first_cooling + 1 + hi)
+// with lo, hi in thousandths of iter_max (hi = kPhaseWindowToEnd: to the end of the schedule), clipped to [0, iter_max + 1).
+// Chosen on DRB1-3123 x120 and a 525k-node bubble graph (profiles/r05/phased_window_probe.log).
+static constexpr int64_t kPhaseWindowLo = 0, kPhaseWindowToEnd = INT64_MAX, kPhaseWindowHi = kPhaseWindowToEnd;
+int gfs_phase_window(const gfs_sgd_params *p, uint64_t *k_begin, uint64_t *k_end) {
+    if (!p || !k_begin || !k_end) return fail(GFS_E_ARG, "null argument");
+    const unsigned __int128 n = p->iter_max, last = n + 1;                 // iterations 0..=iter_max
+    const double fc = std::floor(p->cooling_start * (double)p->iter_max);   // as iter_consts
+    const unsigned __int128 f1 = (!(fc > 0.0) ? 0 : (fc >= 18446744073709551616.0 ? (unsigned __int128)UINT64_MAX : (unsigned __int128)(uint64_t)fc)) + 1;
+    auto at = [&](int64_t per_mille) -> unsigned __int128 {                // f1 + per_mille * iter_max / 1000, clipped to [0, last]
+        if (per_mille == kPhaseWindowToEnd) return last;
+        const unsigned __int128 off = n * (unsigned __int128)(per_mille < 0 ? -per_mille : per_mille) / 1000;
+        const unsigned __int128 v = per_mille < 0 ? (off >= f1 ? 0 : f1 - off) : f1 + off;
+        return v < last ? v : last;
+    };
+    const unsigned __int128 e = at(kPhaseWindowHi), b = std::min(at(kPhaseWindowLo), e);
+    const unsigned __int128 cap = (unsigned __int128)UINT64_MAX;           // (iter_max = 2^64 - 1: iter_max + 1 does not fit)
+    *k_begin = (uint64_t)std::min(b, cap); *k_end = (uint64_t)std::min(e, cap);
     return GFS_OK;
 }
 
@@ -340,6 +367,10 @@ struct gfs_ctx {
     bool lds_tables = true, atomic_loads = true;
     size_t lds_bytes = 0;
     int32_t kshift_override = -1;      // test hook gfs_ctx_debug_kshift: >= 0 replaces the crowding onset of fill_kargs
+    // GFS_F_PHASED (K1e, sgd_kernels_1d_phased.hip): iterations [win_begin, win_end) run reference streams, the others the team
+    // sampler at B = 64.  phased is false where the flag is a no-op (the auto policy picked another bundle).
+    bool phased = false;
+    uint64_t win_begin = 0, win_end = 0;
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     size_t events_used = 0;
@@ -507,8 +538,14 @@ static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs
     int rc = check_params(p);
     if (rc) return rc;
     if (dims < 0 || dims > GFS_MAX_DIMS) return fail(GFS_E_UNSUPPORTED, "dimensions must be 1..8");
+    if (cfg && (cfg->flags & GFS_F_PHASED)) {
+        if (dims != 0) return fail(GFS_E_ARG, "GFS_F_PHASED is a sampler of the 1D sort: layouts have none");
+        const uint32_t b = (cfg->flags >> 16) & 0xFFu;
+        if (b != 0 && b != 64) return fail(GFS_E_ARG, "GFS_F_PHASED switches between reference streams and bundles of 64: GFS_F_BUNDLE must be 0 or 64");
+    }
     HIPCHK(hipSetDevice(c->device));
     free_sgd_state(c);
+    c->phased = false; c->win_begin = c->win_end = 0;
     c->params = *p;
     c->cfg = cfg ? *cfg : gfs_launch_config{};
     c->dims = dims;
@@ -544,6 +581,13 @@ static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs
     rc = choose_bundle(c, dims);
     if (rc) return rc;
     if (!c->cfg.n_streams && c->bundle > 1) c->n_streams = T = auto_stream_count(c, true);   // both counts are multiples of 64
+    if (c->cfg.flags & GFS_F_PHASED) {
+        // the phased sampler where the team sampler at B = 64 runs; where the policy picked reference streams every iteration is
+        // theirs already (the window is the whole schedule, the run the default's), and other bundles have no phased kernel
+        c->phased = c->bundle == 64;
+        if (c->phased) gfs_phase_window(p, &c->win_begin, &c->win_end);
+        else if (c->bundle == 1) { c->win_begin = 0; c->win_end = p->iter_max + 1; }
+    }
     if (dims != 0 && c->bundle > 1 && c->block > 256)
         return fail(GFS_E_ARG, "the layout team kernels are built for workgroups of at most 256 lanes");
     c->atomic_loads = !(c->cfg.flags & GFS_F_PLAIN_LOADS);
@@ -559,7 +603,8 @@ static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs
         // runtime how many fit per CU with this block size and LDS table (33 KB of zeta table = 4 blocks of 256 per CU, not
         // 5), bound the automatic stream count by it, and run one launch per iteration when a caller asks for more streams.
         int per_cu = 0;
-        HIPCHK(gfs::prepare_1d_fused(c->bundle, c->lds_tables, (int)c->block, c->lds_bytes, &per_cu));   // (also: not inside the first launch's event bracket)
+        if (c->phased) HIPCHK(gfs::prepare_1d_phased_fused(c->lds_tables, (int)c->block, c->lds_bytes, &per_cu));
+        else HIPCHK(gfs::prepare_1d_fused(c->bundle, c->lds_tables, (int)c->block, c->lds_bytes, &per_cu));   // (also: not inside the first launch's event bracket)
         c->fused_resident_blocks = (uint64_t)std::max(per_cu, 0) * c->cu_count;
         const uint64_t resident = c->fused_resident_blocks * c->block;
         if (!c->cfg.n_streams && T > resident && resident >= 64) c->n_streams = T = resident;
@@ -610,8 +655,10 @@ static void iter_consts(const gfs_ctx *c, uint64_t k, gfs::IterConsts &it) {
     it.omt_e = h_sat_i32(omt); it.omt_fb = omt - (double)it.omt_e;
     double alpha = 1.0 / (1.0 - theta);                                    // sgd.rs:132
     it.alpha_e = h_sat_i32(alpha); it.alpha_fb = alpha - (double)it.alpha_e;
-    it._pad = 0;
+    it._pad = (c->phased && k >= c->win_begin && k < c->win_end) ? 1 : 0;   // K1e: a window iteration (the other kernels ignore it)
 }
+
+static bool in_window(const gfs_ctx *c, uint64_t k) { return c->phased && k >= c->win_begin && k < c->win_end; }
 
 extern "C" {
 
@@ -916,6 +963,7 @@ int gfs_ctx_run_iteration(gfs_ctx *c, uint64_t k, void *hip_stream) {
     gfs::KArgs a{};
     fill_kargs(c, a);
     iter_consts(c, k, a.it);
+    if (in_window(c, k)) a.bundle = 1;                                     // GFS_F_PHASED: the window's iterations are K1's
     dim3 block(c->block), grid((unsigned)((c->n_streams + c->block - 1) / c->block));
     std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
     int rc = next_event_pair(c, ev);
@@ -951,7 +999,7 @@ int gfs_ctx_run_range(gfs_ctx *c, const uint64_t *ks, uint64_t n, void *hip_stre
                          c->quota_total / (c->dims != 0 && c->bundle > 1 ? 1u : gfs::pool_slots((uint32_t)n_waves)) < (1ull << 31);
     const bool free_running = (c->cfg.flags & GFS_F_DBG_FREE_RUNNING) != 0;
     const bool team_shape = (c->dims == 0 && c->bundle >= 16) || (c->dims >= 2 && c->bundle == 64);   // K1c, K2c
-    const bool team_fusable = team_shape && (pool_ok || free_running) &&
+    const bool team_fusable = team_shape && (c->phased ? pool_ok && !free_running : pool_ok || free_running) &&   // (K1e: pools only)
                               (c->n_streams + c->block - 1) / c->block <= c->fused_resident_blocks;   // every workgroup resident
     const bool ref_fusable = c->bundle == 1 && pool_ok;
     // A range of ONE layout iteration is drawn from the pool too where it is at least four chunks per wave: with fixed quotas a layout
@@ -1029,7 +1077,8 @@ int gfs_ctx_run_range(gfs_ctx *c, const uint64_t *ks, uint64_t n, void *hip_stre
     int rc = next_event_pair(c, ev);
     if (rc) return rc;
     HIPCHK(hipEventRecord(ev->first, st));                // (the event pair brackets the kernel alone)
-    hipError_t e = c->bundle > 1 ? (c->dims == 0 ? gfs::launch_1d_fused(a, d_slice, (uint32_t)n, c->lds_tables, pool, grid, block, c->lds_bytes, st)
+    hipError_t e = c->phased ? gfs::launch_1d_phased_fused(a, d_slice, (uint32_t)n, c->lds_tables, pool, grid, block, c->lds_bytes, st)
+                 : c->bundle > 1 ? (c->dims == 0 ? gfs::launch_1d_fused(a, d_slice, (uint32_t)n, c->lds_tables, pool, grid, block, c->lds_bytes, st)
                                                  : gfs::launch_nd_team_fused(c->dims, a, d_slice, (uint32_t)n, c->lds_tables, pool, grid, block, c->lds_bytes, st))
                    : c->dims == 0 ? gfs::launch_1d_ref_fused(a, d_slice, (uint32_t)n, c->lds_tables, pool, grid, block, c->lds_bytes, st)
                                   : gfs::launch_nd_ref_fused(c->dims, a, d_slice, (uint32_t)n, c->lds_tables, pool, grid, block, c->lds_bytes, st);
@@ -1126,6 +1175,27 @@ int gfs_ctx_debug_kshift(gfs_ctx *c, int32_t set, int32_t *kshift_out) {
         fill_kargs(c, a);
         *kshift_out = a.kshift;
     }
+    return GFS_OK;
+}
+
+int gfs_ctx_phase_window(gfs_ctx *c, int64_t set_begin, int64_t set_end, uint64_t *begin_out, uint64_t *end_out) {
+    if (!c) return fail(GFS_E_ARG, "ctx is null");
+    if (!c->configured || !(c->cfg.flags & GFS_F_PHASED)) return fail(GFS_E_STATE, "context not set up with GFS_F_PHASED");
+    if (set_begin >= 0 || set_end >= 0) {
+        if (set_begin < 0 || set_end < 0 || set_begin > set_end || (uint64_t)set_end > c->params.iter_max + 1)
+            return fail(GFS_E_ARG, "phase window: need 0 <= begin <= end <= iter_max + 1");
+        if (!c->phased) return fail(GFS_E_STATE, "GFS_F_PHASED is a no-op on this context (the auto policy did not pick bundles of 64)");
+        c->win_begin = (uint64_t)set_begin; c->win_end = (uint64_t)set_end;
+        if (c->d_its_all) {                                                // the resident schedule carries the window's marks
+            HIPCHK(hipSetDevice(c->device));
+            HIPCHK(hipDeviceSynchronize());
+            std::vector<gfs::IterConsts> all(c->params.iter_max + 1);
+            for (uint64_t k = 0; k <= c->params.iter_max; ++k) iter_consts(c, k, all[k]);
+            HIPCHK(hipMemcpy(c->d_its_all, all.data(), all.size() * sizeof(gfs::IterConsts), hipMemcpyHostToDevice));
+        }
+    }
+    if (begin_out) *begin_out = c->win_begin;
+    if (end_out) *end_out = c->win_end;
     return GFS_OK;
 }
 

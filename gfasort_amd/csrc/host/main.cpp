@@ -21,6 +21,7 @@ struct Args {
     unsigned verbose = 1;
     uint64_t streams = 0; uint32_t flags = 0;      // HIP launch shape (extra, not in the reference)
     unsigned bundle = 0;                           // 0 = auto, 1 = reference streams, 4..64
+    bool reference_sampler = false, phased = false;
 };
 
 static void usage() {
@@ -34,6 +35,11 @@ static void usage() {
         "                                            ~8x slower on large graphs.  The default on graphs of >= 16384 nodes samples RUNS of\n"
         "                                            terms; on graphs whose haplotypes differ by kilobases it needs a longer schedule\n"
         "                                            (--iter-max 300) to reach what the reference's sampler reaches, DESIGN.md)\n"
+        "                   [--phased-sampler]   (-p Y: the default sampler, but every term of a window of iterations around the\n"
+        "                                       switch to the cooling phase sampled independently as --reference-sampler does;\n"
+        "                                       reaches the reference's quality at the default --iter-max in ~half the time\n"
+        "                                       of --reference-sampler.  Not with --reference-sampler or a --bundle other than\n"
+        "                                       auto or 64; -p L is not affected.  -v 2 prints the window)\n"
         "Pipeline characters: Y = path-guided SGD sort, L = nD layout (HIP engine).\n"
         "g, s, S, u exist in the reference but are not part of this build.\n";
 }
@@ -55,10 +61,16 @@ static bool parse_args(int argc, char **argv, Args &a) {
         else if (f == "--io-threads") { if (!(v = need(i))) return false; set_io_threads(std::stoull(v)); }
         else if (f == "--streams") { if (!(v = need(i))) return false; a.streams = std::stoull(v); }
         else if (f == "--bundle") { if (!(v = need(i))) return false; a.bundle = std::string(v) == "auto" ? 0u : (unsigned)std::stoul(v); }
-        else if (f == "--reference-sampler") { a.bundle = 1; }
+        else if (f == "--reference-sampler") { a.bundle = 1; a.reference_sampler = true; }
+        else if (f == "--phased-sampler") { a.phased = true; }
         else if (f == "--hip-flags") { if (!(v = need(i))) return false; a.flags = (uint32_t)std::stoul(v); }
         else if (f == "-h" || f == "--help") { usage(); exit(0); }
         else { std::cerr << "error: unexpected argument '" << f << "'\n"; return false; }
+    }
+    if (a.phased && (a.reference_sampler || (a.bundle != 0 && a.bundle != 64))) {
+        std::cerr << "error: --phased-sampler switches between the reference sampler and bundles of 64: not with --reference-sampler or --bundle "
+                  << a.bundle << "\n";
+        return false;
     }
     if (a.input.empty() || a.output.empty()) { std::cerr << "error: -i and -o are required\n"; return false; }
     return true;
@@ -129,7 +141,15 @@ int main(int argc, char **argv) {
                           << (c == 'Y' ? std::string("SGD") : std::to_string(args.dimensions) + "D layout") << "\n";
             gfs_stats st{};
             if (c == 'Y') {
-                sgd_sort_only(graph, sgd_params, (uint8_t)args.verbose, opt, &st);          // gfasort.rs:250-252
+                HipOptions opt_y = opt;
+                if (args.phased) opt_y.cfg.flags |= GFS_F_PHASED;
+                sgd_sort_only(graph, sgd_params, (uint8_t)args.verbose, opt_y, &st);        // gfasort.rs:250-252
+                if (args.phased && args.verbose >= 2) {
+                    uint64_t kb = 0, ke = sgd_params.iter_max + 1;         // reference streams picked: the whole schedule is theirs
+                    if (st.bundle == 64) { gfs_sgd_params cp = sgd_params.to_c(); gfs_phase_window(&cp, &kb, &ke); }
+                    std::cerr << "[gfasort_hip] phased sampler: reference streams in iterations [" << kb << ", " << ke << ") of 0.."
+                              << sgd_params.iter_max << "\n";
+                }
             } else {
                 layout = path_linear_sgd_layout(graph, layout_params, opt, &st);            // :265-267
                 have_layout = true;

@@ -345,6 +345,7 @@ int gfs_rank_create(const gfs_graph_view *g, const gfs_sgd_params *p, uint64_t d
     if (cfg->world > GFS_MAX_WORLD) return gfs_set_error(GFS_E_UNSUPPORTED, "world too large");
     if (dims > GFS_MAX_DIMS) return gfs_set_error(GFS_E_UNSUPPORTED, "dimensions must be 1..8");
     if (cfg->merge_rule > 3 || cfg->payload > 1 || cfg->exchange > 1 || cfg->sharding > 2) return gfs_set_error(GFS_E_ARG, "bad rank config");
+    if (cfg->launch.flags & GFS_F_PHASED) return gfs_set_error(GFS_E_ARG, "GFS_F_PHASED is for single-device runs");
     gfs_rank *r = new (std::nothrow) gfs_rank();
     if (!r) return gfs_set_error(GFS_E_NOMEM, "out of memory");
     r->cfg = *cfg; r->params = *p; r->dims = dims; r->n_nodes = g->n_nodes;

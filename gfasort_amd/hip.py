@@ -17,6 +17,7 @@ F_PLAIN_LOADS, F_NO_LDS_TABLES, F_NO_FUSE = 1, 2, 4
 F_DBG_NO_ATOMICS, F_DBG_NO_XLOADS, F_DBG_ONE_COLOUR = 0x100, 0x200, 0x800
 F_DBG_NO_ALIGN, F_DBG_ALIGN_FIRST, F_DBG_WIDE_INDEX, F_DBG_NO_FUSED_TRIP = 0x1000, 0x2000, 0x4000, 0x8000
 F_ONE_PARTNER, F_DBG_NO_TWIN_TRIP, F_DBG_FREE_RUNNING = 0x10, 0x400, 0x20
+F_PHASED = 0x40            # GFS_F_PHASED: the 1D sort's phased sampler (reference streams in a window of iterations)
 
 
 def F_CHAIN(k):
@@ -98,7 +99,7 @@ EXPORTS = [
     "gfs_rank_positions_changed", "gfs_rank_get_positions", "gfs_rank_exchange_count", "gfs_rank_exchange_buffer",
     "gfs_rank_bind_exchange_buffer", "gfs_rank_window_begin", "gfs_rank_window_end", "gfs_rank_finish_begin",
     "gfs_rank_finish_buffer", "gfs_rank_finish_end", "gfs_rank_run",
-    "gfs_ctx_debug_step_records", "gfs_ctx_debug_kshift",
+    "gfs_ctx_debug_step_records", "gfs_ctx_debug_kshift", "gfs_phase_window", "gfs_ctx_phase_window",
 ]
 
 _lib = None
@@ -143,6 +144,8 @@ def lib():
         L.gfs_ctx_node_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.gfs_ctx_debug_step_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.gfs_ctx_debug_kshift.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.gfs_phase_window.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gfs_ctx_phase_window.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
         L.gfs_ctx_setup_1d.argtypes = [C.c_void_p] + [C.c_void_p] * 4
         L.gfs_ctx_setup_nd.argtypes = [C.c_void_p] + [C.c_void_p] * 4
         L.gfs_sort_order.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
@@ -204,6 +207,14 @@ def make_sgd_params(p):
         setattr(s, name, getattr(p, name))
     s.progress = 1 if p.progress else 0
     return s
+
+
+def phase_window(p):
+    """gfs_phase_window: GFS_F_PHASED's default window (k_begin, k_end) for SGD parameters p (host only)."""
+    sp = make_sgd_params(p)
+    b, e = C.c_uint64(0), C.c_uint64(0)
+    check(lib().gfs_phase_window(C.byref(sp), C.byref(b), C.byref(e)))
+    return int(b.value), int(e.value)
 
 
 def make_layout_params(p):
@@ -513,6 +524,13 @@ class Context:
         v = C.c_int32(0)
         check(lib().gfs_ctx_debug_kshift(self._h, C.c_int32(-2 if set is None else int(set)), C.byref(v)))
         return int(v.value)
+
+    def phase_window(self, set_begin=-1, set_end=-1):
+        """GFS_F_PHASED's effective window (begin, end) of this context; set_begin, set_end >= 0 replace it for later launches
+        (a test and probe hook)."""
+        b, e = C.c_uint64(0), C.c_uint64(0)
+        check(lib().gfs_ctx_phase_window(self._h, C.c_int64(int(set_begin)), C.c_int64(int(set_end)), C.byref(b), C.byref(e)))
+        return int(b.value), int(e.value)
 
 
 # ---- one-shot entry points ---------------------------------------------------------------------

@@ -107,7 +107,8 @@ typedef struct gfs_launch_config {
  * profiles/r03/policy_sweep.log).  Layouts of 4..8 dimensions: auto keeps reference streams (n = 1) — their team kernels
  * (n = 8..64) are new and measured on few graphs, and switching would change every existing run's output;
  * an explicit n selects them.  n = 4 is for the 1D sort only.  On graphs whose haplotypes disagree by kilobases the
- * bundled sampler needs a longer schedule than the reference's to reach the same quality (tests/test_gpu_quality.py). */
+ * bundled sampler needs a longer schedule than the reference's to reach the same quality (tests/test_gpu_quality.py), or
+ * GFS_F_PHASED, which reaches it at the default schedule. */
 #define GFS_F_BUNDLE(n) (((uint32_t)(n) & 0xFFu) << 16)  /* n in {0 = auto, 1, 4, 8, 16, 32, 64} */
 /* Long runs: with bundles of 64 a sampled (step a, jump) is expanded over k consecutive trips of its wave, i.e. over
  * 64*k consecutive steps (k adapts downwards on short paths).  k = 0 (default): 64 for the 1D sort, 16 for the layout
@@ -120,6 +121,15 @@ typedef struct gfs_launch_config {
                                          (default: two — a sampled step a with two independent draws of its partner b; where
                                          both are line-aligned long jumps the two terms of a lane share the loads and the add
                                          of their a-side) */
+/* Phased sampler of the 1D sort (gfs_ctx_setup_1d, gfs_path_linear_sgd, gfs_path_sgd_sort): every iteration outside a window
+ * [k_begin, k_end) around the switch to the cooling phase is the team sampler at B = 64; inside it every lane is reference
+ * stream `tid` and draws its terms exactly as GFS_F_BUNDLE(1) does.  Both use the same per-lane RNG states, each continuing
+ * the state the other left; a team pass left over when the window begins is kept and dropped by the team's own rule (the
+ * cooling flag changed) — the oracle's gfo_state with its bundle switched between 64 and 1 between iterations.  n_streams is
+ * the team sampler's.  Where the auto policy picks reference streams (graphs of < 16384 nodes) the flag changes nothing.
+ * Refused (GFS_E_ARG) with gfs_ctx_setup_nd, with a GFS_F_BUNDLE other than 0 or 64, and with gfs_rank_create.  Default
+ * window: gfs_phase_window.  DESIGN.md §3 (K1e) and §5. */
+#define GFS_F_PHASED        0x40u
 #define GFS_F_DBG_NO_TWIN_TRIP 0x400u /* diagnostic: the two partners of a leader as two trips even where one would do   */
 #define GFS_F_DBG_FREE_RUNNING 0x20u   /* diagnostic: fused launches with a fixed quota per wave and iteration and no pacing
                                          (round 1's launch; the waves drift apart in the schedule) instead of work pools */
@@ -226,6 +236,9 @@ int   gfs_ctx_reset_streams(gfs_ctx *ctx);                       /* re-seed RNG 
  * k > floor(cooling_start*iter_max) (sgd.rs:297,383-396).  Asynchronous on hip_stream
  * (a hipStream_t, NULL = the default stream).                                               */
 int   gfs_ctx_run_iteration(gfs_ctx *ctx, uint64_t k, void *hip_stream);
+/* GFS_F_PHASED's default window [*k_begin, *k_end) for these parameters (host only): around first_cooling =
+ * floor(cooling_start * iter_max), scaled with iter_max; always k_begin <= k_end <= iter_max + 1. */
+int   gfs_phase_window(const gfs_sgd_params *p, uint64_t *k_begin, uint64_t *k_end);
 /* iterations ks[0..n): ONE fused persistent launch (the team kernels at their widest bundle: sorts, layouts of 2..8
  * dimensions; reference streams in any dimension) in which the waves walk the schedule and draw every iteration's exact
  * number of updates from a shared pool; otherwise (narrower bundles, traces, GFS_F_NO_FUSE, more streams than fit on the
@@ -245,6 +258,11 @@ int   gfs_ctx_debug_step_records(const gfs_ctx *ctx, uint32_t *out, uint64_t n_w
 /* crowding onset: set >= 0 overrides the kshift of every later launch of this context, set = -1 restores the policy,
  * set < -1 changes nothing; *kshift_out (nullable) receives the value the kernels are handed (the context must be set up) */
 int   gfs_ctx_debug_kshift(gfs_ctx *ctx, int32_t set, int32_t *kshift_out);
+/* GFS_F_PHASED's window: set_begin, set_end >= 0 replace it for later launches (0 <= begin <= end <= iter_max + 1, else
+ * GFS_E_ARG), both < 0 only query; *begin_out / *end_out (nullable) receive the effective window — the whole schedule where the
+ * flag is a no-op (reference streams picked), on which a window cannot be set (GFS_E_STATE).  GFS_E_STATE on a context not set
+ * up with the flag. */
+int   gfs_ctx_phase_window(gfs_ctx *ctx, int64_t set_begin, int64_t set_end, uint64_t *begin_out, uint64_t *end_out);
 
 /* ---- multi-device runs (no reference equivalent: the reference is one process, src/sgd.rs:413-593) ----
  * Paths are sharded over `world` ranks, one rank per GPU (one process per GPU, or one host thread per GPU); every rank
