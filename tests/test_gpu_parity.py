@@ -139,12 +139,16 @@ def test_replay_matches_committed_golden():
             assert hx == ent["x"]
         else:
             assert hx[:32] == ent["x_head"] and hashlib.sha256(x.tobytes()).hexdigest() == ent["x_sha256"]
-    ent = golden["sgd_nd_single_stream"]["DRB1-3123.gfa"]
-    g = load("DRB1-3123.gfa")
-    p = P.LayoutSGDParams.from_graph(g, 2, 1)
-    p.iter_max, p.min_term_updates = ent["iter_max"], ent["min_term_updates"]
-    rc, c, st = hip.path_linear_sgd_layout_raw(g, p, gaussian_init(g, 2, 7), cfg=hip.make_config(n_streams=1))
-    assert hashlib.sha256(c.tobytes()).hexdigest() == ent["coords_sha256"]
+    assert sorted(ent["dims"] for ent in golden["sgd_nd_single_stream"].values()) == [1, 2, 8]
+    for key, ent in golden["sgd_nd_single_stream"].items():
+        dims = ent["dims"]
+        g = load(ent.get("graph", key))
+        p = P.LayoutSGDParams.from_graph(g, dims, 1)
+        p.iter_max, p.min_term_updates = ent["iter_max"], ent["min_term_updates"]
+        rc, c, st = hip.path_linear_sgd_layout_raw(g, p, gaussian_init(g, dims, 7), cfg=hip.make_config(n_streams=1))
+        assert rc == 0 and (st.term_updates, st.attempts) == (ent["term_updates"], ent["attempts"])
+        assert hashlib.sha256(c.tobytes()).hexdigest() == ent["coords_sha256"]
+        assert [format(int(v), "016x") for v in c[:32].view(np.uint64)] == ent["coords_head"]
 
 
 # ---- edge cases the reference handles -----------------------------------------------------------------

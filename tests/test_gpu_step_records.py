@@ -173,7 +173,7 @@ def _g3_graph(name):
 
 
 @pytest.mark.parametrize("name", ["DRB1", "repeats", "hub"])
-@pytest.mark.parametrize("dims", [0, 2, 3])
+@pytest.mark.parametrize("dims", [0, 2, 3, 8])
 def test_reference_streams_a_rule_on_one_stream_equal_the_oracle(name, dims):
     """One stream has no concurrency: with kshift = 0 every term is scaled by 2^-max(a_i, a_j), b is ignored (b > 0 on the
     repeat graph), and K1 / K1d (1D) and K2 / K2d (nD) must equal the oracle's state with crowd_kshift = 0 bit for bit."""

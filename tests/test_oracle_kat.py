@@ -384,14 +384,19 @@ def test_golden_sgd_runs(golden):
             assert _hex(x) == ent["x"]
         else:
             assert _hex(x[:32]) == ent["x_head"] and hashlib.sha256(x.tobytes()).hexdigest() == ent["x_sha256"]
-    ent = golden["sgd_nd_single_stream"]["DRB1-3123.gfa"]
-    g = load("DRB1-3123.gfa")
-    p = P.LayoutSGDParams.from_graph(g, 2, 1)
-    p.iter_max, p.min_term_updates = ent["iter_max"], ent["min_term_updates"]
-    c = gaussian_init(g, 2, 7)
-    rc, st, tr = O.sgd_nd(oracle_graph(g), oracle_params(p), c, n_streams=1, trace_per_stream=8)
-    assert (st.term_updates, st.attempts) == (ent["term_updates"], ent["attempts"])
-    assert _hex(c[:32]) == ent["coords_head"] and hashlib.sha256(c.tobytes()).hexdigest() == ent["coords_sha256"]
+    assert sorted(ent["dims"] for ent in golden["sgd_nd_single_stream"].values()) == [1, 2, 8]
+    for key, ent in golden["sgd_nd_single_stream"].items():
+        dims = ent["dims"]
+        g = load(ent.get("graph", key))
+        p = P.LayoutSGDParams.from_graph(g, dims, 1)
+        p.iter_max, p.min_term_updates = ent["iter_max"], ent["min_term_updates"]
+        c = gaussian_init(g, dims, 7)
+        rc, st, tr = O.sgd_nd(oracle_graph(g), oracle_params(p), c, n_streams=1, trace_per_stream=8)
+        assert (st.term_updates, st.attempts) == (ent["term_updates"], ent["attempts"])
+        assert [[int(t["i"]), int(t["j"]), float(t["d_ij"])] for t in tr] == ent["trace8"]
+        assert _hex(c[:32]) == ent["coords_head"] and hashlib.sha256(c.tobytes()).hexdigest() == ent["coords_sha256"]
+        if "coords_tail" in ent:
+            assert _hex(c[-32:]) == ent["coords_tail"]
 
 
 # ---- rand_distr StandardNormal (ziggurat), restated: PARITY UNPINNED (the crate is not in the container) ------------

@@ -157,3 +157,79 @@ def np_crowding(g):
         out = np.where(v <= 1, 0, np.ceil(np.log2(np.maximum(v, 1))))
         return np.minimum(out, hi).astype(np.int64)
     return cnt, rep, clog2(cnt, 63), clog2(rep, 7)
+
+
+# ---- the layout update, restated without the oracle (tests/test_layout_update_restatement.py) ----
+def replay_layout_trace(c0, D, trace, etas, updates_per_iteration):
+    """One stream's layout updates replayed from its trace of terms (i, j, d_ij): the arithmetic of sgd.rs:1085-1149 as read
+    from the reference, in Python floats (IEEE doubles, one rounding per operation, no fused multiply-add) and math.sqrt
+    (correctly rounded) only.  c0: Layout order, c[(2 * node + end) * D + k]; i and j are the reference's 2 * node + end
+    (sgd.rs:1099-1103).  The n-th term runs at etas[n // updates_per_iteration].  No crowding term: the reference has none.
+    Returns the final coordinates as a new float64 array."""
+    import math
+    c = [float(v) for v in np.asarray(c0, dtype=np.float64)]
+    ti = [int(v) for v in trace["i"]]
+    tj = [int(v) for v in trace["j"]]
+    td = [float(v) for v in trace["d_ij"]]
+    etas = [float(v) for v in etas]
+    dims = range(D)
+    for n in range(len(ti)):
+        eta = etas[n // updates_per_iteration]
+        d_ij = td[n]
+        term_weight = 1.0 / d_ij                               # sgd.rs:1085
+        mu = min(eta * term_weight, 1.0)                       # :1086
+        bi, bj = ti[n] * D, tj[n] * D                          # :1102-1103, coords[d][idx]
+        deltas = [0.0] * D                                     # :1106
+        mag_sq = 0.0                                           # :1107
+        for k in dims:                                         # :1108-1113
+            deltas[k] = c[bi + k] - c[bj + k]
+            mag_sq += deltas[k] * deltas[k]
+        if mag_sq == 0.0:                                      # :1116-1119
+            deltas[0] = 1e-9
+            mag_sq = 1e-18
+        mag = math.sqrt(mag_sq)                                # :1121
+        delta_update = mu * (mag - d_ij) / 2.0                 # :1125
+        r = delta_update / mag                                 # :1142
+        for k in dims:                                         # :1143-1149
+            r_d = r * deltas[k]
+            c_i = c[bi + k]                                    # both ends are read before either is written,
+            c_j = c[bj + k]
+            c[bi + k] = c_i - r_d
+            c[bj + k] = c_j + r_d                              # so the second store wins where i == j
+    return np.array(c, dtype=np.float64)
+
+
+def self_loop_graph():
+    """One path that steps on nodes twice, also twice in a row: layout terms with i == j occur (sgd.rs:1143-1149)."""
+    txt = "".join(f"S\t{i}\t{'ACGT'[:1 + i % 4]}\n" for i in range(1, 9)) + \
+        "P\tp\t1+,2+,3+,2+,3-,4+,4+,5+,1-,6+,7+,8+,7-,8+\t*\n"
+    return G.parse_gfa(txt)
+
+
+def absent_node_graph():
+    """A path with one step on an id that is no node (skipped, sgd.rs:525-538; costs no bp, sgd.rs:52-54) and a one-step path."""
+    txt = "".join(f"S\t{i}\t{'A' * (1 + i % 5)}\n" for i in range(1, 41)) + \
+        "P\tp\t" + ",".join(f"{i}+" for i in list(range(1, 21)) + [99] + list(range(21, 41))) + "\t*\n" + \
+        "P\tq\t7+\t*\n"
+    return G.parse_gfa(txt)
+
+
+def reverse_short_paths_graph():
+    """One long path and 4000 paths of 12 steps over 6000 nodes, 30 % of the steps reverse (the graph of
+    test_gpu_parity.py test_reverse_steps_and_short_paths_mix)."""
+    rng = np.random.default_rng(5)
+    n = 6000
+    lens = rng.integers(1, 9, n).astype(np.uint32)
+    long_path = np.arange(n, dtype=np.uint32)
+    shorts = [np.arange(s, s + 12, dtype=np.uint32) for s in rng.integers(0, n - 12, 4000)]
+    steps = np.concatenate([long_path] + shorts)
+    firsts = np.concatenate([[0], np.cumsum([len(long_path)] + [12] * len(shorts))]).astype(np.uint64)
+    rev = (rng.random(steps.shape[0]) < 0.3).astype(np.uint8)
+    return G.FlatGraph(node_len=lens, step_node=steps, step_is_rev=rev, path_first_step=firsts,
+                       node_ids=np.arange(1, n + 1, dtype=np.uint64), path_names=[f"p{k}" for k in range(len(shorts) + 1)])
+
+
+def single_stream_kshift(g):
+    """The crowding onset of a one-stream run (capi.hip fill_kargs): floor(log2(n_steps / 2)) + 2."""
+    per = max(g.n_steps // 2, 1)
+    return per.bit_length() - 1 + 2
