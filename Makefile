@@ -16,7 +16,7 @@ CXXFLAGS := -O2 -std=c++17 -Wall -ffp-contract=off
 
 KERNELS := sgd_kernels_1d sgd_kernels_1d_phased sgd_kernels_nd sgd_kernels_nd_team sgd_kernels_nd_team_wide index_kernels capi multi
 OBJS    := $(KERNELS:%=$(OBJDIR)/%.o)
-HDRS    := $(CSRC)/sgd_device.h $(CSRC)/sgd_kernel_common.h $(CSRC)/sgd_1d.h $(CSRC)/sgd_nd_team.h include/gfasort_hip.h
+HDRS    := $(CSRC)/sgd_device.h $(CSRC)/sgd_kernel_common.h $(CSRC)/sgd_1d.h $(CSRC)/sgd_nd_team.h $(CSRC)/sgd_host.h include/gfasort_hip.h
 HOSTSRC := $(HOST)/graph.cpp $(HOST)/sgd.cpp
 HOSTHDR := $(HOST)/graph.hpp $(HOST)/sgd.hpp
 

@@ -3,6 +3,7 @@
 // that stand where path_linear_sgd / path_linear_sgd_layout stand in the reference.
 #include "../../include/gfasort_hip.h"
 #include "sgd_kernel_common.h"
+#include "sgd_host.h"
 
 #include <algorithm>
 #include <chrono>
@@ -14,47 +15,6 @@
 #include <numeric>
 #include <string>
 #include <vector>
-
-namespace gfs {
-hipError_t launch_1d(const KArgs &a, bool lds_tables, bool atomic_loads, bool trace,
-                     dim3 grid, dim3 block, size_t lds, hipStream_t st);
-hipError_t launch_nd(int dims, const KArgs &a, bool lds_tables, bool atomic_loads, bool trace,
-                     dim3 grid, dim3 block, size_t lds, hipStream_t st);
-size_t pool_bytes(uint64_t n_iters);
-hipError_t launch_1d_fused(const KArgs &a, const IterConsts *d_its, uint32_t n_iters, bool lds_tables, uint32_t *pool,
-                           dim3 grid, dim3 block, size_t lds, hipStream_t st);
-hipError_t launch_1d_ref_fused(const KArgs &a, const IterConsts *d_its, uint32_t n_iters, bool lds_tables, uint32_t *pool,
-                               dim3 grid, dim3 block, size_t lds, hipStream_t st);
-hipError_t launch_nd_ref_fused(int dims, const KArgs &a, const IterConsts *d_its, uint32_t n_iters, bool lds_tables, uint32_t *pool,
-                               dim3 grid, dim3 block, size_t lds, hipStream_t st);
-hipError_t warm_module_1d();
-hipError_t launch_1d_phased_fused(const KArgs &a, const IterConsts *d_its, uint32_t n_iters, bool lds_tables, uint32_t *pool,
-                                  dim3 grid, dim3 block, size_t lds, hipStream_t st);
-hipError_t prepare_1d_phased_fused(bool lds_tables, int block, size_t lds, int *blocks_per_cu);
-hipError_t warm_module_1d_phased();
-hipError_t prepare_1d_fused(uint32_t bundle, bool lds_tables, int block, size_t lds, int *blocks_per_cu);
-hipError_t warm_module_nd();
-hipError_t warm_module_nd_team();
-hipError_t warm_module_nd_team_wide();
-int nd_team_waves(int dims);
-hipError_t launch_nd_team_fused(int dims, const KArgs &a, const IterConsts *d_its, uint32_t n_iters, bool lds_tables, uint32_t *pool,
-                                dim3 grid, dim3 block, size_t lds, hipStream_t st);
-hipError_t prepare_nd_team_fused(int dims, uint32_t bundle, bool lds_tables, int block, size_t lds, int *blocks_per_cu);
-hipError_t warm_module_index();
-hipError_t init_positions_device(const uint32_t *d_node_len, const uint32_t *d_perm, double *d_x, uint64_t n);
-hipError_t reorder_positions_device(const double *d_src, double *d_dst, const uint32_t *d_perm, uint64_t N, uint32_t D,
-                                    int to_device, hipStream_t st);
-hipError_t first_visit_layout_device(const uint32_t *d_step_node, uint64_t n_steps, uint64_t n_nodes, const uint64_t *d_path_first,
-                                     uint32_t n_paths, uint32_t *d_perm,
-                                     int *bad_out);
-hipError_t build_path_index_device(const uint32_t *d_step_node, const uint8_t *d_step_is_rev, const uint32_t *d_node_len,
-                                   const uint32_t *d_perm, const uint64_t *d_path_first, uint32_t n_paths,
-                                   uint64_t n_steps, uint64_t n_nodes, uint64_t *d_tmp, uint4 *d_rec, uint64_t *d_path_len);
-hipError_t sort_order_device(const double *d_x_layout, const uint32_t *d_perm, uint64_t n, uint64_t stride_doubles,
-                             void *d_tmp, uint32_t **d_order_out);
-hipError_t launch_merge_prepare(const double *x, const double *x_prev, float *buf, uint64_t n, hipStream_t st);
-hipError_t launch_merge_apply(double *x, double *x_prev, const float *buf, uint64_t n, double scale_all, hipStream_t st);
-}
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -329,6 +289,18 @@ int gfs_sort_order(const double *x, uint64_t n, uint64_t *order) {         // sg
 // ---------------------------------------------------------------------------------------------
 static constexpr size_t kCounterBytes = 1024 * 8 * sizeof(unsigned long long);   // gfs::COUNTER_SLOTS lines of 64 B
 
+// What a configured context launches: everything of gfs_ctx_run_iteration / gfs_ctx_run_range that does not depend on the
+// call, resolved once by setup_common (plan_launches).
+struct LaunchPlan {
+    const void *iteration = nullptr;         // K1 / K1b, K2 / K2b: one iteration per launch
+    const void *window_iteration = nullptr;  // GFS_F_PHASED: K1, for the iterations of the window
+    const void *fused = nullptr;             // K1c / K1d / K1e / K2c / K2d: a range of iterations per launch; null: one launch per iteration
+    bool pooled = false;                     // ... drawing from work pools (false: GFS_F_DBG_FREE_RUNNING's fixed quotas)
+    bool fuse_one = false;                   // a range of ONE iteration is a fused launch too, in chunks of one_chunk
+    bool fuse_one_probe = false;             // ... or would be if GFS_DBG_ONE_CHUNK asked for it
+    uint32_t one_chunk = 0;
+};
+
 struct gfs_ctx {
     int device = 0;
     int cu_count = 0;
@@ -359,7 +331,8 @@ struct gfs_ctx {
     gfs::IterConsts *d_its_all = nullptr;                     // constants of iterations 0..=iter_max, resident
     uint32_t *d_pool = nullptr; uint64_t pool_cap = 0;        // fused launch: per-iteration work pool counters (sgd_kernels_1d.hip)
     uint64_t n_streams = 0, quota_total = 0;
-    uint64_t fused_resident_blocks = 0; // workgroups of the fused 1D kernel the chip holds at once (block size, LDS table)
+    uint64_t fused_resident_blocks = 0; // workgroups of the fused team kernel the chip holds at once (block size, LDS table)
+    LaunchPlan plan;
     uint32_t block = 256;
     uint32_t bundle = 1;               // lanes per sampling bundle actually used (1 = reference streams)
     uint32_t partners = 1;             // partner draws per leader (2: 1D team kernel at B = 64)
@@ -443,6 +416,127 @@ static int upload_zeta_table(gfs_ctx *c, const gfs_sgd_params *p, const double *
     return GFS_OK;
 }
 
+static void iter_consts(const gfs_ctx *c, uint64_t k, gfs::IterConsts &it) {
+    const gfs_sgd_params &p = c->params;
+    double fc = std::floor(p.cooling_start * (double)p.iter_max);          // sgd.rs:297
+    uint64_t first_cooling = !(fc > 0.0) ? 0 : (fc >= 18446744073709551616.0 ? UINT64_MAX : (uint64_t)fc);
+    bool cooling = k > first_cooling;                                      // sgd.rs:393-396
+    double theta = cooling ? 0.001 : p.theta;
+    it.eta = c->etas[k];
+    it.cooling = cooling ? 1 : 0;
+    it.zeta2theta = 1.0 + h_fpp(0.5, theta);                               // sgd.rs:471 (== :143 bound)
+    double omt = 1.0 - theta;                                              // sgd.rs:133
+    it.omt_e = h_sat_i32(omt); it.omt_fb = omt - (double)it.omt_e;
+    double alpha = 1.0 / (1.0 - theta);                                    // sgd.rs:132
+    it.alpha_e = h_sat_i32(alpha); it.alpha_fb = alpha - (double)it.alpha_e;
+    it._pad = (c->phased && k >= c->win_begin && k < c->win_end) ? 1 : 0;   // K1e: a window iteration (the other kernels ignore it)
+}
+
+static bool in_window(const gfs_ctx *c, uint64_t k) { return c->phased && k >= c->win_begin && k < c->win_end; }
+
+// The resident table of the whole schedule's constants (d_its_all); again whenever the phase window moves, whose marks it carries.
+static int upload_schedule(gfs_ctx *c) {
+    std::vector<gfs::IterConsts> all(c->params.iter_max + 1);
+    for (uint64_t k = 0; k <= c->params.iter_max; ++k) iter_consts(c, k, all[k]);
+    HIPCHK(hipMemcpy(c->d_its_all, all.data(), all.size() * sizeof(gfs::IterConsts), hipMemcpyHostToDevice));
+    return GFS_OK;
+}
+
+// ---- kernels: one selection, one residency query, one launch -------------------------------------------------------------
+// The dispatch over the kernel units (sgd_host.h): reference streams, the team kernels of D = 1..3 and those of D = 4..8.
+static const void *iteration_kernel(const gfs::KernelShape &s) {
+    if (s.dims == 0) return gfs::iteration_kernel_1d(s);
+    if (s.bundle <= 1) return gfs::iteration_kernel_nd(s);
+    return s.dims <= 3 ? gfs::iteration_kernel_nd_team(s) : gfs::iteration_kernel_nd_team_wide(s);
+}
+static const void *fused_kernel(const gfs::KernelShape &s, bool pooled) {
+    if (s.dims == 0) return gfs::fused_kernel_1d(s, pooled);
+    if (s.bundle <= 1) return gfs::fused_kernel_nd(s, pooled);
+    return s.dims <= 3 ? gfs::fused_kernel_nd_team(s, pooled) : gfs::fused_kernel_nd_team_wide(s, pooled);
+}
+// "This context has a fused team kernel": K1c (K1e where phased) at the sort's widest bundles, K2c for layouts of 2 and more
+// dimensions at B = 64.  Such a context is bounded by residency, keeps the schedule's constants resident and draws two partners
+// per leader at B = 64 (choose_bundle).
+static bool has_fused_team_kernel(int dims, uint32_t bundle) { return (dims == 0 && bundle >= 16) || (dims >= 2 && bundle == 64); }
+
+// Workgroups of `fn` one CU holds at once with this context's block size and LDS table (registers, waves per SIMD and the table
+// all count).  Also: the first launch of a kernel function costs the host ~0.1 ms (the runtime materialises the function
+// lazily), and a caller that brackets its launch with events pays that inside the bracket; this resolves the function at setup.
+static int resident_blocks_per_cu(const gfs_ctx *c, const void *fn, int *per_cu) {
+    hipFuncAttributes attr;
+    HIPCHK(hipFuncGetAttributes(&attr, fn));
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, fn, (int)c->block, c->lds_bytes));
+    return GFS_OK;
+}
+
+// Every kernel here takes its KArgs first, by value; the fused ones then (const IterConsts *its, uint32_t n_iters, uint32_t *pool).
+static hipError_t launch(const gfs_ctx *c, const void *fn, gfs::KArgs &a, const gfs::IterConsts *its, uint32_t n_iters, uint32_t *pool,
+                         hipStream_t st) {
+    void *args[] = {&a, &its, &n_iters, &pool};                            // (a per-iteration kernel reads args[0] only)
+    const dim3 block(c->block), grid((unsigned)((c->n_streams + c->block - 1) / c->block));
+    return hipLaunchKernel(fn, grid, block, args, c->lds_bytes, st);
+}
+
+// Resolves c->plan — and bounds the automatic stream count by residency.  Needs the bundle, the flags and lds_bytes.
+static int plan_launches(gfs_ctx *c) {
+    LaunchPlan &pl = c->plan;
+    pl = LaunchPlan{};
+    c->fused_resident_blocks = 0;
+    const bool trace = c->cfg.trace_per_stream != 0;
+    const gfs::KernelShape shape{c->dims, c->bundle, c->lds_tables, c->atomic_loads, trace};
+    const bool team = has_fused_team_kernel(c->dims, c->bundle), ref = c->bundle == 1;
+    const bool free_running = (c->cfg.flags & GFS_F_DBG_FREE_RUNNING) != 0;
+    pl.iteration = iteration_kernel(shape);
+    if (c->phased) pl.window_iteration = iteration_kernel({0, 1, c->lds_tables, c->atomic_loads, trace});
+    const void *pooled_kernel = c->phased ? gfs::phased_fused_kernel(c->lds_tables) : (team || ref) ? fused_kernel(shape, true) : nullptr;
+    const void *free_kernel = team && !c->phased && free_running ? fused_kernel(shape, false) : nullptr;   // (K1e, K1d, K2d: pools only)
+    if (!pl.iteration || (c->phased && !pl.window_iteration) || ((team || ref) && !pooled_kernel) ||
+        (team && !c->phased && free_running && !free_kernel))
+        return fail(GFS_E_UNSUPPORTED, "no kernel is built for dims=" + std::to_string(c->dims) + " bundle=" + std::to_string(c->bundle) +
+                                           " lds_tables=" + std::to_string(c->lds_tables) + " atomic_loads=" + std::to_string(c->atomic_loads) +
+                                           " trace=" + std::to_string(trace) + " phased=" + std::to_string(c->phased));
+    if (team) {
+        // The fused launch has no grid barrier: a workgroup that does not fit on the chip beside the others would walk
+        // its whole schedule, early large-eta iterations included, after they have finished theirs — on a 525k-node graph
+        // 5 such waves of 4101 were enough to wreck the layout (relative error 64 at path distance 1:
+        // profiles/r02/streams_5_waves.log).  So the fused team kernel (sort and layout alike) is only launched with every
+        // workgroup resident: ask the runtime how many fit per CU with this block size and LDS table (33 KB of zeta table = 4
+        // blocks of 256 per CU, not 5), bound the automatic stream count by it, and run one launch per iteration when a caller
+        // asks for more streams.
+        int per_cu = 0;
+        int rc = resident_blocks_per_cu(c, pooled_kernel, &per_cu);
+        if (rc) return rc;
+        c->fused_resident_blocks = (uint64_t)std::max(per_cu, 0) * c->cu_count;
+        const uint64_t resident = c->fused_resident_blocks * c->block;
+        if (!c->cfg.n_streams && c->n_streams > resident && resident >= 64) c->n_streams = resident;
+    }
+    // One persistent launch for a range where a fused kernel exists: the team kernels above and reference streams in any
+    // dimension (K1d / K2d).  The waves of a fused launch draw an iteration's updates from a work pool (a share per counter
+    // beyond 2^31 — 3e10 updates per iteration — cannot be pooled: one launch per iteration then, unless the diagnostic
+    // GFS_F_DBG_FREE_RUNNING asks for round 1's fixed quotas).  The team kernel is only fused with every workgroup resident —
+    // which assumes this context has the device to itself: concurrent streams or a second rank on the same device can delay a
+    // workgroup, harmlessly under pools (a late wave finds the counters exhausted and leaves), not so with fixed quotas.
+    const uint64_t n_waves = (c->n_streams + 63) / 64;
+    // (layouts draw an iteration from ONE counter, sgd_nd_team.h K2c: the whole iteration must stay below 2^31)
+    const bool pool_ok = n_waves <= 0xFFFFFFFFull &&
+                         c->quota_total / (c->dims != 0 && c->bundle > 1 ? 1u : gfs::pool_slots((uint32_t)n_waves)) < (1ull << 31);
+    const bool team_fusable = team && (c->phased ? pool_ok && !free_running : pool_ok || free_running) &&
+                              (c->n_streams + c->block - 1) / c->block <= c->fused_resident_blocks;   // every workgroup resident
+    pl.pooled = pool_ok && !(free_running && c->bundle > 1);
+    if ((team_fusable || (ref && pool_ok)) && c->atomic_loads && !trace && !(c->cfg.flags & GFS_F_NO_FUSE))
+        pl.fused = pl.pooled ? pooled_kernel : free_kernel;
+    // A range of ONE layout iteration is drawn from the pool too where it is at least four chunks per wave: with fixed quotas a layout
+    // launch's waves finish as far apart as their leaders' costs are (C4: 2.33 ms per iteration against 2.21 pooled, 2.04 inside
+    // a fused range).  Not with shorter chunks for smaller iterations: the layout pool is ONE counter, and it takes ~2e7 claims/s
+    // comfortably and 4e7 not (C4 in chunks of 1024 / 512 / 256: 2.41 / 3.05 / 5.24 ms).  Not for the sort either: its launches of
+    // one iteration are short (C3: 0.16 ms with fixed quotas, 0.15 pooled in chunks of 1024, 0.10 inside a fused range)
+    // (profiles/r03/one_iteration_launch_probe.log, launch_overhead_probe.log).
+    pl.one_chunk = c->dims ? gfs::ND_TEAM_CHUNK : gfs::TEAM_CHUNK;
+    pl.fuse_one_probe = team_fusable && pool_ok;
+    pl.fuse_one = pl.fuse_one_probe && c->dims != 0 && c->quota_total / n_waves >= 4ull * pl.one_chunk;
+    return GFS_OK;
+}
+
 // Streams per launch when the caller leaves it to the library.
 static uint64_t auto_stream_count(const gfs_ctx *c, bool team) {
     // Lanes per CU: each wave is a serial chain of memory round trips, so more chains raise throughput until the memory-side
@@ -520,7 +614,7 @@ static int choose_bundle(gfs_ctx *c, int dims) {
     if (k == 0) k = dims ? 16 : 64;
     // Two partners per leader (sgd_device.h Leader): the team kernels at B = 64 (1D; layouts of 2 and more dimensions), unless
     // GFS_F_ONE_PARTNER
-    c->partners = (b == 64 && (dims == 0 || dims >= 2) && !(c->cfg.flags & GFS_F_ONE_PARTNER)) ? 2u : 1u;
+    c->partners = (b == 64 && has_fused_team_kernel(dims, b) && !(c->cfg.flags & GFS_F_ONE_PARTNER)) ? 2u : 1u;
     // ... auto: and short enough that an iteration still draws >= 64 leaders (a leader stands for up to 64 * K * partners
     // terms): at 16k nodes runs of 32 trips left 37 leaders per iteration and +6 % at path distance 1, runs of 16 (74 leaders)
     // +1 %; from 32k nodes up 37 leaders were within 3 % (same table).  Binds only below ~500k steps.
@@ -529,8 +623,6 @@ static int choose_bundle(gfs_ctx *c, int dims) {
     c->chain = b == 64 ? k : 1;
     return GFS_OK;
 }
-
-static void iter_consts(const gfs_ctx *c, uint64_t k, gfs::IterConsts &it);
 
 static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs_launch_config *cfg,
                         const double *etas, const double *zetas) {
@@ -594,29 +686,9 @@ static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs
     size_t lds = (size_t)c->n_paths * sizeof(uint4) + (size_t)c->zlen_staged * 8;
     c->lds_tables = !(c->cfg.flags & GFS_F_NO_LDS_TABLES) && lds <= 48 * 1024;
     c->lds_bytes = c->lds_tables ? lds : 0;
-    c->fused_resident_blocks = 0;
-    if (dims == 0 && c->bundle >= 16) {
-        // The fused launch has no grid barrier: a workgroup that does not fit on the chip beside the others would walk
-        // its whole schedule, early large-eta iterations included, after they have finished theirs — on a 525k-node graph
-        // 5 such waves of 4101 were enough to wreck the layout (relative error 64 at path distance 1:
-        // profiles/r02/streams_5_waves.log).  So the fused kernel is only launched with every workgroup resident: ask the
-        // runtime how many fit per CU with this block size and LDS table (33 KB of zeta table = 4 blocks of 256 per CU, not
-        // 5), bound the automatic stream count by it, and run one launch per iteration when a caller asks for more streams.
-        int per_cu = 0;
-        if (c->phased) HIPCHK(gfs::prepare_1d_phased_fused(c->lds_tables, (int)c->block, c->lds_bytes, &per_cu));
-        else HIPCHK(gfs::prepare_1d_fused(c->bundle, c->lds_tables, (int)c->block, c->lds_bytes, &per_cu));   // (also: not inside the first launch's event bracket)
-        c->fused_resident_blocks = (uint64_t)std::max(per_cu, 0) * c->cu_count;
-        const uint64_t resident = c->fused_resident_blocks * c->block;
-        if (!c->cfg.n_streams && T > resident && resident >= 64) c->n_streams = T = resident;
-    }
-    if (dims >= 2 && c->bundle == 64) {
-        // the layout team kernel's fused launch (K2c): the same residency rule
-        int per_cu = 0;
-        HIPCHK(gfs::prepare_nd_team_fused(dims, c->bundle, c->lds_tables, (int)c->block, c->lds_bytes, &per_cu));
-        c->fused_resident_blocks = (uint64_t)std::max(per_cu, 0) * c->cu_count;
-        const uint64_t resident = c->fused_resident_blocks * c->block;
-        if (!c->cfg.n_streams && T > resident && resident >= 64) c->n_streams = T = resident;
-    }
+    rc = plan_launches(c);                                               // (may lower n_streams)
+    if (rc) return rc;
+    T = c->n_streams;
 
     HIPCHK(hipMalloc(&c->d_rng, 4 * T * 8));
     if (c->bundle > 1) {                                                 // team kernels, sort and layout
@@ -631,34 +703,15 @@ static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs
     }
     rc = seed_streams(c);
     if (rc) return rc;
-    if (((dims == 0 && c->bundle >= 16) || (dims >= 2 && c->bundle == 64) || c->bundle == 1) && c->params.iter_max < (1u << 20)) {
+    if ((has_fused_team_kernel(dims, c->bundle) || c->bundle == 1) && c->params.iter_max < (1u << 20)) {
         // the whole schedule's per-iteration constants, for fused launches over consecutive iterations
-        std::vector<gfs::IterConsts> all(c->params.iter_max + 1);
-        for (uint64_t k = 0; k <= c->params.iter_max; ++k) iter_consts(c, k, all[k]);
-        HIPCHK(hipMalloc(&c->d_its_all, all.size() * sizeof(gfs::IterConsts)));
-        HIPCHK(hipMemcpy(c->d_its_all, all.data(), all.size() * sizeof(gfs::IterConsts), hipMemcpyHostToDevice));
+        HIPCHK(hipMalloc(&c->d_its_all, (c->params.iter_max + 1) * sizeof(gfs::IterConsts)));
+        rc = upload_schedule(c);
+        if (rc) return rc;
     }
     c->configured = true;
     return GFS_OK;
 }
-
-static void iter_consts(const gfs_ctx *c, uint64_t k, gfs::IterConsts &it) {
-    const gfs_sgd_params &p = c->params;
-    double fc = std::floor(p.cooling_start * (double)p.iter_max);          // sgd.rs:297
-    uint64_t first_cooling = !(fc > 0.0) ? 0 : (fc >= 18446744073709551616.0 ? UINT64_MAX : (uint64_t)fc);
-    bool cooling = k > first_cooling;                                      // sgd.rs:393-396
-    double theta = cooling ? 0.001 : p.theta;
-    it.eta = c->etas[k];
-    it.cooling = cooling ? 1 : 0;
-    it.zeta2theta = 1.0 + h_fpp(0.5, theta);                               // sgd.rs:471 (== :143 bound)
-    double omt = 1.0 - theta;                                              // sgd.rs:133
-    it.omt_e = h_sat_i32(omt); it.omt_fb = omt - (double)it.omt_e;
-    double alpha = 1.0 / (1.0 - theta);                                    // sgd.rs:132
-    it.alpha_e = h_sat_i32(alpha); it.alpha_fb = alpha - (double)it.alpha_e;
-    it._pad = (c->phased && k >= c->win_begin && k < c->win_end) ? 1 : 0;   // K1e: a window iteration (the other kernels ignore it)
-}
-
-static bool in_window(const gfs_ctx *c, uint64_t k) { return c->phased && k >= c->win_begin && k < c->win_end; }
 
 extern "C" {
 
@@ -963,15 +1016,13 @@ int gfs_ctx_run_iteration(gfs_ctx *c, uint64_t k, void *hip_stream) {
     gfs::KArgs a{};
     fill_kargs(c, a);
     iter_consts(c, k, a.it);
-    if (in_window(c, k)) a.bundle = 1;                                     // GFS_F_PHASED: the window's iterations are K1's
-    dim3 block(c->block), grid((unsigned)((c->n_streams + c->block - 1) / c->block));
+    const bool window = in_window(c, k);                                   // GFS_F_PHASED: the window's iterations are K1's
+    if (window) a.bundle = 1;
     std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
     int rc = next_event_pair(c, ev);
     if (rc) return rc;
     HIPCHK(hipEventRecord(ev->first, st));
-    hipError_t e = c->dims == 0
-        ? gfs::launch_1d(a, c->lds_tables, c->atomic_loads, c->d_trace != nullptr, grid, block, c->lds_bytes, st)
-        : gfs::launch_nd(c->dims, a, c->lds_tables, c->atomic_loads, c->d_trace != nullptr, grid, block, c->lds_bytes, st);
+    hipError_t e = launch(c, window ? c->plan.window_iteration : c->plan.iteration, a, nullptr, 0, nullptr, st);
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     HIPCHK(hipEventRecord(ev->second, st));
     c->iterations++;
@@ -980,44 +1031,22 @@ int gfs_ctx_run_iteration(gfs_ctx *c, uint64_t k, void *hip_stream) {
 }
 
 // A range of iterations ks[0..n) (each in 0..=iter_max): ONE fused launch for the team kernels (sgd1d_team_fused_kernel; layouts of 2
-// and more dimensions at B = 64: sgdnd_team_fused_kernel) and for reference streams (sgd1d_fused_kernel, sgdnd_fused_kernel); otherwise one launch per iteration.
+// and more dimensions at B = 64: sgdnd_team_fused_kernel) and for reference streams (sgd1d_fused_kernel, sgdnd_fused_kernel); otherwise one
+// launch per iteration.  Which of the two, with which kernel, is the context's plan (plan_launches); only the length of the range
+// and the probe knobs are looked at here.
 int gfs_ctx_run_range(gfs_ctx *c, const uint64_t *ks, uint64_t n, void *hip_stream) {
     if (!c || (!ks && n)) return fail(GFS_E_ARG, "null argument");
     if (!c->configured) return fail(GFS_E_STATE, "context not set up");
     if (!c->valid_paths || c->n_nodes == 0) return GFS_NOTHING_TO_DO;
     for (uint64_t i = 0; i < n; ++i) if (ks[i] > c->params.iter_max) return fail(GFS_E_ARG, "iteration beyond iter_max");
-    // One persistent launch for the range where a fused kernel exists: the 1D team kernel at its widest bundles (K1c) and
-    // reference streams in any dimension (K1d / K2d).  The waves of a fused launch draw an iteration's updates from a work
-    // pool (a share per counter beyond 2^31 — 3e10 updates per iteration — cannot be pooled: one launch per iteration
-    // then, unless the diagnostic GFS_F_DBG_FREE_RUNNING asks for round 1's fixed quotas).  The team kernel is only fused
-    // with every workgroup resident — which assumes this context has the device to itself: concurrent streams or a second
-    // rank on the same device can delay a workgroup, harmlessly under pools (a late wave finds the counters exhausted and
-    // leaves), not so with fixed quotas.
-    const uint64_t n_waves = (c->n_streams + 63) / 64;
-    // (layouts draw an iteration from ONE counter, sgd_kernels_nd_team.hip K2c: the whole iteration must stay below 2^31)
-    const bool pool_ok = n_waves <= 0xFFFFFFFFull &&
-                         c->quota_total / (c->dims != 0 && c->bundle > 1 ? 1u : gfs::pool_slots((uint32_t)n_waves)) < (1ull << 31);
-    const bool free_running = (c->cfg.flags & GFS_F_DBG_FREE_RUNNING) != 0;
-    const bool team_shape = (c->dims == 0 && c->bundle >= 16) || (c->dims >= 2 && c->bundle == 64);   // K1c, K2c
-    const bool team_fusable = team_shape && (c->phased ? pool_ok && !free_running : pool_ok || free_running) &&   // (K1e: pools only)
-                              (c->n_streams + c->block - 1) / c->block <= c->fused_resident_blocks;   // every workgroup resident
-    const bool ref_fusable = c->bundle == 1 && pool_ok;
-    // A range of ONE layout iteration is drawn from the pool too where it is at least four chunks per wave: with fixed quotas a layout
-    // launch's waves finish as far apart as their leaders' costs are (C4: 2.33 ms per iteration against 2.21 pooled, 2.04 inside
-    // a fused range).  Not with shorter chunks for smaller iterations: the layout pool is ONE counter, and it takes ~2e7 claims/s
-    // comfortably and 4e7 not (C4 in chunks of 1024 / 512 / 256: 2.41 / 3.05 / 5.24 ms).  Not for the sort either: its launches of
-    // one iteration are short (C3: 0.16 ms with fixed quotas, 0.15 pooled in chunks of 1024, 0.10 inside a fused range)
-    // (profiles/r03/one_iteration_launch_probe.log, launch_overhead_probe.log).
-    uint32_t one_chunk = c->dims ? gfs::ND_TEAM_CHUNK : gfs::TEAM_CHUNK;
-    const uint64_t per_wave = c->quota_total / n_waves;
-    bool single_ok = team_fusable && pool_ok && c->dims != 0 && per_wave >= 4ull * one_chunk;
+    const LaunchPlan &pl = c->plan;
+    uint32_t one_chunk = pl.one_chunk;
+    bool fuse_one = pl.fuse_one;
     if (const char *e = std::getenv("GFS_DBG_ONE_CHUNK")) {               // probe knob (scripts/one_iteration_launch_probe.py): also for the sort
         const long v = std::atol(e);
-        if (v >= 64 && v <= 4096 && !(v & (v - 1))) { one_chunk = (uint32_t)v; single_ok = team_fusable && pool_ok; }
+        if (v >= 64 && v <= 4096 && !(v & (v - 1))) { one_chunk = (uint32_t)v; fuse_one = pl.fuse_one_probe; }
     }
-    const bool can_fuse = (team_fusable || ref_fusable) && c->atomic_loads && !c->d_trace && (n > 1 || (n == 1 && single_ok)) &&
-                          n <= 0xFFFFFFFFull && !(c->cfg.flags & GFS_F_NO_FUSE);
-    if (!can_fuse) {
+    if (!pl.fused || n == 0 || (n == 1 && !fuse_one) || n > 0xFFFFFFFFull) {
         for (uint64_t i = 0; i < n; ++i) { int rc = gfs_ctx_run_iteration(c, ks[i], hip_stream); if (rc) return rc; }
         return GFS_OK;
     }
@@ -1060,10 +1089,9 @@ int gfs_ctx_run_range(gfs_ctx *c, const uint64_t *ks, uint64_t n, void *hip_stre
         if (c->bundle > 1 && v >= 64 && v <= 16384 && !(v & (v - 1))) a.chunk = (uint32_t)v;
     }
     iter_consts(c, ks[0], a.it);
-    dim3 block(c->block), grid((unsigned)((c->n_streams + c->block - 1) / c->block));
     // work pools (sgd_kernels_1d.hip): the waves draw an iteration's updates from shared counters, zeroed per launch
     uint32_t *pool = nullptr;
-    if (pool_ok && !(free_running && c->bundle > 1)) {
+    if (pl.pooled) {
         if (c->pool_cap < n) {
             if (c->d_pool) HIPCHK(hipFree(c->d_pool));
             c->d_pool = nullptr; c->pool_cap = 0;
@@ -1077,11 +1105,7 @@ int gfs_ctx_run_range(gfs_ctx *c, const uint64_t *ks, uint64_t n, void *hip_stre
     int rc = next_event_pair(c, ev);
     if (rc) return rc;
     HIPCHK(hipEventRecord(ev->first, st));                // (the event pair brackets the kernel alone)
-    hipError_t e = c->phased ? gfs::launch_1d_phased_fused(a, d_slice, (uint32_t)n, c->lds_tables, pool, grid, block, c->lds_bytes, st)
-                 : c->bundle > 1 ? (c->dims == 0 ? gfs::launch_1d_fused(a, d_slice, (uint32_t)n, c->lds_tables, pool, grid, block, c->lds_bytes, st)
-                                                 : gfs::launch_nd_team_fused(c->dims, a, d_slice, (uint32_t)n, c->lds_tables, pool, grid, block, c->lds_bytes, st))
-                   : c->dims == 0 ? gfs::launch_1d_ref_fused(a, d_slice, (uint32_t)n, c->lds_tables, pool, grid, block, c->lds_bytes, st)
-                                  : gfs::launch_nd_ref_fused(c->dims, a, d_slice, (uint32_t)n, c->lds_tables, pool, grid, block, c->lds_bytes, st);
+    hipError_t e = launch(c, pl.fused, a, d_slice, (uint32_t)n, pool, st);
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("fused kernel launch: ") + hipGetErrorString(e));
     HIPCHK(hipEventRecord(ev->second, st));
     c->iterations += n;
@@ -1189,9 +1213,8 @@ int gfs_ctx_phase_window(gfs_ctx *c, int64_t set_begin, int64_t set_end, uint64_
         if (c->d_its_all) {                                                // the resident schedule carries the window's marks
             HIPCHK(hipSetDevice(c->device));
             HIPCHK(hipDeviceSynchronize());
-            std::vector<gfs::IterConsts> all(c->params.iter_max + 1);
-            for (uint64_t k = 0; k <= c->params.iter_max; ++k) iter_consts(c, k, all[k]);
-            HIPCHK(hipMemcpy(c->d_its_all, all.data(), all.size() * sizeof(gfs::IterConsts), hipMemcpyHostToDevice));
+            int rc = upload_schedule(c);
+            if (rc) return rc;
         }
     }
     if (begin_out) *begin_out = c->win_begin;

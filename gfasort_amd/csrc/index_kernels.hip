@@ -4,6 +4,7 @@
 //   K3  PathIndex::from_graph (src/sgd.rs:34-71): step positions = per-path exclusive prefix sum
 //       of node lengths over the steps, written straight into the 16-byte step records
 //   K6  path_sgd_sort's sort (src/sgd.rs:665-671): positions -> rank order
+#include "sgd_host.h"
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <stdint.h>

@@ -18,6 +18,7 @@
 // Host-only planning (gfs_shard_paths, gfs_shard_quotas, gfs_shared_node_layout, gfs_exchange_plan) needs no
 // device and is what the CPU tests and the Python driver for test engines use too.
 #include "../../include/gfasort_hip.h"
+#include "sgd_host.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -27,8 +28,6 @@
 #include <numeric>
 #include <string>
 #include <vector>
-
-int gfs_set_error(int code, const std::string &msg);      // capi.hip
 
 #define MHIPCHK(expr)                                                                          \
     do {                                                                                       \

@@ -1,0 +1,68 @@
+// sgd_host.h — the host-side interface between the translation units of libgfasort_hip.so: the only declaration of
+// everything one unit calls in another.  The kernel units SELECT (shape -> address of the kernel, null where no such kernel is
+// built); capi.hip resolves a context's kernels once, when the context is set up, and launches them through one path.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string>
+#include <type_traits>
+
+int gfs_set_error(int code, const std::string &msg);      // capi.hip: sets gfs_last_error(), returns code
+
+namespace gfs {
+
+// What picks a kernel: dims 0 = the 1D sort, 1..8 = layouts; bundle 0 / 1 = reference streams, 4..64 = team kernels.
+struct KernelShape { int dims; uint32_t bundle; bool lds_tables, atomic_loads, trace; };
+
+template <typename... A> inline const void *kernel_addr(void (*k)(A...)) { return reinterpret_cast<const void *>(k); }
+// a run-time flag as a template argument: f(std::true_type{}) or f(std::false_type{})
+template <typename F> inline auto with_flag(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// One iteration per launch, kernel(KArgs).  K1 / K2 (reference streams) are built for every combination of the three flags.
+// The team kernels' trace variants always read with agent-scope loads, and the layout team kernels (K2b) have no other loads:
+// they ignore atomic_loads.  K1b exists for B = 4..64, K2b for B = 8..64: D = 1..3 in one unit, D = 4..8 in another, so that
+// the two compile side by side.
+const void *iteration_kernel_1d(const KernelShape &s);              // sgd_kernels_1d.hip: K1, K1b
+const void *iteration_kernel_nd(const KernelShape &s);              // sgd_kernels_nd.hip: K2
+const void *iteration_kernel_nd_team(const KernelShape &s);         // sgd_kernels_nd_team.hip: K2b, D = 1..3
+const void *iteration_kernel_nd_team_wide(const KernelShape &s);    // sgd_kernels_nd_team_wide.hip: K2b, D = 4..8
+
+// A range of iterations per launch, kernel(KArgs, const IterConsts *, uint32_t n_iters, uint32_t *pool).  pooled: the waves
+// draw an iteration's updates from pool (zeroed counters, pool_bytes(n_iters) of them); otherwise fixed quotas per wave,
+// free-running, and pool is null.  The fused kernels are built with agent-scope loads and without trace only — a context
+// with other flags does not fuse — so those two fields are not looked at.  Reference streams (K1d, K2d) and the phased
+// sampler (K1e) have no free-running form; K1c exists for B = 16, 32, 64, K2c for B = 64 and D = 2..8.
+const void *fused_kernel_1d(const KernelShape &s, bool pooled);             // sgd_kernels_1d.hip: K1d, K1c
+const void *phased_fused_kernel(bool lds_tables);                           // sgd_kernels_1d_phased.hip: K1e
+const void *fused_kernel_nd(const KernelShape &s, bool pooled);             // sgd_kernels_nd.hip: K2d
+const void *fused_kernel_nd_team(const KernelShape &s, bool pooled);        // sgd_kernels_nd_team.hip: K2c, D = 2, 3
+const void *fused_kernel_nd_team_wide(const KernelShape &s, bool pooled);   // sgd_kernels_nd_team_wide.hip: K2c, D = 4..8
+
+size_t pool_bytes(uint64_t n_iters);                      // sgd_kernels_1d.hip
+int nd_team_waves(int dims);                              // sgd_kernels_nd_team.hip: waves per SIMD the layout team kernels are built for
+
+// HIP loads a translation unit's code object on first use: each of these touches one kernel of its unit (gfs_warmup)
+hipError_t warm_module_1d();
+hipError_t warm_module_1d_phased();
+hipError_t warm_module_nd();
+hipError_t warm_module_nd_team();
+hipError_t warm_module_nd_team_wide();
+hipError_t warm_module_index();
+
+// index_kernels.hip
+hipError_t init_positions_device(const uint32_t *d_node_len, const uint32_t *d_perm, double *d_x, uint64_t n);
+hipError_t reorder_positions_device(const double *d_src, double *d_dst, const uint32_t *d_perm, uint64_t N, uint32_t D,
+                                    int to_device, hipStream_t st);
+hipError_t first_visit_layout_device(const uint32_t *d_step_node, uint64_t n_steps, uint64_t n_nodes, const uint64_t *d_path_first,
+                                     uint32_t n_paths, uint32_t *d_perm, int *bad_out);
+hipError_t build_path_index_device(const uint32_t *d_step_node, const uint8_t *d_step_is_rev, const uint32_t *d_node_len,
+                                   const uint32_t *d_perm, const uint64_t *d_path_first, uint32_t n_paths,
+                                   uint64_t n_steps, uint64_t n_nodes, uint64_t *d_tmp, uint4 *d_rec, uint64_t *d_path_len);
+hipError_t sort_order_device(const double *d_x_layout, const uint32_t *d_perm, uint64_t n, uint64_t stride_doubles,
+                             void *d_tmp, uint32_t **d_order_out);
+
+// sgd_kernels_1d.hip: the multi-GPU replica merge
+hipError_t launch_merge_prepare(const double *x, const double *x_prev, float *buf, uint64_t n, hipStream_t st);
+hipError_t launch_merge_apply(double *x, double *x_prev, const float *buf, uint64_t n, double scale_all, hipStream_t st);
+
+}  // namespace gfs

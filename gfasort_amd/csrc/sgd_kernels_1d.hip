@@ -1,6 +1,7 @@
 // sgd_kernels_1d.hip — K1 (reference streams) and K1b (team kernel) of path_linear_sgd, plus the
 // multi-GPU replica-merge kernels.  See sgd_kernel_common.h / sgd_device.h.
 #include "sgd_1d.h"
+#include "sgd_host.h"
 
 namespace gfs {
 
@@ -195,98 +196,42 @@ hipError_t launch_merge_apply(double *x, double *x_prev, const float *buf, uint6
     return hipGetLastError();
 }
 
-template <bool L, bool A>
-static hipError_t launch_1d_t(const KArgs &a, bool trace, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-    if (trace) hipLaunchKernelGGL((sgd1d_kernel<L, A, true>), grid, block, lds, st, a);
-    else       hipLaunchKernelGGL((sgd1d_kernel<L, A, false>), grid, block, lds, st, a);
-    return hipGetLastError();
-}
-template <int B, bool L, bool A>
-static hipError_t launch_1db_t(const KArgs &a, bool trace, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-    if (trace) hipLaunchKernelGGL((sgd1d_team_kernel<B, L, true, true>), grid, block, lds, st, a);   // debug trace: agent-scope loads
-    else       hipLaunchKernelGGL((sgd1d_team_kernel<B, L, A, false>), grid, block, lds, st, a);
-    return hipGetLastError();
-}
+// Fused ranges of iterations: K1d for reference streams (pooled only); K1c only for the team kernel with its widest bundles (what
+// the auto policy picks on graphs large enough for launch overhead to matter), pooled or with GFS_F_DBG_FREE_RUNNING's fixed quotas.
 template <int B>
-static hipError_t launch_1db(const KArgs &a, bool lds_tables, bool atomic_loads, bool trace,
-                             dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-    if (lds_tables) return atomic_loads ? launch_1db_t<B, true, true>(a, trace, grid, block, lds, st)
-                                        : launch_1db_t<B, true, false>(a, trace, grid, block, lds, st);
-    return atomic_loads ? launch_1db_t<B, false, true>(a, trace, grid, block, 0, st)
-                        : launch_1db_t<B, false, false>(a, trace, grid, block, 0, st);
+static const void *team_fused_kernel_1d(const KernelShape &s, bool pooled) {
+    return with_flag(pooled, [&](auto P) { return with_flag(s.lds_tables, [&](auto L) { return kernel_addr(sgd1d_team_fused_kernel<B, L(), P()>); }); });
 }
-template <int B>
-static hipError_t launch_1d_fused_b(const KArgs &a, const IterConsts *d_its, uint32_t n_iters, bool lds_tables,
-                                    uint32_t *pool, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-    if (pool) {
-        if (lds_tables) hipLaunchKernelGGL((sgd1d_team_fused_kernel<B, true, true>), grid, block, lds, st, a, d_its, n_iters, pool);
-        else            hipLaunchKernelGGL((sgd1d_team_fused_kernel<B, false, true>), grid, block, 0, st, a, d_its, n_iters, pool);
-    } else {                                                           // GFS_F_DBG_FREE_RUNNING: fixed quotas
-        if (lds_tables) hipLaunchKernelGGL((sgd1d_team_fused_kernel<B, true, false>), grid, block, lds, st, a, d_its, n_iters, pool);
-        else            hipLaunchKernelGGL((sgd1d_team_fused_kernel<B, false, false>), grid, block, 0, st, a, d_its, n_iters, pool);
+const void *fused_kernel_1d(const KernelShape &s, bool pooled) {
+    switch (s.bundle) {
+        case 16: return team_fused_kernel_1d<16>(s, pooled);
+        case 32: return team_fused_kernel_1d<32>(s, pooled);
+        case 64: return team_fused_kernel_1d<64>(s, pooled);
+        case 0: case 1: return pooled ? with_flag(s.lds_tables, [](auto L) { return kernel_addr(sgd1d_fused_kernel<L()>); }) : nullptr;
+        default: return nullptr;
     }
-    return hipGetLastError();
 }
-// fused range of iterations; only for the team kernel with its widest bundles (what the auto policy picks
-// on graphs large enough for launch overhead to matter).  pool: zeroed counters, pool_bytes(n_iters) of them, or null
-// (fixed quota per wave, free-running).
 size_t pool_bytes(uint64_t n_iters) { return (size_t)n_iters * POOL_SLOTS * POOL_STRIDE * sizeof(uint32_t); }
-hipError_t launch_1d_fused(const KArgs &a, const IterConsts *d_its, uint32_t n_iters, bool lds_tables, uint32_t *pool,
-                           dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-    switch (a.bundle) {
-        case 16: return launch_1d_fused_b<16>(a, d_its, n_iters, lds_tables, pool, grid, block, lds, st);
-        case 32: return launch_1d_fused_b<32>(a, d_its, n_iters, lds_tables, pool, grid, block, lds, st);
-        case 64: return launch_1d_fused_b<64>(a, d_its, n_iters, lds_tables, pool, grid, block, lds, st);
-        default: return hipErrorInvalidValue;
-    }
-}
 
-// reference streams, fused (K1d); pool: zeroed counters, pool_bytes(n_iters) of them
-hipError_t launch_1d_ref_fused(const KArgs &a, const IterConsts *d_its, uint32_t n_iters, bool lds_tables, uint32_t *pool,
-                               dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-    if (lds_tables) hipLaunchKernelGGL((sgd1d_fused_kernel<true>), grid, block, lds, st, a, d_its, n_iters, pool);
-    else            hipLaunchKernelGGL((sgd1d_fused_kernel<false>), grid, block, 0, st, a, d_its, n_iters, pool);
-    return hipGetLastError();
-}
-
-// The first launch of a kernel function costs the host ~0.1 ms (the runtime materialises the function lazily); a
-// caller that brackets its launch with events pays that inside the bracket.  Resolve the fused kernel a context will
-// use when the context is set up instead — and report how many of its workgroups one CU holds at once (registers,
-// waves per SIMD and the LDS table all count): the fused kernel has no grid barrier and must be launched with every
-// workgroup resident (capi.hip setup_common).
+// K1 for reference streams, K1b<B> for bundles of 4..64 (its debug trace always reads with agent-scope loads)
 template <int B>
-static hipError_t prepare_1d_fused_b(bool lds_tables, int block, size_t lds, int *blocks_per_cu) {
-    hipFuncAttributes attr;
-    const void *fn = lds_tables ? reinterpret_cast<const void *>(&sgd1d_team_fused_kernel<B, true, true>)
-                                : reinterpret_cast<const void *>(&sgd1d_team_fused_kernel<B, false, true>);
-    hipError_t e = hipFuncGetAttributes(&attr, fn);
-    if (e != hipSuccess) return e;
-    return lds_tables ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, sgd1d_team_fused_kernel<B, true, true>, block, lds)
-                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, sgd1d_team_fused_kernel<B, false, true>, block, 0);
+static const void *team_kernel_1d(const KernelShape &s) {
+    return with_flag(s.lds_tables, [&](auto L) { return with_flag(s.atomic_loads, [&](auto A) { return with_flag(s.trace, [&](auto T) {
+        return kernel_addr(sgd1d_team_kernel<B, L(), A() || T(), T()>);
+    }); }); });
 }
-hipError_t prepare_1d_fused(uint32_t bundle, bool lds_tables, int block, size_t lds, int *blocks_per_cu) {
-    switch (bundle) {
-        case 16: return prepare_1d_fused_b<16>(lds_tables, block, lds, blocks_per_cu);
-        case 32: return prepare_1d_fused_b<32>(lds_tables, block, lds, blocks_per_cu);
-        case 64: return prepare_1d_fused_b<64>(lds_tables, block, lds, blocks_per_cu);
-        default: *blocks_per_cu = 0; return hipSuccess;
-    }
-}
-
-hipError_t launch_1d(const KArgs &a, bool lds_tables, bool atomic_loads, bool trace,
-                     dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-    switch (a.bundle) {
+const void *iteration_kernel_1d(const KernelShape &s) {
+    switch (s.bundle) {
         case 0: case 1:
-            if (lds_tables) return atomic_loads ? launch_1d_t<true, true>(a, trace, grid, block, lds, st)
-                                                : launch_1d_t<true, false>(a, trace, grid, block, lds, st);
-            return atomic_loads ? launch_1d_t<false, true>(a, trace, grid, block, 0, st)
-                                : launch_1d_t<false, false>(a, trace, grid, block, 0, st);
-        case 4:  return launch_1db<4>(a, lds_tables, atomic_loads, trace, grid, block, lds, st);
-        case 8:  return launch_1db<8>(a, lds_tables, atomic_loads, trace, grid, block, lds, st);
-        case 16: return launch_1db<16>(a, lds_tables, atomic_loads, trace, grid, block, lds, st);
-        case 32: return launch_1db<32>(a, lds_tables, atomic_loads, trace, grid, block, lds, st);
-        case 64: return launch_1db<64>(a, lds_tables, atomic_loads, trace, grid, block, lds, st);
-        default: return hipErrorInvalidValue;
+            return with_flag(s.lds_tables, [&](auto L) { return with_flag(s.atomic_loads, [&](auto A) { return with_flag(s.trace, [&](auto T) {
+                return kernel_addr(sgd1d_kernel<L(), A(), T()>);
+            }); }); });
+        case 4:  return team_kernel_1d<4>(s);
+        case 8:  return team_kernel_1d<8>(s);
+        case 16: return team_kernel_1d<16>(s);
+        case 32: return team_kernel_1d<32>(s);
+        case 64: return team_kernel_1d<64>(s);
+        default: return nullptr;
     }
 }
 

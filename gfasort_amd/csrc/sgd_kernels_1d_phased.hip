@@ -7,6 +7,7 @@
 // under).  That is the oracle with gfo_state_set_bundle switched between 64 and 1 between iterations.
 // The device functions are sgd_1d.h's, shared with K1 / K1b / K1c / K1d.
 #include "sgd_1d.h"
+#include "sgd_host.h"
 
 namespace gfs {
 
@@ -74,24 +75,9 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 4))) sgd1d_phased_fused_ke
     flush_counters(a, ts.done, ts.att);
 }
 
-// pool: zeroed counters, pool_bytes(n_iters) of them (the phased launch is always pooled)
-hipError_t launch_1d_phased_fused(const KArgs &a, const IterConsts *d_its, uint32_t n_iters, bool lds_tables, uint32_t *pool,
-                                  dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-    if (lds_tables) hipLaunchKernelGGL((sgd1d_phased_fused_kernel<true>), grid, block, lds, st, a, d_its, n_iters, pool);
-    else            hipLaunchKernelGGL((sgd1d_phased_fused_kernel<false>), grid, block, 0, st, a, d_its, n_iters, pool);
-    return hipGetLastError();
-}
-
-// workgroups of K1e one CU holds at once (the fused launch needs every workgroup resident: capi.hip setup_common); also
-// resolves the kernel outside the first launch's event bracket (sgd_kernels_1d.hip prepare_1d_fused)
-hipError_t prepare_1d_phased_fused(bool lds_tables, int block, size_t lds, int *blocks_per_cu) {
-    hipFuncAttributes attr;
-    const void *fn = lds_tables ? reinterpret_cast<const void *>(&sgd1d_phased_fused_kernel<true>)
-                                : reinterpret_cast<const void *>(&sgd1d_phased_fused_kernel<false>);
-    hipError_t e = hipFuncGetAttributes(&attr, fn);
-    if (e != hipSuccess) return e;
-    return lds_tables ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, sgd1d_phased_fused_kernel<true>, block, lds)
-                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, sgd1d_phased_fused_kernel<false>, block, 0);
+// (the phased launch is always pooled)
+const void *phased_fused_kernel(bool lds_tables) {
+    return with_flag(lds_tables, [](auto L) { return kernel_addr(sgd1d_phased_fused_kernel<L()>); });
 }
 
 // loads this translation unit's code object (HIP loads modules on first use); see gfs_warmup

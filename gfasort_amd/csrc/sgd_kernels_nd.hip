@@ -1,5 +1,6 @@
 // sgd_kernels_nd.hip — K2: reference-stream kernels of path_linear_sgd_layout, D = 1..8.
 #include "sgd_kernel_common.h"
+#include "sgd_host.h"
 
 namespace gfs {
 
@@ -141,42 +142,43 @@ __global__ void sgdnd_fused_kernel(const KArgs a0, const IterConsts *its, const 
     flush_counters(a, done, att);
 }
 
-template <int D, bool L, bool A>
-static hipError_t launch_nd_t(const KArgs &a, bool trace, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-    if (trace) hipLaunchKernelGGL((sgdnd_kernel<D, L, A, true>), grid, block, lds, st, a);
-    else       hipLaunchKernelGGL((sgdnd_kernel<D, L, A, false>), grid, block, lds, st, a);
-    return hipGetLastError();
+template <int D>
+static const void *kernel_nd(const KernelShape &s) {
+    return with_flag(s.lds_tables, [&](auto L) { return with_flag(s.atomic_loads, [&](auto A) { return with_flag(s.trace, [&](auto T) {
+        return kernel_addr(sgdnd_kernel<D, L(), A(), T()>);
+    }); }); });
 }
-hipError_t launch_nd_ref(int dims, const KArgs &a, bool lds_tables, bool atomic_loads, bool trace,
-                         dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-#define GFS_ND_CASE(D)                                                                                   \
-    case D:                                                                                              \
-        if (lds_tables) return atomic_loads ? launch_nd_t<D, true, true>(a, trace, grid, block, lds, st)  \
-                                            : launch_nd_t<D, true, false>(a, trace, grid, block, lds, st); \
-        return atomic_loads ? launch_nd_t<D, false, true>(a, trace, grid, block, 0, st)                   \
-                            : launch_nd_t<D, false, false>(a, trace, grid, block, 0, st);
-    switch (dims) {
-        GFS_ND_CASE(1) GFS_ND_CASE(2) GFS_ND_CASE(3) GFS_ND_CASE(4)
-        GFS_ND_CASE(5) GFS_ND_CASE(6) GFS_ND_CASE(7) GFS_ND_CASE(8)
-        default: return hipErrorInvalidValue;
-    }
-#undef GFS_ND_CASE
+template <int D>
+static const void *fused_kernel_nd(bool lds_tables) {
+    return with_flag(lds_tables, [](auto L) { return kernel_addr(sgdnd_fused_kernel<D, L()>); });
 }
-
-// reference streams, fused (K2d); pool: zeroed counters, pool_bytes(n_iters) of them
-hipError_t launch_nd_ref_fused(int dims, const KArgs &a, const IterConsts *d_its, uint32_t n_iters, bool lds_tables, uint32_t *pool,
-                               dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-#define GFS_NDF_CASE(D)                                                                                              \
-    case D:                                                                                                          \
-        if (lds_tables) hipLaunchKernelGGL((sgdnd_fused_kernel<D, true>), grid, block, lds, st, a, d_its, n_iters, pool);  \
-        else            hipLaunchKernelGGL((sgdnd_fused_kernel<D, false>), grid, block, 0, st, a, d_its, n_iters, pool);   \
-        return hipGetLastError();
-    switch (dims) {
-        GFS_NDF_CASE(1) GFS_NDF_CASE(2) GFS_NDF_CASE(3) GFS_NDF_CASE(4)
-        GFS_NDF_CASE(5) GFS_NDF_CASE(6) GFS_NDF_CASE(7) GFS_NDF_CASE(8)
-        default: return hipErrorInvalidValue;
+const void *iteration_kernel_nd(const KernelShape &s) {
+    switch (s.dims) {
+        case 1: return kernel_nd<1>(s);
+        case 2: return kernel_nd<2>(s);
+        case 3: return kernel_nd<3>(s);
+        case 4: return kernel_nd<4>(s);
+        case 5: return kernel_nd<5>(s);
+        case 6: return kernel_nd<6>(s);
+        case 7: return kernel_nd<7>(s);
+        case 8: return kernel_nd<8>(s);
+        default: return nullptr;
     }
-#undef GFS_NDF_CASE
+}
+// reference streams, fused (K2d): pooled only
+const void *fused_kernel_nd(const KernelShape &s, bool pooled) {
+    if (!pooled) return nullptr;
+    switch (s.dims) {
+        case 1: return fused_kernel_nd<1>(s.lds_tables);
+        case 2: return fused_kernel_nd<2>(s.lds_tables);
+        case 3: return fused_kernel_nd<3>(s.lds_tables);
+        case 4: return fused_kernel_nd<4>(s.lds_tables);
+        case 5: return fused_kernel_nd<5>(s.lds_tables);
+        case 6: return fused_kernel_nd<6>(s.lds_tables);
+        case 7: return fused_kernel_nd<7>(s.lds_tables);
+        case 8: return fused_kernel_nd<8>(s.lds_tables);
+        default: return nullptr;
+    }
 }
 
 // loads this translation unit's code object (HIP loads modules on first use); see gfs_warmup

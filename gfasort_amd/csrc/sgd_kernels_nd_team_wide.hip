@@ -8,37 +8,25 @@
 
 namespace gfs {
 
-hipError_t launch_nd_team_wide(int dims, const KArgs &a, bool lds_tables, bool trace, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-#define GFS_NDB_CASE(D, B) if (dims == D && a.bundle == B) return launch_ndb<D, B>(a, lds_tables, true, trace, grid, block, lds, st);
+const void *iteration_kernel_nd_team_wide(const KernelShape &s) {
+#define GFS_NDB_CASE(D, B) if (s.dims == D && s.bundle == B) return team_kernel_nd<D, B>(s);
     GFS_NDB_CASE(4, 8) GFS_NDB_CASE(4, 16) GFS_NDB_CASE(4, 32) GFS_NDB_CASE(4, 64)
     GFS_NDB_CASE(5, 8) GFS_NDB_CASE(5, 16) GFS_NDB_CASE(5, 32) GFS_NDB_CASE(5, 64)
     GFS_NDB_CASE(6, 8) GFS_NDB_CASE(6, 16) GFS_NDB_CASE(6, 32) GFS_NDB_CASE(6, 64)
     GFS_NDB_CASE(7, 8) GFS_NDB_CASE(7, 16) GFS_NDB_CASE(7, 32) GFS_NDB_CASE(7, 64)
     GFS_NDB_CASE(8, 8) GFS_NDB_CASE(8, 16) GFS_NDB_CASE(8, 32) GFS_NDB_CASE(8, 64)
 #undef GFS_NDB_CASE
-    return hipErrorInvalidValue;
+    return nullptr;
 }
 
-hipError_t launch_nd_team_fused_wide(int dims, const KArgs &a, const IterConsts *d_its, uint32_t n_iters, bool lds_tables, uint32_t *pool,
-                                     dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-    switch (dims) {
-    case 4: return launch_nd_team_fused_d<4>(a, d_its, n_iters, lds_tables, pool, grid, block, lds, st);
-    case 5: return launch_nd_team_fused_d<5>(a, d_its, n_iters, lds_tables, pool, grid, block, lds, st);
-    case 6: return launch_nd_team_fused_d<6>(a, d_its, n_iters, lds_tables, pool, grid, block, lds, st);
-    case 7: return launch_nd_team_fused_d<7>(a, d_its, n_iters, lds_tables, pool, grid, block, lds, st);
-    case 8: return launch_nd_team_fused_d<8>(a, d_its, n_iters, lds_tables, pool, grid, block, lds, st);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t prepare_nd_team_fused_wide(int dims, bool lds_tables, int block, size_t lds, int *blocks_per_cu) {
-    switch (dims) {
-    case 4: return prepare_nd_team_fused_d<4>(lds_tables, block, lds, blocks_per_cu);
-    case 5: return prepare_nd_team_fused_d<5>(lds_tables, block, lds, blocks_per_cu);
-    case 6: return prepare_nd_team_fused_d<6>(lds_tables, block, lds, blocks_per_cu);
-    case 7: return prepare_nd_team_fused_d<7>(lds_tables, block, lds, blocks_per_cu);
-    case 8: return prepare_nd_team_fused_d<8>(lds_tables, block, lds, blocks_per_cu);
-    default: *blocks_per_cu = 0; return hipSuccess;
+const void *fused_kernel_nd_team_wide(const KernelShape &s, bool pooled) {
+    switch (s.dims) {
+    case 4: return team_fused_kernel_nd<4>(s, pooled);
+    case 5: return team_fused_kernel_nd<5>(s, pooled);
+    case 6: return team_fused_kernel_nd<6>(s, pooled);
+    case 7: return team_fused_kernel_nd<7>(s, pooled);
+    case 8: return team_fused_kernel_nd<8>(s, pooled);
+    default: return nullptr;
     }
 }
 

@@ -3,6 +3,7 @@
 // dispatcher) and sgd_kernels_nd_team_wide.hip (D = 4..8).
 #pragma once
 #include "sgd_kernel_common.h"
+#include "sgd_host.h"
 
 namespace gfs {
 
@@ -685,40 +686,16 @@ sgdnd_team_fused_kernel(const KArgs a0, const IterConsts *its, const uint32_t n_
     flush_counters(a, ts.done, ts.att);
 }
 
-// one launch of K2b for (D, B): LDS tables on/off, trace on/off
+// K2b for (D, B): LDS tables on/off, trace on/off; the layout team kernels always use agent-scope loads
 template <int D, int B>
-static hipError_t launch_ndb(const KArgs &a, bool lds_tables, bool atomic_loads, bool trace,
-                             dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-    // team kernel variants: LDS tables on/off; agent-scope loads; trace on/off
-    (void)atomic_loads;                               // team layout kernels always use agent-scope loads
-    if (lds_tables) {
-        if (trace) hipLaunchKernelGGL((sgdnd_team_kernel<D, B, true, true, true>), grid, block, lds, st, a);
-        else hipLaunchKernelGGL((sgdnd_team_kernel<D, B, true, true, false>), grid, block, lds, st, a);
-    } else {
-        if (trace) hipLaunchKernelGGL((sgdnd_team_kernel<D, B, false, true, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((sgdnd_team_kernel<D, B, false, true, false>), grid, block, 0, st, a);
-    }
-    return hipGetLastError();
+static const void *team_kernel_nd(const KernelShape &s) {
+    return with_flag(s.lds_tables, [&](auto L) { return with_flag(s.trace, [&](auto T) { return kernel_addr(sgdnd_team_kernel<D, B, L(), true, T()>); }); });
 }
-
-// K2c launcher for D at B = 64.  pool: zeroed counters, pool_bytes(n_iters) of them, or null (fixed quota per wave, free-running).
+// K2c for D at B = 64, pooled or with fixed quotas per wave (free-running)
 template <int D>
-static hipError_t launch_nd_team_fused_d(const KArgs &a, const IterConsts *d_its, uint32_t n_iters, bool lds_tables,
-                                         uint32_t *pool, dim3 grid, dim3 block, size_t lds, hipStream_t st) {
-    if (pool) {
-        if (lds_tables) hipLaunchKernelGGL((sgdnd_team_fused_kernel<D, 64, true, true>), grid, block, lds, st, a, d_its, n_iters, pool);
-        else            hipLaunchKernelGGL((sgdnd_team_fused_kernel<D, 64, false, true>), grid, block, 0, st, a, d_its, n_iters, pool);
-    } else {
-        if (lds_tables) hipLaunchKernelGGL((sgdnd_team_fused_kernel<D, 64, true, false>), grid, block, lds, st, a, d_its, n_iters, pool);
-        else            hipLaunchKernelGGL((sgdnd_team_fused_kernel<D, 64, false, false>), grid, block, 0, st, a, d_its, n_iters, pool);
-    }
-    return hipGetLastError();
-}
-// workgroups of the fused kernel one CU holds at once
-template <int D>
-static hipError_t prepare_nd_team_fused_d(bool lds_tables, int block, size_t lds, int *blocks_per_cu) {
-    return lds_tables ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, sgdnd_team_fused_kernel<D, 64, true, true>, block, lds)
-                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, sgdnd_team_fused_kernel<D, 64, false, true>, block, 0);
+static const void *team_fused_kernel_nd(const KernelShape &s, bool pooled) {
+    if (s.bundle != 64u) return nullptr;
+    return with_flag(pooled, [&](auto P) { return with_flag(s.lds_tables, [&](auto L) { return kernel_addr(sgdnd_team_fused_kernel<D, 64, L(), P()>); }); });
 }
 
 }  // namespace gfs

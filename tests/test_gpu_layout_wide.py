@@ -113,14 +113,20 @@ def test_wide_fused_layout_launch_equals_per_iteration_launches_on_one_wave(dims
     p.min_term_updates = 150_000
     c0 = gaussian_init(g, dims, 5)
     out = []
-    for extra in (0, hip.F_NO_FUSE):
+    # (and the kernels' other forms, bit for bit the same on one wave: fixed quotas — one wave's is the whole iteration, in the
+    # pool's chunks — and tables read from global memory)
+    others = (hip.F_DBG_FREE_RUNNING, hip.F_NO_LDS_TABLES, hip.F_NO_LDS_TABLES | hip.F_DBG_FREE_RUNNING, hip.F_NO_LDS_TABLES | hip.F_NO_FUSE)
+    for extra in (0, hip.F_NO_FUSE) + others:
         ctx = hip.Context(g)
         ctx.setup_nd(p, hip.make_config(n_streams=64, flags=hip.F_BUNDLE(64) | extra))
         ctx.upload(c0)
         ctx.run()
         out.append((ctx.download(), ctx.stats()))
         ctx.close()
-    (cf, sf), (cu, su) = out
+    for (c, s), launches in zip(out[2:], (1, 1, 1, 10)):
+        assert s.launches == launches and (s.term_updates, s.attempts) == (out[1][1].term_updates, out[1][1].attempts)
+        assert np.array_equal(c.view(np.uint64), out[1][0].view(np.uint64))
+    (cf, sf), (cu, su) = out[:2]
     assert (sf.launches, su.launches) == (1, 10) and sf.iterations == su.iterations == 10
     assert (sf.term_updates, sf.attempts) == (su.term_updates, su.attempts) and sf.term_updates == 10 * p.min_term_updates
     assert np.array_equal(cf.view(np.uint64), cu.view(np.uint64))

@@ -737,6 +737,19 @@ def test_wide_index_path_matches_oracle(bundle):
 
 
 # ---- fused persistent launch (gfs_ctx_run_range) -------------------------------------------------------------
+# The other forms of the team kernels, on one wave bit for bit the run of one launch per iteration too: the fused kernel with
+# fixed quotas (GFS_F_DBG_FREE_RUNNING: one wave's quota is the whole iteration, worked through in the pool's chunks), and every
+# kernel reading its tables from global memory (GFS_F_NO_LDS_TABLES: the same values).
+_OTHER_FORMS = (hip.F_DBG_FREE_RUNNING, hip.F_NO_LDS_TABLES, hip.F_NO_LDS_TABLES | hip.F_DBG_FREE_RUNNING, hip.F_NO_LDS_TABLES | hip.F_NO_FUSE)
+
+
+def _check_other_forms(out, x_unfused, s_unfused, n_iterations):
+    for (x, s), launches in zip(out, (1, 1, 1, n_iterations)):
+        assert s.launches == launches and s.iterations == n_iterations
+        assert (s.term_updates, s.attempts) == (s_unfused.term_updates, s_unfused.attempts)
+        assert np.array_equal(x.view(np.uint64), x_unfused.view(np.uint64))
+
+
 @pytest.mark.parametrize("bundle", [16, 64])
 def test_fused_launch_equals_per_iteration_launches_on_one_wave(bundle):
     """One wave is deterministic, and the fused kernel keeps the per-iteration kernel's flush points: the whole
@@ -745,7 +758,7 @@ def test_fused_launch_equals_per_iteration_launches_on_one_wave(bundle):
     p = P.YgsParams.from_graph(g, 0, 1).path_sgd
     p.iter_max = 12
     out = []
-    for extra in (0, hip.F_NO_FUSE):
+    for extra in (0, hip.F_NO_FUSE) + _OTHER_FORMS + (hip.F_PLAIN_LOADS,):
         ctx = hip.Context(g)
         ctx.setup_1d(p, hip.make_config(n_streams=64, flags=hip.F_BUNDLE(bundle) | extra))
         ctx.upload(hip.init_positions(g))
@@ -753,10 +766,14 @@ def test_fused_launch_equals_per_iteration_launches_on_one_wave(bundle):
         st = ctx.stats()
         out.append((ctx.download(), st))
         ctx.close()
-    (xf, sf), (xu, su) = out
+    (xf, sf), (xu, su) = out[:2]
     assert (sf.launches, su.launches) == (1, 13) and sf.iterations == su.iterations == 13
     assert (sf.term_updates, sf.attempts) == (su.term_updates, su.attempts) and sf.term_updates == 13 * p.min_term_updates
     assert np.array_equal(xf.view(np.uint64), xu.view(np.uint64))
+    _check_other_forms(out[2:2 + len(_OTHER_FORMS)], xu, su, 13)
+    # plain loads do not fuse; they may see a position before an atomic add of the same wave has landed, so only the counts are held
+    xp, sp = out[-1]
+    assert sp.launches == 13 and sp.iterations == 13 and sp.term_updates == su.term_updates and np.isfinite(xp).all()
 
 
 @pytest.mark.parametrize("dims", [2, 3])
@@ -769,17 +786,18 @@ def test_fused_layout_launch_equals_per_iteration_launches_on_one_wave(dims):
     p.min_term_updates = 150_000
     c0 = gaussian_init(g, dims, 5)
     out = []
-    for extra in (0, hip.F_NO_FUSE):
+    for extra in (0, hip.F_NO_FUSE) + _OTHER_FORMS:
         ctx = hip.Context(g)
         ctx.setup_nd(p, hip.make_config(n_streams=64, flags=hip.F_BUNDLE(64) | extra))
         ctx.upload(c0)
         ctx.run()
         out.append((ctx.download(), ctx.stats()))
         ctx.close()
-    (cf, sf), (cu, su) = out
+    (cf, sf), (cu, su) = out[:2]
     assert (sf.launches, su.launches) == (1, 10) and sf.iterations == su.iterations == 10
     assert (sf.term_updates, sf.attempts) == (su.term_updates, su.attempts) and sf.term_updates == 10 * p.min_term_updates
     assert np.array_equal(cf.view(np.uint64), cu.view(np.uint64))
+    _check_other_forms(out[2:], cu, su, 10)
 
 
 @pytest.mark.parametrize("dims", [2, 3])
@@ -844,11 +862,13 @@ def test_reference_streams_fused_equal_unfused_equal_oracle_on_one_stream(name, 
     rc, st, _ = O.sgd_1d(og, op, x_ref, n_streams=1)
     assert rc == 0
     out = []
-    for extra in (0, hip.F_NO_FUSE):
+    for extra in (0, hip.F_NO_FUSE, hip.F_NO_LDS_TABLES):
         rc, x, hst = hip.path_linear_sgd_raw(g, p, cfg=hip.make_config(n_streams=1, flags=extra))
         assert rc == 0 and hst.bundle == 1
         out.append((x, hst))
-    (xf, sf), (xu, su) = out
+    (xf, sf), (xu, su), (xg, sg) = out
+    assert sg.launches == 1 and (sg.term_updates, sg.attempts) == (st.term_updates, st.attempts)      # K1d reading its tables from global memory
+    assert np.array_equal(xg.view(np.uint64), x_ref.view(np.uint64))
     assert (sf.launches, su.launches) == (1, iter_max + 1) and sf.iterations == su.iterations == iter_max + 1
     assert sf.term_updates == su.term_updates == st.term_updates == (iter_max + 1) * p.min_term_updates
     assert sf.attempts == su.attempts == st.attempts

@@ -112,15 +112,15 @@ def test_fused_equals_per_iteration_launches_single_wave(graph, monkeypatch):
     p = _wave_params(g)
     window = (3, 7)
     out = []
-    for extra, want in ((0, 1), (hip.F_NO_FUSE, 9)):
+    for extra, want in ((0, 1), (hip.F_NO_FUSE, 9), (hip.F_NO_LDS_TABLES, 1)):      # (the last: K1e reading its tables from global memory)
         ctx = _phased(g, p, 64, window, extra)
         hst, x = ctx.stats(), ctx.download()
         ctx.close()
         assert hst.launches == want and hst.term_updates == 9 * 200_000
         out.append((x, hst))
-    (xf, sf), (xu, su) = out
-    assert sf.attempts == su.attempts
-    assert np.array_equal(xf.view(np.uint64), xu.view(np.uint64))
+    (xf, sf), (xu, su), (xg, sg) = out
+    assert sf.attempts == su.attempts == sg.attempts
+    assert np.array_equal(xf.view(np.uint64), xu.view(np.uint64)) and np.array_equal(xg.view(np.uint64), xu.view(np.uint64))
     # and both draw what the oracle with its bundle switched for the window draws (its positions differ: its reference streams
     # take one attempt each in turn, 64 lanes of a wave take theirs at once)
     x_ref = O.init_positions(oracle_graph(g))
