@@ -1089,7 +1089,7 @@ int gfs_ctx_run_range(gfs_ctx *c, const uint64_t *ks, uint64_t n, void *hip_stre
         if (c->bundle > 1 && v >= 64 && v <= 16384 && !(v & (v - 1))) a.chunk = (uint32_t)v;
     }
     iter_consts(c, ks[0], a.it);
-    // work pools (sgd_kernels_1d.hip): the waves draw an iteration's updates from shared counters, zeroed per launch
+    // work pools (sgd_kernel_common.h pool_walk): the waves draw an iteration's updates from shared counters, zeroed per launch
     uint32_t *pool = nullptr;
     if (pl.pooled) {
         if (c->pool_cap < n) {

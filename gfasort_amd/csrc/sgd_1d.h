@@ -64,13 +64,7 @@ __device__ __forceinline__ void ref_run_1d(const KArgs &a, const uint4 *path_tab
             add_pos(x + cur.j, r_x);                                                   // :576
         }
         ++d;                                                                           // :579
-        if (TRACE) {
-            if (ntr < a.trace_per_stream) {
-                TraceTerm *tt = reinterpret_cast<TraceTerm *>(a.trace) + (size_t)tid * a.trace_per_stream + ntr;
-                tt->i = cur.i; tt->j = cur.j; tt->d = cur.term_dist;
-                ++ntr;
-            }
-        }
+        if (TRACE) record_trace(a, tid, ntr, cur.i, cur.j, cur.term_dist);
     }
     done += d;
     att += t > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)t;
@@ -222,25 +216,14 @@ __device__ __forceinline__ bool fused_trip(const KArgs &a, TeamState &ts, const 
 #pragma unroll
     for (uint32_t colour = 0; colour < 2u; ++colour) {
         ++ts.att;
-        bool valid = term_ok && grp == colour;
-        const unsigned long long vmask = __ballot(valid);
-        const uint64_t remaining = wave_quota - wave_done;
-        const uint32_t nvalid = (uint32_t)__popcll(vmask);
-        if (valid && nvalid > remaining) valid = (uint32_t)__popcll(vmask & ((1ull << lane) - 1ull)) < remaining;
-        wave_done += nvalid < remaining ? nvalid : remaining;
+        const bool valid = quota_cut(term_ok && grp == colour, lane, wave_quota, wave_done);
         const double xpart_in = shfl_f64(xo, dstc);                    // partner's CURRENT position (colour 0's result for colour 1)
         const double xj = out ? xp : xpart_in;
         double r_x = 0.0;
         if (valid) {
             r_x = term_move(a, term_dist, xo, xj, crowd);
             ++ts.done;                                                                 // :579
-            if (TRACE) {
-                if (ts.ntr < a.trace_per_stream) {
-                    TraceTerm *tt = reinterpret_cast<TraceTerm *>(a.trace) + (size_t)tid * a.trace_per_stream + ts.ntr;
-                    tt->i = node; tt->j = pnode; tt->d = term_dist;
-                    ++ts.ntr;
-                }
-            }
+            if (TRACE) record_trace(a, tid, ts.ntr, node, pnode, term_dist);
         }
         // the +r of the lane whose partner I am
         // (every shuffle is a statement of its own: inside `a && __shfl(..)` or `c ? x : __shfl(..)` the compiler may run it
@@ -288,22 +271,12 @@ __device__ __forceinline__ bool twin_trip(const KArgs &a, TeamState &ts, const T
         const uint4 &rp = p ? cur.rc : cur.rb;
         const uint32_t pn = p ? nc : nb;
         const double term_dist = fabs(pa - rec_pos(rp));                               // sgd.rs:513
-        bool valid = term_dist != 0.0 && node != 0xFFFFFFFFu && pn != 0xFFFFFFFFu;     // :514, :525-538
-        const unsigned long long vmask = __ballot(valid);
-        const uint64_t remaining = wave_quota - wave_done;
-        const uint32_t nvalid = (uint32_t)__popcll(vmask);
-        if (valid && nvalid > remaining) valid = (uint32_t)__popcll(vmask & ((1ull << lane) - 1ull)) < remaining;
-        wave_done += nvalid < remaining ? nvalid : remaining;
+        const bool valid = quota_cut(term_dist != 0.0 && node != 0xFFFFFFFFu && pn != 0xFFFFFFFFu,   // :514, :525-538
+                                     lane, wave_quota, wave_done);
         if (valid) {
             const double r_x = term_move(a, term_dist, xa, p ? xc : xb, crowd_shift<true>(a, cur.ra, rp));   // :518-571
             ++ts.done;                                                                 // :579
-            if (TRACE) {
-                if (ts.ntr < a.trace_per_stream) {
-                    TraceTerm *tt = reinterpret_cast<TraceTerm *>(a.trace) + (size_t)tid * a.trace_per_stream + ts.ntr;
-                    tt->i = node; tt->j = pn; tt->d = term_dist;
-                    ++ts.ntr;
-                }
-            }
+            if (TRACE) record_trace(a, tid, ts.ntr, node, pn, term_dist);
             xa = xa - r_x;                                                             // :575
             acc = touched ? acc - r_x : -r_x; touched = true;
             if (!(a.dbg & 1u)) add_pos(x + pn, r_x);                                   // :576
@@ -392,14 +365,7 @@ __device__ __forceinline__ void team_iteration(const KArgs &a, const uint4 *path
                 i = ra.x; j = rb.x;
                 valid = term_dist != 0.0 && i != 0xFFFFFFFFu && j != 0xFFFFFFFFu;      // :514, :525-538
             }
-            const unsigned long long vmask = __ballot(valid);
-            const uint64_t remaining = wave_quota - wave_done;
-            const uint32_t nvalid = (uint32_t)__popcll(vmask);
-            if (valid && nvalid > remaining) {
-                const uint32_t rank = (uint32_t)__popcll(vmask & ((1ull << lane) - 1ull));
-                valid = rank < remaining;
-            }
-            wave_done += nvalid < remaining ? nvalid : remaining;
+            valid = quota_cut(valid, lane, wave_quota, wave_done);
             double xi = 0.0, xj = 0.0;
             if (valid) {
                 if (a.dbg & 2u) { xi = (double)i; xj = (double)j; }                    // ablation: no position loads
@@ -409,13 +375,7 @@ __device__ __forceinline__ void team_iteration(const KArgs &a, const uint4 *path
             if (valid) {
                 r_x = term_move(a, term_dist, xi, xj, crowd_shift<true>(a, ra, rb));   // :518-571
                 ++ts.done;                                                             // :579
-                if (TRACE) {
-                    if (ts.ntr < a.trace_per_stream) {
-                        TraceTerm *tt = reinterpret_cast<TraceTerm *>(a.trace) + (size_t)tid * a.trace_per_stream + ts.ntr;
-                        tt->i = i; tt->j = j; tt->d = term_dist;
-                        ++ts.ntr;
-                    }
-                }
+                if (TRACE) record_trace(a, tid, ts.ntr, i, j, term_dist);
             }
             // the adds of this trip (:575-576): -r_x to node i, +r_x to node j
             bool o1f = valid, o2f = valid; uint32_t o1s = i, o2s = j; double o1v = -r_x, o2v = r_x;
@@ -442,38 +402,6 @@ __device__ __forceinline__ void team_iteration(const KArgs &a, const uint4 *path
             cur = nxt; t = t_n; colour = colour_n; seg = seg_n; p = p_n;
         }
     }
-}
-
-// lead word: ok bits of partner 0 (0..7) | trips left (8..15) | cooling (16) | colour (17) | seg (18..25) | partner (26) |
-// ok bits of partner 1 (27..31)
-__device__ __forceinline__ void load_pass(const KArgs &a, uint32_t tid, TeamState &ts) {
-    if (!a.lead) return;
-    const uint64_t T = a.n_streams;
-    ts.L.first_lo = a.lead[tid]; ts.L.first_hi = a.lead[T + tid]; ts.L.cnt = a.lead[2 * T + tid];
-    ts.L.ra0 = a.lead[3 * T + tid]; ts.L.rb0 = a.lead[4 * T + tid];
-    const uint32_t w = a.lead[5 * T + tid];
-    ts.L.ra1 = a.lead[6 * T + tid]; ts.L.rb1 = a.lead[7 * T + tid];
-    ts.L.ok = (w & 0xFFu) | ((w >> 27) << 8);
-    // (the place in the pass is the same for all 64 lanes of the wave: scalar registers)
-    const uint32_t ws = (uint32_t)__builtin_amdgcn_readfirstlane((int)w);
-    ts.left = (ws >> 8) & 0xFFu; ts.cool = (ws >> 16) & 1u; ts.colour = (ws >> 17) & 1u; ts.seg = (ws >> 18) & 0xFFu; ts.p = (ws >> 26) & 1u;
-}
-__device__ __forceinline__ void store_pass(const KArgs &a, uint32_t tid, const TeamState &ts) {
-    if (!a.lead) return;
-    const uint64_t T = a.n_streams;
-    a.lead[tid] = ts.L.first_lo; a.lead[T + tid] = ts.L.first_hi; a.lead[2 * T + tid] = ts.L.cnt;
-    a.lead[3 * T + tid] = ts.L.ra0; a.lead[4 * T + tid] = ts.L.rb0;
-    a.lead[5 * T + tid] = (ts.L.ok & 0xFFu) | (ts.left << 8) | (ts.cool << 16) | (ts.colour << 17) | (ts.seg << 18) | (ts.p << 26) |
-                          (((ts.L.ok >> 8) & 0x1Fu) << 27);
-    a.lead[6 * T + tid] = ts.L.ra1; a.lead[7 * T + tid] = ts.L.rb1;
-}
-
-__device__ __forceinline__ uint64_t wave_quota_of(const KArgs &a, uint32_t tid) {
-    // wave quota = sum of its 64 lanes' per-stream quotas
-    const uint32_t wave_first = tid & ~63u;
-    uint64_t wq = (uint64_t)a.quota_base * 64u;
-    if (wave_first < a.quota_rem) wq += (a.quota_rem - wave_first) < 64u ? (a.quota_rem - wave_first) : 64u;
-    return wq;
 }
 
 }  // namespace gfs

@@ -96,7 +96,8 @@ struct KArgs {
     void           *trace;         // gfs_term[n_streams*trace_per_stream] or null
     uint32_t       *trace_cnt;     // [n_streams]
     uint32_t       *lead;          // [8][n_streams] SoA: leaders a 1D team wave has sampled but not yet expanded
-                                   // (first lo, first hi, cnt, ra0, rb0, ok | trips left << 8 | ..., ra1, rb1: load_pass); or null
+                                   // (first lo, first hi, cnt, ra0, rb0, ok | trips left << 8 | ..., ra1, rb1:
+                                   // sgd_kernel_common.h load_pass); or null
     uint64_t n_steps, steps_thresh;   // thresh = (2^w - n) mod n, w = 32 if n_steps <= u32::MAX else 64
     uint32_t n_paths, zlen_full;   // zlen_full: true table length (index clamp, sgd.rs:469)
     uint32_t zlen_staged;          // entries copied to LDS (>= every reachable index)
@@ -272,7 +273,7 @@ __device__ __forceinline__ uint32_t leader_ok(uint32_t okw, uint32_t p) { return
 // both terms of a lane from one load of its a-side record and position, with one add for the a-side (TWIN trip,
 // sgd_kernels_1d.hip twin_trip): 3 blocks of records, position loads and atomic requests for 128 updates instead of 4.
 // The kernel is bound by the memory side's atomic units, then by HBM bytes; this takes a quarter off both.
-// A team wave works through an iteration in CHUNKS of this many updates (sgd_kernels_1d.hip, work pools); the rank cut-off
+// A team wave works through an iteration in CHUNKS of this many updates (sgd_kernel_common.h, work pools); the rank cut-off
 // that makes a count exact applies at the end of every chunk.  2048 = 32 full trips.
 constexpr uint32_t TEAM_CHUNK = 2048;        // (the value of KArgs.chunk unless a probe says otherwise: capi.hip gfs_ctx_run_range)
 // ... and of this many in the layout kernels: their pool is ONE counter per iteration (sgd_kernels_nd_team.hip K2c), and half as many

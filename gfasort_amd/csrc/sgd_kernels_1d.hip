@@ -17,21 +17,20 @@ __global__ void sgd1d_kernel(const KArgs a) {
     uint32_t done = 0, att = 0;
     if (live) {
         Rng rng;
-        const uint64_t T = a.n_streams;
-        rng.s0 = a.rng[tid]; rng.s1 = a.rng[T + tid]; rng.s2 = a.rng[2 * T + tid]; rng.s3 = a.rng[3 * T + tid];
+        load_rng(a, tid, rng);
         const uint32_t quota = a.quota_base + (tid < a.quota_rem ? 1u : 0u);
         const uint64_t max_att64 = (uint64_t)a.attempt_factor * quota + 1024u;
         const uint64_t max_att = max_att64 > 0xFFFFFFFFull ? 0xFFFFFFFFull : max_att64;
         uint32_t ntr = TRACE ? a.trace_cnt[tid] : 0;
         ref_run_1d<LDS_TABLES, ATOMIC_LOADS, TRACE>(a, path_tab, zeta_tab, rng, quota, max_att, tid, done, att, ntr);
-        a.rng[tid] = rng.s0; a.rng[T + tid] = rng.s1; a.rng[2 * T + tid] = rng.s2; a.rng[3 * T + tid] = rng.s3;
+        store_rng(a, tid, rng);
         if (TRACE) a.trace_cnt[tid] = ntr;
     }
     flush_counters(a, done, att);
 }
 
 // K1d: the same streams, a range of iterations in one persistent launch with work pools (sgd_kernel_common.h
-// ref_pooled_walk).  RNG state stays in registers for the whole schedule.
+// ref_pooled_walk, pool_walk).  RNG state stays in registers for the whole schedule.
 template <bool LDS_TABLES>
 __global__ void sgd1d_fused_kernel(const KArgs a0, const IterConsts *its, const uint32_t n_iters, uint32_t *pool) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -40,15 +39,14 @@ __global__ void sgd1d_fused_kernel(const KArgs a0, const IterConsts *its, const 
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
     if ((tid & ~63u) >= a0.n_streams) return;                          // waves without a live lane
     const bool live = tid < a0.n_streams;
-    const uint64_t T = a0.n_streams;
     KArgs a = a0;
     Rng rng = {0, 0, 0, 0};
-    if (live) { rng.s0 = a.rng[tid]; rng.s1 = a.rng[T + tid]; rng.s2 = a.rng[2 * T + tid]; rng.s3 = a.rng[3 * T + tid]; }
+    if (live) load_rng(a, tid, rng);
     uint32_t done = 0, att = 0, ntr = 0;
     ref_pooled_walk(a, its, n_iters, pool, tid, [&](const uint32_t share, const uint64_t max_att) {
         ref_run_1d<LDS_TABLES, true, false>(a, path_tab, zeta_tab, rng, share, max_att, tid, done, att, ntr);
     });
-    if (live) { a.rng[tid] = rng.s0; a.rng[T + tid] = rng.s1; a.rng[2 * T + tid] = rng.s2; a.rng[3 * T + tid] = rng.s3; }
+    if (live) store_rng(a, tid, rng);
     flush_counters(a, done, att);
 }
 
@@ -63,42 +61,23 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 4))) sgd1d_team_kernel(con
     stage_tables<LDS_TABLES>(a, smem, path_tab, zeta_tab);
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;       // n_streams % 64 == 0 (host-checked)
     if (tid >= a.n_streams) return;                                   // whole waves only
-    const uint64_t T = a.n_streams;
     TeamState ts;
-    ts.rng.s0 = a.rng[tid]; ts.rng.s1 = a.rng[T + tid]; ts.rng.s2 = a.rng[2 * T + tid]; ts.rng.s3 = a.rng[3 * T + tid];
+    uint32_t no_flips = 0;                                            // (the sort has no end flips)
+    load_rng(a, tid, ts.rng);
     ts.ntr = TRACE ? a.trace_cnt[tid] : 0;
-    load_pass(a, tid, ts);
-    const uint64_t wq = wave_quota_of(a, tid);                        // worked through in chunks, like a pool (K1c)
+    load_pass(a, tid, ts, no_flips);
+    const uint64_t wq = wave_quota_of(a, tid & ~63u);                 // worked through in chunks, like a pool (K1c)
     for (uint64_t done = 0; done < wq; done += a.chunk)
         team_iteration<B, LDS_TABLES, ATOMIC_LOADS, TRACE>(a, path_tab, zeta_tab, ts, tid, wq - done < a.chunk ? wq - done : a.chunk);
-    a.rng[tid] = ts.rng.s0; a.rng[T + tid] = ts.rng.s1; a.rng[2 * T + tid] = ts.rng.s2; a.rng[3 * T + tid] = ts.rng.s3;
+    store_rng(a, tid, ts.rng);
     if (TRACE) a.trace_cnt[tid] = ts.ntr;
-    store_pass(a, tid, ts);
+    store_pass(a, tid, ts, 0u);
     flush_counters(a, ts.done, ts.att);
 }
 
 // K1c: the same, FUSED over a range of iterations (single-GPU runs): one persistent launch in which every wave walks
-// the schedule its[0..n_iters).  Saves the per-launch ramp, tail and RNG round trip.
-//
-// WORK POOLS.  Round 1 gave every wave a fixed quota per iteration and no grid barrier.  Free-running waves drift apart:
-// one whose trips happen to be cheap runs iterations ahead of one whose trips are dear, so terms of several iterations —
-// several values of eta — are applied side by side, and the last, finest iterations are finished by the stragglers alone.
-// (The reference's iterations overlap by what its workers do in 1 ms, sgd.rs:366-403: a few per cent of an iteration.)
-// Measured on the 525k-node bubble graph: relative error at path distance 1 of 0.195-0.246 depending on the stream count
-// with free-running waves, 0.187-0.191 at every count with one launch per iteration — which is what the oracle's
-// sequential mirror gives (profiles/r02/pacing.log).  A counting barrier per iteration (with a lag of 1-6 iterations)
-// restores the precision but leaves the fast waves idle: C3 66-88 G updates/s against 93.
-// Instead an iteration's min_term_updates updates are a POOL that the waves draw from in chunks of TEAM_CHUNK updates
-// (one returning atomic per chunk, on one of up to 16 counters — one per 16 waves, sgd_kernel_common.h pool_slots — so that the
-// claims do not queue on one address; a wave
-// claims its next chunk before it works on the current one).  A wave moves on to iteration k + 1 when its counter of
-// iteration k is exhausted: no wave is ever more than two chunks away from the others OF ITS COUNTER (the counters are fixed
-// shares of an iteration: the waves of a fast one can run ahead of a slow one's — harmless for the sort, whose figures are the
-// same with a launch per iteration; the layout kernel, K2c, uses one counter), nobody waits, and a wave that is
-// slow simply takes fewer chunks — which is the reference's own rule (its workers share one count per iteration).  Every
-// iteration still applies exactly min_term_updates updates with its own eta/theta.  C3: 97.8 G updates/s.
-// (A single wave claims every chunk itself, in order: the kernel with fixed quotas works through its quota in the same
-// chunks, so that one wave is bit for bit the oracle's mirror in both.)
+// the schedule its[0..n_iters) and draws each iteration's updates from its work pool in chunks of TEAM_CHUNK (sgd_kernel_common.h
+// pool_walk has the reasons and the rules).  Saves the per-launch ramp, tail and RNG round trip.
 // (POOL is a template parameter so that each build holds ONE inlined copy of the trip machine: with both launch modes in one
 // kernel the pooled path spilled 65 VGPRs into 188 B of scratch per lane — and a first dispatch that needs more scratch than any
 // kernel before it makes the runtime re-size the queue's scratch, the ~0.12 ms "first-dispatch latency" of profiles/r02/launch_gap.log.)
@@ -111,45 +90,28 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 4))) sgd1d_team_fused_kern
     stage_tables<LDS_TABLES>(a0, smem, path_tab, zeta_tab);
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
     if (tid >= a0.n_streams) return;
-    const uint64_t T = a0.n_streams;
     KArgs a = a0;
     TeamState ts;
-    ts.rng.s0 = a.rng[tid]; ts.rng.s1 = a.rng[T + tid]; ts.rng.s2 = a.rng[2 * T + tid]; ts.rng.s3 = a.rng[3 * T + tid];
-    const int lane = threadIdx.x & 63;
-    load_pass(a, tid, ts);
+    uint32_t no_flips = 0;                                            // (the sort has no end flips)
+    load_rng(a, tid, ts.rng);
+    load_pass(a, tid, ts, no_flips);
     if (POOL) {
-        const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), n_waves = a0.n_streams >> 6;   // (scalar registers)
-        const uint32_t slots = pool_slots(n_waves), slot = wave % slots;
-        const uint64_t total = (uint64_t)a0.quota_base * a0.n_streams + a0.quota_rem;
-        const uint32_t cap = (uint32_t)(total / slots + (slot < total % slots ? 1u : 0u));   // < 2^31 (host-checked)
-        uint32_t k = 0, claim = 0;
-        a.it = its[0];
-        if (lane == 0) claim = __hip_atomic_fetch_add(pool + slot * POOL_STRIDE, a0.chunk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        while (k < n_iters) {
-            const uint32_t old = (uint32_t)__builtin_amdgcn_readfirstlane((int)claim);
-            if (old >= cap) {                                          // this iteration's pool is exhausted
-                if (++k == n_iters) break;
-                a.it = its[k];                                         // wave-uniform: scalar loads
-                if (lane == 0) claim = __hip_atomic_fetch_add(pool + ((size_t)k * POOL_SLOTS + slot) * POOL_STRIDE, a0.chunk,
-                                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                continue;
-            }
-            // the next claim travels while this chunk is worked on
-            if (lane == 0) claim = __hip_atomic_fetch_add(pool + ((size_t)k * POOL_SLOTS + slot) * POOL_STRIDE, a0.chunk,
-                                                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            team_iteration<B, LDS_TABLES, ATOMIC_LOADS, false>(a, path_tab, zeta_tab, ts, tid, cap - old < a0.chunk ? cap - old : a0.chunk, its + k);
-        }
+        const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));   // (scalar registers)
+        pool_walk(a, its, n_iters, pool, pool_share(a0, wave, a0.n_streams >> 6), [&]() __attribute__((always_inline)) { return a0.chunk; },
+                  [&](const uint32_t k, const uint32_t m) __attribute__((always_inline)) {
+            team_iteration<B, LDS_TABLES, ATOMIC_LOADS, false>(a, path_tab, zeta_tab, ts, tid, m, its + k);
+        });
     } else {
         // fixed quota per wave and iteration, free-running (GFS_F_DBG_FREE_RUNNING)
-        const uint64_t wq = wave_quota_of(a, tid);
+        const uint64_t wq = wave_quota_of(a, tid & ~63u);
         for (uint32_t k = 0; k < n_iters; ++k) {
             a.it = its[k];
             for (uint64_t done = 0; done < wq; done += a.chunk)
                 team_iteration<B, LDS_TABLES, ATOMIC_LOADS, false>(a, path_tab, zeta_tab, ts, tid, wq - done < a.chunk ? wq - done : a.chunk, its + k);
         }
     }
-    a.rng[tid] = ts.rng.s0; a.rng[T + tid] = ts.rng.s1; a.rng[2 * T + tid] = ts.rng.s2; a.rng[3 * T + tid] = ts.rng.s3;
-    store_pass(a, tid, ts);
+    store_rng(a, tid, ts.rng);
+    store_pass(a, tid, ts, 0u);
     flush_counters(a, ts.done, ts.att);
 }
 

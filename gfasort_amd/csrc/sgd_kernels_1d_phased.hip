@@ -11,10 +11,11 @@
 
 namespace gfs {
 
-// The work pools of K1c / K1d (sgd_kernel_common.h): iteration k's updates are claimed from its own counters, in chunks of
-// TEAM_CHUNK updates per wave in a team iteration and of REF_CHUNK_PER_LANE per lane in a window iteration (each drawn dry
-// before the wave moves on, so every iteration applies exactly its updates).  The claim a wave sends ahead is always for the
-// iteration it works in; the first claim of iteration k + 1 is sized by k + 1's own sampler.
+// The work pools of K1c / K1d (sgd_kernel_common.h pool_walk): iteration k's updates are claimed from its own counters, in chunks
+// of TEAM_CHUNK updates per wave in a team iteration and of REF_CHUNK_PER_LANE per lane in a window iteration (each drawn dry
+// before the wave moves on, so every iteration applies exactly its updates).  The first claim of iteration k + 1 is sized by
+// k + 1's own sampler, not by k's: one wave is bit for bit K1d in a window iteration and K1c in a team iteration (tested), and
+// each works through an iteration in its own chunks.
 // (4 waves per SIMD, as K1c: the trip machine needs its 128 VGPRs; ref_run_1d needs far fewer.)
 template <bool LDS_TABLES>
 __global__ void __attribute__((amdgpu_waves_per_eu(4, 4))) sgd1d_phased_fused_kernel(const KArgs a0, const IterConsts *its, const uint32_t n_iters,
@@ -25,35 +26,33 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 4))) sgd1d_phased_fused_ke
     stage_tables<LDS_TABLES>(a0, smem, path_tab, zeta_tab);
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;       // n_streams % 64 == 0 (host-checked): whole waves
     if (tid >= a0.n_streams) return;
-    const uint64_t T = a0.n_streams;
     KArgs a = a0;
     TeamState ts;
-    ts.rng.s0 = a.rng[tid]; ts.rng.s1 = a.rng[T + tid]; ts.rng.s2 = a.rng[2 * T + tid]; ts.rng.s3 = a.rng[3 * T + tid];
+    uint32_t no_flips = 0;                                            // (the sort has no end flips)
+    load_rng(a, tid, ts.rng);
     const uint32_t lane = threadIdx.x & 63u;
-    load_pass(a, tid, ts);
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), n_waves = a0.n_streams >> 6;   // (scalar registers)
-    const uint32_t slots = pool_slots(n_waves), slot = wave % slots;
-    const uint64_t total = (uint64_t)a0.quota_base * a0.n_streams + a0.quota_rem;
-    const uint32_t cap = (uint32_t)(total / slots + (slot < total % slots ? 1u : 0u));   // < 2^31 (host-checked)
+    load_pass(a, tid, ts, no_flips);
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));   // (scalar registers)
     const uint32_t ref_chunk = 64u * a0.ref_chunk;                    // K1d's chunk of a wave of 64 live lanes
+    // pool_walk's loop written out — KEEP IN STEP with sgd_kernel_common.h pool_walk.  (Through the helper the LDS_TABLES build,
+    // the one a graph whose tables fit the LDS gets, spills 35 scalar registers to lanes instead of 29; the build without them
+    // 42 instead of 53.  Both then take 128 VGPRs instead of 127, and the same 12 B of scratch.)
+    const PoolShare ps = pool_share(a0, wave, a0.n_streams >> 6);
     uint32_t k = 0, claim = 0;
     a.it = its[0];
     uint32_t chunk = a.it._pad ? ref_chunk : a0.chunk;
-    if (lane == 0) claim = __hip_atomic_fetch_add(pool + slot * POOL_STRIDE, chunk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    send_claim(pool + ps.slot * POOL_STRIDE, chunk, claim);
     while (k < n_iters) {
         const uint32_t old = (uint32_t)__builtin_amdgcn_readfirstlane((int)claim);
-        if (old >= cap) {                                              // this iteration's pool is exhausted
+        if (old >= ps.cap) {                                           // this iteration's pool is exhausted
             if (++k == n_iters) break;
             a.it = its[k];                                             // wave-uniform: scalar loads
             chunk = a.it._pad ? ref_chunk : a0.chunk;                  // the first claim of an iteration is sized by its sampler
-            if (lane == 0) claim = __hip_atomic_fetch_add(pool + ((size_t)k * POOL_SLOTS + slot) * POOL_STRIDE, chunk,
-                                                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            send_claim(pool + ((size_t)k * POOL_SLOTS + ps.slot) * POOL_STRIDE, chunk, claim);
             continue;
         }
-        // the next claim travels while this chunk is worked on
-        if (lane == 0) claim = __hip_atomic_fetch_add(pool + ((size_t)k * POOL_SLOTS + slot) * POOL_STRIDE, chunk,
-                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t m = cap - old < chunk ? cap - old : chunk;
+        send_claim(pool + ((size_t)k * POOL_SLOTS + ps.slot) * POOL_STRIDE, chunk, claim);   // travels while this chunk is worked on
+        const uint32_t m = ps.cap - old < chunk ? ps.cap - old : chunk;
         if (__builtin_expect(a.it._pad != 0, 0)) {                                               // window: reference streams, K1d's equal shares
             // (the launch constants read afresh, as the team sampler does — sgd_kernel_common.h reload_kargs: held through the
             // trip machine as well, they spilled 49 scalar registers and 10 vector ones into scratch)
@@ -70,8 +69,8 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 4))) sgd1d_phased_fused_ke
     // (the exit addresses are derived afresh: kept from the entry's loads they were spilled to scratch for the whole launch)
     uint32_t te = tid;
     asm volatile("" : "+v"(te));
-    a.rng[te] = ts.rng.s0; a.rng[T + te] = ts.rng.s1; a.rng[2 * T + te] = ts.rng.s2; a.rng[3 * T + te] = ts.rng.s3;
-    store_pass(a, te, ts);
+    store_rng(a, te, ts.rng);
+    store_pass(a, te, ts, 0u);
     flush_counters(a, ts.done, ts.att);
 }
 

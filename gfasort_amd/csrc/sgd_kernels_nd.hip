@@ -63,6 +63,7 @@ __device__ __forceinline__ void ref_run_nd(const KArgs &a, const uint4 *path_tab
         double *ci = coord_ptr<D>(a, cur.ni, oa), *cj = coord_ptr<D>(a, cur.nj, ob);
         const uint64_t cs = coord_step(a);
         const double mu = crowd_scale(fmin(a.it.eta * (1.0 / cur.term_dist), 1.0), cur.crowd);   // :1085-1086
+        // (the step written out, not layout_step: through the helper the trace kernel at D = 8 spills a register)
         double deltas[D];
         double mag_sq = 0.0;
 #pragma unroll
@@ -84,13 +85,7 @@ __device__ __forceinline__ void ref_run_nd(const KArgs &a, const uint4 *path_tab
             add_pos(cj + k * cs, r_d);
         }
         ++d;                                                                           // :1151
-        if (TRACE) {
-            if (ntr < a.trace_per_stream) {
-                TraceTerm *tt = reinterpret_cast<TraceTerm *>(a.trace) + (size_t)tid * a.trace_per_stream + ntr;
-                tt->i = (uint32_t)idx_i; tt->j = (uint32_t)idx_j; tt->d = cur.term_dist;
-                ++ntr;
-            }
-        }
+        if (TRACE) record_trace(a, tid, ntr, (uint32_t)idx_i, (uint32_t)idx_j, cur.term_dist);
     }
     done += d;
     att += t > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)t;
@@ -107,21 +102,20 @@ __global__ void sgdnd_kernel(const KArgs a) {
     uint32_t done = 0, att = 0;
     if (live) {
         Rng rng;
-        const uint64_t T = a.n_streams;
-        rng.s0 = a.rng[tid]; rng.s1 = a.rng[T + tid]; rng.s2 = a.rng[2 * T + tid]; rng.s3 = a.rng[3 * T + tid];
+        load_rng(a, tid, rng);
         const uint32_t quota = a.quota_base + (tid < a.quota_rem ? 1u : 0u);
         const uint64_t max_att64 = (uint64_t)a.attempt_factor * quota + 1024u;
         const uint64_t max_att = max_att64 > 0xFFFFFFFFull ? 0xFFFFFFFFull : max_att64;
         uint32_t ntr = TRACE ? a.trace_cnt[tid] : 0;
         ref_run_nd<D, LDS_TABLES, ATOMIC_LOADS, TRACE>(a, path_tab, zeta_tab, rng, quota, max_att, tid, done, att, ntr);
-        a.rng[tid] = rng.s0; a.rng[T + tid] = rng.s1; a.rng[2 * T + tid] = rng.s2; a.rng[3 * T + tid] = rng.s3;
+        store_rng(a, tid, rng);
         if (TRACE) a.trace_cnt[tid] = ntr;
     }
     flush_counters(a, done, att);
 }
 
 // K2d: the same streams, a range of iterations in one persistent launch with work pools (sgd_kernel_common.h
-// ref_pooled_walk; K1d in sgd_kernels_1d.hip is the 1D form).
+// ref_pooled_walk, pool_walk; K1d in sgd_kernels_1d.hip is the 1D form).
 template <int D, bool LDS_TABLES>
 __global__ void sgdnd_fused_kernel(const KArgs a0, const IterConsts *its, const uint32_t n_iters, uint32_t *pool) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -130,15 +124,14 @@ __global__ void sgdnd_fused_kernel(const KArgs a0, const IterConsts *its, const 
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
     if ((tid & ~63u) >= a0.n_streams) return;                          // waves without a live lane
     const bool live = tid < a0.n_streams;
-    const uint64_t T = a0.n_streams;
     KArgs a = a0;
     Rng rng = {0, 0, 0, 0};
-    if (live) { rng.s0 = a.rng[tid]; rng.s1 = a.rng[T + tid]; rng.s2 = a.rng[2 * T + tid]; rng.s3 = a.rng[3 * T + tid]; }
+    if (live) load_rng(a, tid, rng);
     uint32_t done = 0, att = 0, ntr = 0;
     ref_pooled_walk(a, its, n_iters, pool, tid, [&](const uint32_t share, const uint64_t max_att) {
         ref_run_nd<D, LDS_TABLES, true, false>(a, path_tab, zeta_tab, rng, share, max_att, tid, done, att, ntr);
     });
-    if (live) { a.rng[tid] = rng.s0; a.rng[T + tid] = rng.s1; a.rng[2 * T + tid] = rng.s2; a.rng[3 * T + tid] = rng.s3; }
+    if (live) store_rng(a, tid, rng);
     flush_counters(a, done, att);
 }
 

@@ -190,12 +190,7 @@ __device__ __forceinline__ bool fused_trip_nd(const KArgs &a, const TripND &cur,
 #pragma unroll
     for (uint32_t colour = 0; colour < 2u; ++colour) {
         ++att;
-        bool valid = term_ok && grp == colour;
-        const unsigned long long vmask = __ballot(valid);
-        const uint64_t remaining = wave_quota - wave_done;
-        const uint32_t nvalid = (uint32_t)__popcll(vmask);
-        if (valid && nvalid > remaining) valid = (uint32_t)__popcll(vmask & ((1ull << lane) - 1ull)) < remaining;
-        wave_done += nvalid < remaining ? nvalid : remaining;
+        const bool valid = quota_cut(term_ok && grp == colour, lane, wave_quota, wave_done);
         // my partner's CURRENT b-end coordinates (each shuffle a statement of its own, see fused_trip)
         double cj[D];
 #pragma unroll
@@ -208,6 +203,7 @@ __device__ __forceinline__ bool fused_trip_nd(const KArgs &a, const TripND &cur,
         for (int d = 0; d < D; ++d) r_d[d] = 0.0;
         if (valid) {
             double mu = crowd_scale(fmin(a.it.eta * (1.0 / term_dist), 1.0), crowd);  // :1085-1086
+            // (the step written out, not layout_step: through the helper K2b at D = 4, B = 64 spills two more scalar registers)
             double deltas[D], mag_sq = 0.0;
 #pragma unroll
             for (int d = 0; d < D; ++d) { deltas[d] = ca[d] - cj[d]; mag_sq += deltas[d] * deltas[d]; }   // :1108-1113
@@ -218,13 +214,7 @@ __device__ __forceinline__ bool fused_trip_nd(const KArgs &a, const TripND &cur,
 #pragma unroll
             for (int d = 0; d < D; ++d) r_d[d] = r * deltas[d];
             ++done;                                                            // :1151
-            if (TRACE) {
-                if (ntr < a.trace_per_stream) {
-                    TraceTerm *tt = reinterpret_cast<TraceTerm *>(a.trace) + (size_t)tid * a.trace_per_stream + ntr;
-                    tt->i = (uint32_t)idx_i; tt->j = (uint32_t)idx_j; tt->d = term_dist;
-                    ++ntr;
-                }
-            }
+            if (TRACE) record_trace(a, tid, ntr, (uint32_t)idx_i, (uint32_t)idx_j, term_dist);
         }
         // the +r of the lane whose partner I am
         double rv[D];
@@ -317,21 +307,14 @@ __device__ __forceinline__ bool twin_trip_nd(const KArgs &a, const TripND &cur, 
         if (!second) continue;                                                         // (wave-uniform)
         ++att;
         const double term_dist = fabs(pos_a - pos_p[p]);                               // :1080
-        bool valid = term_dist != 0.0 && node != 0xFFFFFFFFu && node_p[p] != 0xFFFFFFFFu;   // :1081, :1089-1096
-        const unsigned long long vmask = __ballot(valid);
-        const uint64_t remaining = wave_quota - wave_done;
-        const uint32_t nvalid = (uint32_t)__popcll(vmask);
-        if (valid && nvalid > remaining) valid = (uint32_t)__popcll(vmask & ((1ull << lane) - 1ull)) < remaining;
-        wave_done += nvalid < remaining ? nvalid : remaining;
+        const bool valid = quota_cut(term_dist != 0.0 && node != 0xFFFFFFFFu && node_p[p] != 0xFFFFFFFFu,   // :1081, :1089-1096
+                                     lane, wave_quota, wave_done);
         if (valid) {
             const double mu = crowd_scale(fmin(a.it.eta * (1.0 / term_dist), 1.0), crowd_shift<true>(a, cur.ra, p ? cur.rc : cur.rb));   // :1085-1086
-            double deltas[D], mag_sq = 0.0;
+            double deltas[D];
 #pragma unroll
-            for (int d = 0; d < D; ++d) { deltas[d] = ca[d] - cp[p][d]; mag_sq += deltas[d] * deltas[d]; }   // :1108-1113
-            if (mag_sq == 0.0) { deltas[0] = 1e-9; mag_sq = 1e-18; }                   // :1116-1119
-            const double mag = sqrt(mag_sq);                                           // :1121
-            const double delta = mu * (mag - term_dist) / 2.0;                         // :1125
-            const double r = delta / mag;                                              // :1142
+            for (int d = 0; d < D; ++d) deltas[d] = ca[d] - cp[p][d];                  // :1108-1113
+            const double r = layout_step<D>(deltas, mu, term_dist);                    // :1116-1142
             const bool same = idx_a == idx_p[p];
 #pragma unroll
             for (int d = 0; d < D; ++d) {
@@ -341,13 +324,7 @@ __device__ __forceinline__ bool twin_trip_nd(const KArgs &a, const TripND &cur, 
             if (!same) touched = true;
             fadd[p] = 1;                                                               // :1147-1148
             ++done;                                                                    // :1151
-            if (TRACE) {
-                if (ntr < a.trace_per_stream) {
-                    TraceTerm *tt = reinterpret_cast<TraceTerm *>(a.trace) + (size_t)tid * a.trace_per_stream + ntr;
-                    tt->i = (uint32_t)idx_a; tt->j = (uint32_t)idx_p[p]; tt->d = term_dist;
-                    ++ntr;
-                }
-            }
+            if (TRACE) record_trace(a, tid, ntr, (uint32_t)idx_a, (uint32_t)idx_p[p], term_dist);
         }
         if (p == 0 && wave_done >= wave_quota) second = false;
     }
@@ -486,14 +463,7 @@ __device__ __forceinline__ void nd_team_iteration(const KArgs &a, const uint4 *p
                 idx_i = (uint64_t)ra.x * 2u + (oa ? 1u : 0u);                          // :1099-1103
                 idx_j = (uint64_t)rb.x * 2u + (ob ? 1u : 0u);
             }
-            const unsigned long long vmask = __ballot(valid);
-            const uint64_t remaining = wave_quota - wave_done;
-            const uint32_t nvalid = (uint32_t)__popcll(vmask);
-            if (valid && nvalid > remaining) {
-                const uint32_t rank = (uint32_t)__popcll(vmask & ((1ull << lane) - 1ull));
-                valid = rank < remaining;
-            }
-            wave_done += nvalid < remaining ? nvalid : remaining;
+            valid = quota_cut(valid, lane, wave_quota, wave_done);
             double upd_r[D]; double *upd_ci = a.x, *upd_cj = a.x; bool upd_i = false, upd_j = false;
 #pragma unroll
             for (int d = 0; d < D; ++d) upd_r[d] = 0.0;
@@ -501,16 +471,9 @@ __device__ __forceinline__ void nd_team_iteration(const KArgs &a, const uint4 *p
                 double mu = crowd_scale(fmin(a.it.eta * (1.0 / term_dist), 1.0), crowd_shift<true>(a, ra, rb));                   // :1085-1086
                 double *ci = coord_ptr<D>(a, ra.x, oa), *cj = coord_ptr<D>(a, rb.x, ob);
                 double deltas[D];
-                double mag_sq = 0.0;
 #pragma unroll
-                for (int d = 0; d < D; ++d) {                                          // :1108-1113
-                    deltas[d] = load_pos<ATOMIC_LOADS>(ci + d * cs) - load_pos<ATOMIC_LOADS>(cj + d * cs);
-                    mag_sq += deltas[d] * deltas[d];
-                }
-                if (mag_sq == 0.0) { deltas[0] = 1e-9; mag_sq = 1e-18; }               // :1116-1119
-                double mag = sqrt(mag_sq);                                             // :1121
-                double delta = mu * (mag - term_dist) / 2.0;                           // :1125
-                double r = delta / mag;                                                // :1142
+                for (int d = 0; d < D; ++d) deltas[d] = load_pos<ATOMIC_LOADS>(ci + d * cs) - load_pos<ATOMIC_LOADS>(cj + d * cs);   // :1108-1113
+                const double r = layout_step<D>(deltas, mu, term_dist);                // :1116-1142
                 const bool same = idx_i == idx_j;
                 if (D < 2) {
 #pragma unroll
@@ -525,13 +488,7 @@ __device__ __forceinline__ void nd_team_iteration(const KArgs &a, const uint4 *p
                     upd_ci = ci; upd_cj = cj; upd_i = !same; upd_j = true;
                 }
                 ++ts.done;                                                                // :1151
-                if (TRACE) {
-                    if (ts.ntr < a.trace_per_stream) {
-                        TraceTerm *tt = reinterpret_cast<TraceTerm *>(a.trace) + (size_t)tid * a.trace_per_stream + ts.ntr;
-                        tt->i = (uint32_t)idx_i; tt->j = (uint32_t)idx_j; tt->d = term_dist;
-                        ++ts.ntr;
-                    }
-                }
+                if (TRACE) record_trace(a, tid, ts.ntr, (uint32_t)idx_i, (uint32_t)idx_j, term_dist);
             }
             if (D >= 2) {
                 // the two adds of this lane: A = -r to end i, B = +r to end j (:1143-1149)
@@ -569,29 +526,6 @@ __device__ __forceinline__ void nd_team_iteration(const KArgs &a, const uint4 *p
     }
 }
 
-// lead word (KArgs.lead[5]): as K1b's (sgd_kernels_1d.hip load_pass), with the pass's end flips in bits 5..7
-__device__ __forceinline__ void load_pass_nd(const KArgs &a, uint32_t tid, NdTeamState &ts) {
-    if (!a.lead) return;
-    const uint64_t T = a.n_streams;
-    ts.L.first_lo = a.lead[tid]; ts.L.first_hi = a.lead[T + tid]; ts.L.cnt = a.lead[2 * T + tid];
-    ts.L.ra0 = a.lead[3 * T + tid]; ts.L.rb0 = a.lead[4 * T + tid];
-    const uint32_t w = a.lead[5 * T + tid];
-    ts.L.ra1 = a.lead[6 * T + tid]; ts.L.rb1 = a.lead[7 * T + tid];
-    ts.L.ok = (w & 0x1Fu) | ((w >> 27) << 8);
-    ts.lflips = (w >> 5) & 7u;
-    const uint32_t ws = (uint32_t)__builtin_amdgcn_readfirstlane((int)w);      // the place in the pass: the same for the whole wave
-    ts.left = (ws >> 8) & 0xFFu; ts.cool = (ws >> 16) & 1u; ts.colour = (ws >> 17) & 1u; ts.seg = (ws >> 18) & 0xFFu; ts.p = (ws >> 26) & 1u;
-}
-__device__ __forceinline__ void store_pass_nd(const KArgs &a, uint32_t tid, const NdTeamState &ts) {
-    if (!a.lead) return;
-    const uint64_t T = a.n_streams;
-    a.lead[tid] = ts.L.first_lo; a.lead[T + tid] = ts.L.first_hi; a.lead[2 * T + tid] = ts.L.cnt;
-    a.lead[3 * T + tid] = ts.L.ra0; a.lead[4 * T + tid] = ts.L.rb0;
-    a.lead[5 * T + tid] = (ts.L.ok & 0x1Fu) | ((ts.lflips & 7u) << 5) | (ts.left << 8) | (ts.cool << 16) | (ts.colour << 17) | (ts.seg << 18) |
-                          (ts.p << 26) | (((ts.L.ok >> 8) & 0x1Fu) << 27);
-    a.lead[6 * T + tid] = ts.L.ra1; a.lead[7 * T + tid] = ts.L.rb1;
-}
-
 // K2b: one launch = one iteration, a fixed quota per wave worked through in chunks (like a pool of its own: one wave is bit for
 // bit the oracle's mirror here and in K2c).
 template <int D, int B, bool LDS_TABLES, bool ATOMIC_LOADS, bool TRACE>
@@ -601,29 +535,24 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(nd_wav
     stage_tables<LDS_TABLES>(a, smem, path_tab, zeta_tab);
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
     if (tid >= a.n_streams) return;
-    const uint64_t T = a.n_streams;
     NdTeamState ts;
-    ts.rng.s0 = a.rng[tid]; ts.rng.s1 = a.rng[T + tid]; ts.rng.s2 = a.rng[2 * T + tid]; ts.rng.s3 = a.rng[3 * T + tid];
+    load_rng(a, tid, ts.rng);
     ts.ntr = TRACE ? a.trace_cnt[tid] : 0;
-    load_pass_nd(a, tid, ts);
-    // (readfirstlane: the wave's quota, and with it every loop variable of the trip machine, is then wave-uniform for the
-    // compiler too — scalar registers and scalar arithmetic instead of 64 copies, as in K1c)
-    const uint32_t wave_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid & ~63u));
-    uint64_t wq = (uint64_t)a.quota_base * 64u;
-    if (wave_first < a.quota_rem) wq += (a.quota_rem - wave_first) < 64u ? (a.quota_rem - wave_first) : 64u;
+    load_pass(a, tid, ts, ts.lflips);
+    const uint64_t wq = wave_quota_of(a, (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid & ~63u)));
     for (uint64_t done = 0; done < wq; done += a.chunk)
         nd_team_iteration<D, B, LDS_TABLES, ATOMIC_LOADS, TRACE>(a, path_tab, zeta_tab, ts, tid, wq - done < a.chunk ? wq - done : a.chunk);
     // (the stream's addresses are computed again here rather than kept in registers since the loads at the top: built for three
     // waves per SIMD the kernel would otherwise spill exactly those registers, and a kernel with scratch pays for its set-up)
     uint32_t tid_out = tid;
     asm volatile("" : "+v"(tid_out));
-    a.rng[tid_out] = ts.rng.s0; a.rng[T + tid_out] = ts.rng.s1; a.rng[2 * T + tid_out] = ts.rng.s2; a.rng[3 * T + tid_out] = ts.rng.s3;
+    store_rng(a, tid_out, ts.rng);
     if (TRACE) a.trace_cnt[tid] = ts.ntr;
-    store_pass_nd(a, tid_out, ts);
+    store_pass(a, tid_out, ts, ts.lflips);
     flush_counters(a, ts.done, ts.att);
 }
 
-// K2c: the same, FUSED over a range of iterations with WORK POOLS — K1c (sgd_kernels_1d.hip, which has the reasons) for layouts.
+// K2c: the same, FUSED over a range of iterations with WORK POOLS (sgd_kernel_common.h pool_walk, which has the reasons) — K1c for layouts.
 // Fixed quotas leave a layout launch's waves finishing up to a fifth of the launch apart (a wave's trips cost by what its few
 // leaders happen to be; profiles/r03/nd_k_probe.log: the longer the runs, the fewer leaders per wave and the slower the launch);
 // drawn from a pool, an iteration ends for all waves within a chunk of each other, and the next one starts without a launch.
@@ -636,12 +565,10 @@ sgdnd_team_fused_kernel(const KArgs a0, const IterConsts *its, const uint32_t n_
     stage_tables<LDS_TABLES>(a0, smem, path_tab, zeta_tab);
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
     if (tid >= a0.n_streams) return;
-    const uint64_t T = a0.n_streams;
     KArgs a = a0;
     NdTeamState ts;
-    ts.rng.s0 = a.rng[tid]; ts.rng.s1 = a.rng[T + tid]; ts.rng.s2 = a.rng[2 * T + tid]; ts.rng.s3 = a.rng[3 * T + tid];
-    const int lane = threadIdx.x & 63;
-    load_pass_nd(a, tid, ts);
+    load_rng(a, tid, ts.rng);
+    load_pass(a, tid, ts, ts.lflips);
     if (POOL) {
         // ONE counter per iteration for layouts.  K1c spreads an iteration over up to 16 counters so that the claims do not queue on
         // one address; each is a fixed share of the iteration, so the waves of a fast counter run ahead of the others' — without
@@ -649,30 +576,26 @@ sgdnd_team_fused_kernel(const KArgs a0, const IterConsts *its, const uint32_t n_
         // ends - its length| was 1.6 bp with 16 counters, 1.15 with one, 1.09 with a launch per iteration and 2.4 with free-running
         // waves (reference streams 0.92; profiles/r03/tiled_layout_e2e_probe.log, nd_pool_slots_probe.log).  A layout chunk is
         // 16 heavy trips, so one counter takes ~2e7 claims/s at most: 49.5 against 50.3 G updates/s on C4.
-        constexpr uint32_t slot = 0u;
-        const uint32_t cap = (uint32_t)((uint64_t)a0.quota_base * a0.n_streams + a0.quota_rem);   // the iteration's updates, < 2^31 (host-checked)
+        // pool_walk's loop written out — KEEP IN STEP with sgd_kernel_common.h pool_walk.  (Through the helper the kernel at D = 2,
+        // built for 168 registers, spills 8 of them into 12 B of scratch.)
+        const PoolShare ps = pool_share_single(a0);
         uint32_t k = 0, claim = 0;
         a.it = its[0];
-        if (lane == 0) claim = __hip_atomic_fetch_add(pool + slot * POOL_STRIDE, a0.chunk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        send_claim(pool + ps.slot * POOL_STRIDE, a0.chunk, claim);
         while (k < n_iters) {
             const uint32_t old = (uint32_t)__builtin_amdgcn_readfirstlane((int)claim);
-            if (old >= cap) {                                          // this iteration's pool is exhausted
+            if (old >= ps.cap) {                                       // this iteration's pool is exhausted
                 if (++k == n_iters) break;
                 a.it = its[k];                                         // wave-uniform: scalar loads
-                if (lane == 0) claim = __hip_atomic_fetch_add(pool + ((size_t)k * POOL_SLOTS + slot) * POOL_STRIDE, a0.chunk,
-                                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                send_claim(pool + ((size_t)k * POOL_SLOTS + ps.slot) * POOL_STRIDE, a0.chunk, claim);
                 continue;
             }
-            // the next claim travels while this chunk is worked on
-            if (lane == 0) claim = __hip_atomic_fetch_add(pool + ((size_t)k * POOL_SLOTS + slot) * POOL_STRIDE, a0.chunk,
-                                                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            nd_team_iteration<D, B, LDS_TABLES, ATOMIC_LOADS, false>(a, path_tab, zeta_tab, ts, tid, cap - old < a0.chunk ? cap - old : a0.chunk, its + k);
+            send_claim(pool + ((size_t)k * POOL_SLOTS + ps.slot) * POOL_STRIDE, a0.chunk, claim);   // travels while this chunk is worked on
+            nd_team_iteration<D, B, LDS_TABLES, ATOMIC_LOADS, false>(a, path_tab, zeta_tab, ts, tid, ps.cap - old < a0.chunk ? ps.cap - old : a0.chunk, its + k);
         }
     } else {
         // fixed quota per wave and iteration, free-running (GFS_F_DBG_FREE_RUNNING)
-        const uint32_t wave_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid & ~63u));
-        uint64_t wq = (uint64_t)a.quota_base * 64u;
-        if (wave_first < a.quota_rem) wq += (a.quota_rem - wave_first) < 64u ? (a.quota_rem - wave_first) : 64u;
+        const uint64_t wq = wave_quota_of(a, (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid & ~63u)));
         for (uint32_t k = 0; k < n_iters; ++k) {
             a.it = its[k];
             for (uint64_t done = 0; done < wq; done += a.chunk)
@@ -681,8 +604,8 @@ sgdnd_team_fused_kernel(const KArgs a0, const IterConsts *its, const uint32_t n_
     }
     uint32_t tid_out = tid;
     asm volatile("" : "+v"(tid_out));
-    a.rng[tid_out] = ts.rng.s0; a.rng[T + tid_out] = ts.rng.s1; a.rng[2 * T + tid_out] = ts.rng.s2; a.rng[3 * T + tid_out] = ts.rng.s3;
-    store_pass_nd(a, tid_out, ts);
+    store_rng(a, tid_out, ts.rng);
+    store_pass(a, tid_out, ts, ts.lflips);
     flush_counters(a, ts.done, ts.att);
 }
 
