@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libgfasort_hip.so")
-SOURCES = ["sgd_kernels_1d.hip", "sgd_kernels_1d_phased.hip", "sgd_kernels_nd.hip", "sgd_kernels_nd_team.hip", "sgd_kernels_nd_team_wide.hip", "index_kernels.hip",
+SOURCES = ["sgd_kernels_1d.hip", "sgd_kernels_1d_phased.hip", "sgd_kernels_nd.hip", "sgd_kernels_nd_team.hip", "sgd_kernels_nd_team_wide.hip", "index_kernels.hip", "quality_kernels.hip",
            "capi.hip", "multi.hip"]
 HEADERS = ["sgd_device.h", "sgd_kernel_common.h", "sgd_1d.h", "sgd_nd_team.h", "sgd_host.h", os.path.join("..", "..", "include", "gfasort_hip.h")]
 

@@ -94,6 +94,7 @@ int gfs_warmup(int device) {
     HIPCHK(gfs::warm_module_1d_phased());
     lap("module 1d");
     HIPCHK(gfs::warm_module_index());
+    HIPCHK(gfs::warm_module_quality());
     lap("module index");
     HIPCHK(gfs::warm_module_nd());
     HIPCHK(gfs::warm_module_nd_team());
@@ -222,6 +223,14 @@ struct Xo256p {                                                            // ra
         s[2] ^= s[0]; s[3] ^= s[1]; s[1] ^= s[2]; s[0] ^= s[3]; s[2] ^= t; s[3] = (s[3] << 45) | (s[3] >> 19);
         return r;
     }
+    uint64_t uniform_usize(uint64_t n) {                                       // rand 0.9 Uniform<usize>::new(0, n): the u32 sampler
+        if (n <= 0xFFFFFFFFull) {                                              // where n fits, widening multiply and rejection
+            const uint32_t range = (uint32_t)n, thresh = (uint32_t)(0u - range) % range;
+            for (;;) { const uint64_t m = (uint64_t)(uint32_t)(next() >> 32) * range; if ((uint32_t)m >= thresh) return m >> 32; }
+        }
+        const uint64_t thresh = (0ull - n) % n;
+        for (;;) { const unsigned __int128 m = (unsigned __int128)next() * n; if ((uint64_t)m >= thresh) return (uint64_t)(m >> 64); }
+    }
 };
 inline double float_with_exponent(uint64_t fraction52, int e) {
     const uint64_t b = fraction52 | ((uint64_t)(1023 + e) << 52);
@@ -344,6 +353,7 @@ struct gfs_ctx {
     // sampler at B = 64.  phased is false where the flag is a no-op (the auto policy picked another bundle).
     bool phased = false;
     uint64_t win_begin = 0, win_end = 0;
+    uint64_t *d_quality = nullptr; uint64_t quality_cap = 0;   // K7 read-outs: scratch in 8-byte words, kept between calls
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     size_t events_used = 0;
@@ -871,6 +881,7 @@ void gfs_ctx_destroy(gfs_ctx *c) {
     if (c->d_path_len) (void)hipFree(c->d_path_len);
     if (c->d_perm) (void)hipFree(c->d_perm);
     if (c->d_node_len) (void)hipFree(c->d_node_len);
+    if (c->d_quality) (void)hipFree(c->d_quality);
     delete c;
 }
 
@@ -1242,6 +1253,145 @@ int gfs_ctx_sort_order(gfs_ctx *c, uint64_t *order, uint64_t n) {
     return GFS_OK;
 }
 
+// ---- K7: quality read-outs of the resident positions (quality_kernels.hip) --------------------------------------------
+static int quality_scratch(gfs_ctx *c, uint64_t words) {
+    if (c->quality_cap >= words) return GFS_OK;
+    if (c->d_quality) HIPCHK(hipFree(c->d_quality));
+    c->d_quality = nullptr; c->quality_cap = 0;
+    HIPCHK(hipMalloc(&c->d_quality, words * 8));
+    c->quality_cap = words;
+    return GFS_OK;
+}
+static int check_step_distances(const uint64_t *zs, uint64_t n_z, const gfs_pair_error *out) {
+    if ((!zs || !out) && n_z) return fail(GFS_E_ARG, "null argument");
+    if (n_z > 65535) return fail(GFS_E_ARG, "at most 65535 step distances per call");
+    for (uint64_t k = 0; k < n_z; ++k) if (zs[k] == 0) return fail(GFS_E_ARG, "a step distance of 0");
+    return GFS_OK;
+}
+
+int gfs_ctx_pair_errors(gfs_ctx *c, const uint64_t *zs, uint64_t n_z, gfs_pair_error *out, void *hip_stream) {
+    if (!c) return fail(GFS_E_ARG, "ctx is null");
+    int rc = check_step_distances(zs, n_z, out);
+    if (rc) return rc;
+    if (!c->d_x) return fail(GFS_E_STATE, "the context has no positions (not set up)");
+    if (n_z == 0) return GFS_OK;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const uint64_t blocks = gfs::quality_blocks(c->n_steps);
+    // scratch: [zs | out words | partials]
+    rc = quality_scratch(c, n_z + 5 * n_z + 5 * n_z * blocks);
+    if (rc) return rc;
+    uint64_t *d_zs = c->d_quality, *d_out = d_zs + n_z, *d_partials = d_out + 5 * n_z;
+    HIPCHK(hipMemcpyAsync(d_zs, zs, n_z * 8, hipMemcpyHostToDevice, st));
+    const bool timing = std::getenv("GFS_TIMING") != nullptr;             // the kernels' duration on stderr (HIP events)
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (timing) { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventRecord(e0, st)); }
+    hipError_t e = gfs::pair_errors_device(c->d_step_rec, c->n_steps, c->d_x, c->n_nodes, (uint32_t)c->dims, d_zs, (uint32_t)n_z,
+                                           d_partials, d_out, st);
+    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("pair_errors_device: ") + hipGetErrorString(e));
+    if (timing) HIPCHK(hipEventRecord(e1, st));
+    std::vector<uint64_t> w(5 * n_z);
+    HIPCHK(hipMemcpyAsync(w.data(), d_out, w.size() * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (timing) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        std::fprintf(stderr, "[gfs_ctx_pair_errors] %llu step distances, %llu steps: kernels %.4f ms\n", (unsigned long long)n_z,
+                     (unsigned long long)c->n_steps, ms);
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    }
+    for (uint64_t k = 0; k < n_z; ++k) {
+        out[k].step_distance = zs[k]; out[k].pairs = w[5 * k];
+        std::memcpy(&out[k].sum_rel_sq, &w[5 * k + 1], 8); std::memcpy(&out[k].max_rel_sq, &w[5 * k + 2], 8);
+        std::memcpy(&out[k].sum_abs, &w[5 * k + 3], 8); std::memcpy(&out[k].sum_sq, &w[5 * k + 4], 8);
+    }
+    return GFS_OK;
+}
+
+// the step-drawing half of calculate_layout_stress (sgd.rs:1218-1250); host only
+int gfs_stress_sample_pairs(const gfs_graph_view *g, uint64_t sample_count, uint64_t seed, uint64_t *step_a, uint64_t *step_b,
+                            uint64_t *n_out) {
+    if (!g || !n_out || ((!step_a || !step_b) && sample_count)) return fail(GFS_E_ARG, "null argument");
+    *n_out = 0;
+    if (g->n_steps < 2) return GFS_OK;                                     // :1220
+    if (!g->path_first_step || g->n_paths == 0 || g->path_first_step[0] != 0 || g->path_first_step[g->n_paths] != g->n_steps)
+        return fail(GFS_E_ARG, "path_first_step must start at 0 and end at n_steps");
+    for (uint64_t p = 0; p < g->n_paths; ++p)
+        if (g->path_first_step[p + 1] < g->path_first_step[p]) return fail(GFS_E_ARG, "path_first_step not monotone");
+    Xo256p rng(seed);                                                      // :1218
+    uint64_t n = 0;
+    for (uint64_t k = 0; k < sample_count; ++k) {
+        const uint64_t a = rng.uniform_usize(g->n_steps);                  // :1230
+        // the path of step a: the last p with path_first_step[p] <= a (empty paths share a boundary)
+        const uint64_t p = (uint64_t)(std::upper_bound(g->path_first_step, g->path_first_step + g->n_paths, a) - g->path_first_step) - 1;
+        const uint64_t first = g->path_first_step[p], cnt = g->path_first_step[p + 1] - first;
+        if (cnt < 2) continue;                                             // :1234
+        const uint64_t rank_a = a - first, rank_b = rng.uniform_usize(cnt);   // :1238-1240
+        if (rank_a == rank_b) continue;                                    // :1242
+        step_a[n] = first + rank_a; step_b[n] = first + rank_b;
+        ++n;
+    }
+    *n_out = n;
+    return GFS_OK;
+}
+
+int gfs_ctx_stress_of_pairs(gfs_ctx *c, const uint64_t *step_a, const uint64_t *step_b, uint64_t n, double *rel_sq_out,
+                            uint64_t *counted, double *stress) {
+    if (!c || !counted || !stress || ((!step_a || !step_b) && n)) return fail(GFS_E_ARG, "null argument");
+    *counted = 0; *stress = 0.0;
+    for (uint64_t i = 0; i < n; ++i)
+        if (step_a[i] >= c->n_steps || step_b[i] >= c->n_steps) return fail(GFS_E_ARG, "a step index beyond n_steps");
+    if (!c->d_x) return fail(GFS_E_STATE, "the context has no positions (not set up)");
+    if (n == 0) return GFS_OK;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipDeviceSynchronize());
+    int rc = quality_scratch(c, 3 * n);                                    // [step_a | step_b | rel_sq]
+    if (rc) return rc;
+    uint64_t *d_a = c->d_quality, *d_b = d_a + n;
+    double *d_rel = reinterpret_cast<double *>(d_b + n);
+    HIPCHK(hipMemcpy(d_a, step_a, n * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_b, step_b, n * 8, hipMemcpyHostToDevice));
+    hipError_t e = gfs::pair_list_device(c->d_step_rec, c->n_steps, c->d_x, c->n_nodes, (uint32_t)c->dims, d_a, d_b, n, d_rel, nullptr);
+    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("pair_list_device: ") + hipGetErrorString(e));
+    std::vector<double> own;
+    double *rel = rel_sq_out;
+    if (!rel) { own.resize(n); rel = own.data(); }
+    HIPCHK(hipMemcpy(rel, d_rel, n * 8, hipMemcpyDeviceToHost));
+    double sum = 0.0; uint64_t cnt = 0;                                    // in sample order: sgd.rs:1274-1275
+    for (uint64_t i = 0; i < n; ++i) if (rel[i] >= 0.0) { sum += rel[i]; ++cnt; }
+    *counted = cnt;
+    *stress = cnt ? std::sqrt(sum / (double)cnt) : 0.0;                    // :1278-1282
+    return GFS_OK;
+}
+
+int gfs_ctx_sort_quality(gfs_ctx *c, gfs_sort_quality *out) {
+    if (!c || !out) return fail(GFS_E_ARG, "null argument");
+    std::memset(out, 0, sizeof *out);
+    if (!c->d_x || c->dims != 0) return fail(GFS_E_STATE, "needs a 1D context that has been set up");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipDeviceSynchronize());
+    const uint64_t n = c->n_nodes, blocks = gfs::quality_blocks(c->n_steps);
+    void *d_sort = nullptr;
+    HIPCHK(hipMalloc(&d_sort, n * (2 * 8 + 2 * 4)));
+    uint32_t *d_order = nullptr;
+    hipError_t e = gfs::sort_order_device(c->d_x, c->d_perm, n, 1, d_sort, &d_order);
+    int rc = e == hipSuccess ? quality_scratch(c, (n + 1) + n + 5 * blocks + 5)      // [prefix | sorted positions | partials | out]
+                             : fail(GFS_E_HIP, std::string("sort_order_device: ") + hipGetErrorString(e));
+    if (rc) { (void)hipFree(d_sort); return rc; }
+    uint64_t *d_prefix = c->d_quality, *d_spos = d_prefix + n + 1, *d_partials = d_spos + n, *d_out = d_partials + 5 * blocks;
+    uint64_t total_len = 0;
+    e = gfs::sort_quality_device(c->d_step_rec, c->n_steps, d_order, c->d_node_len, c->d_perm, n, d_prefix, d_spos, d_partials, d_out,
+                                 &total_len, nullptr);
+    (void)hipFree(d_sort);
+    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("sort_quality_device: ") + hipGetErrorString(e));
+    if (total_len >= (1ull << 53)) return fail(GFS_E_UNSUPPORTED, "a graph of 2^53 bp or more");
+    uint64_t w[5];
+    HIPCHK(hipMemcpy(w, d_out, sizeof w, hipMemcpyDeviceToHost));
+    out->steps = w[0]; out->abs_err_sum = w[1]; out->genomic_sum = w[2];
+    std::memcpy(&out->sq_err_sum, &w[3], 8);
+    return GFS_OK;
+}
+
 // ---- multi-GPU replica merge helpers (device pointers, asynchronous on hip_stream) -----------------
 int gfs_merge_prepare(const double *x, const double *x_prev, float *buf2n, uint64_t n, void *hip_stream) {
     if (!x || !x_prev || !buf2n) return fail(GFS_E_ARG, "null argument");
@@ -1294,6 +1444,30 @@ static int one_shot(const gfs_graph_view *g, const gfs_sgd_params *p, int dims, 
     }
     gfs_ctx_destroy(c);
     lap("destroy");
+    return rc;
+}
+
+// A finished result measured without a run: a context that holds positions and nothing else (no schedule, no streams).
+int gfs_pair_errors(const gfs_graph_view *g, uint64_t dims, const double *positions, const uint64_t *zs, uint64_t n_z,
+                    gfs_pair_error *out) {
+    if (!g) return fail(GFS_E_ARG, "null argument");
+    int rc = check_step_distances(zs, n_z, out);
+    if (rc) return rc;
+    if (dims > GFS_MAX_DIMS) return fail(GFS_E_ARG, "dims must be 0 (1D positions) or 1..8");
+    for (uint64_t k = 0; k < n_z; ++k) { out[k] = gfs_pair_error{}; out[k].step_distance = zs[k]; }
+    if (g->n_nodes == 0) return GFS_NOTHING_TO_DO;
+    if (!positions) return fail(GFS_E_ARG, "positions buffer is null");
+    gfs_ctx *c = nullptr;
+    rc = gfs_ctx_create(g, 0, &c);
+    if (rc) return rc;
+    c->dims = (int)dims;
+    c->x_len = dims ? c->n_nodes * 2 * dims : c->n_nodes;
+    hipError_t e = hipMalloc(&c->d_x, c->x_len * 8);
+    if (e != hipSuccess) { gfs_ctx_destroy(c); return fail(GFS_E_HIP, std::string("hipMalloc positions: ") + hipGetErrorString(e)); }
+    c->x_owned = true;
+    rc = gfs_ctx_upload_positions(c, positions, c->x_len);
+    if (!rc) rc = gfs_ctx_pair_errors(c, zs, n_z, out, nullptr);
+    gfs_ctx_destroy(c);
     return rc;
 }
 

@@ -3,6 +3,7 @@
 // engine.  The other pipeline characters (g, s, S, u) belong to subsystems that are out of
 // scope for this build: they are rejected with a clear message.
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -10,6 +11,7 @@
 #include <sstream>
 #include <string>
 #include <thread>
+#include <vector>
 
 #include "sgd.hpp"
 
@@ -22,6 +24,7 @@ struct Args {
     uint64_t streams = 0; uint32_t flags = 0;      // HIP launch shape (extra, not in the reference)
     unsigned bundle = 0;                           // 0 = auto, 1 = reference streams, 4..64
     bool reference_sampler = false, phased = false;
+    bool stress_profile = false;                   // after a Y or an L step: the exhaustive error per step distance
 };
 
 static void usage() {
@@ -40,6 +43,10 @@ static void usage() {
         "                                       reaches the reference's quality at the default --iter-max in ~half the time\n"
         "                                       of --reference-sampler.  Not with --reference-sampler or a --bundle other than\n"
         "                                       auto or 64; -p L is not affected.  -v 2 prints the window)\n"
+        "                   [--stress-profile]   (after every Y or L step, on stderr: the error of ALL pairs of path steps z apart,\n"
+        "                                       one line per step distance z = 1, 2, 3, 4, 6, 8, 12, ... — exhaustive, computed on\n"
+        "                                       the device from the step's final positions; the sampled `layout stress` of -v is\n"
+        "                                       dominated by the few short-range pairs it happens to hit)\n"
         "Pipeline characters: Y = path-guided SGD sort, L = nD layout (HIP engine).\n"
         "g, s, S, u exist in the reference but are not part of this build.\n";
 }
@@ -63,6 +70,7 @@ static bool parse_args(int argc, char **argv, Args &a) {
         else if (f == "--bundle") { if (!(v = need(i))) return false; a.bundle = std::string(v) == "auto" ? 0u : (unsigned)std::stoul(v); }
         else if (f == "--reference-sampler") { a.bundle = 1; a.reference_sampler = true; }
         else if (f == "--phased-sampler") { a.phased = true; }
+        else if (f == "--stress-profile") { a.stress_profile = true; }
         else if (f == "--hip-flags") { if (!(v = need(i))) return false; a.flags = (uint32_t)std::stoul(v); }
         else if (f == "-h" || f == "--help") { usage(); exit(0); }
         else { std::cerr << "error: unexpected argument '" << f << "'\n"; return false; }
@@ -92,6 +100,17 @@ static int validate_pipeline(const std::string &p) {                  // gfasort
     }
     if (p.empty()) { std::cerr << "Error: Pipeline cannot be empty\n"; return 1; }
     return 0;
+}
+
+static void print_stress_profile(const std::vector<gfs_pair_error> &rows) {
+    for (const gfs_pair_error &r : rows) {
+        const double n = (double)r.pairs;
+        char buf[320];
+        snprintf(buf, sizeof buf, "[gfasort] stress profile: z=%llu pairs=%llu rms_rel=%.17g max_rel=%.17g rmse_bp=%.17g mae_bp=%.17g\n",
+                 (unsigned long long)r.step_distance, (unsigned long long)r.pairs, r.pairs ? std::sqrt(r.sum_rel_sq / n) : 0.0,
+                 std::sqrt(r.max_rel_sq), r.pairs ? std::sqrt(r.sum_sq / n) : 0.0, r.pairs ? r.sum_abs / n : 0.0);
+        std::cerr << buf;
+    }
 }
 
 int main(int argc, char **argv) {
@@ -143,7 +162,12 @@ int main(int argc, char **argv) {
             if (c == 'Y') {
                 HipOptions opt_y = opt;
                 if (args.phased) opt_y.cfg.flags |= GFS_F_PHASED;
-                sgd_sort_only(graph, sgd_params, (uint8_t)args.verbose, opt_y, &st);        // gfasort.rs:250-252
+                // (the profile speaks the dense indices of the graph as it is before the sort reorders it)
+                FlatGraph before;
+                std::vector<double> x;
+                if (args.stress_profile) before = graph.flatten();
+                sgd_sort_only(graph, sgd_params, (uint8_t)args.verbose, opt_y, &st, args.stress_profile ? &x : nullptr);   // gfasort.rs:250-252
+                if (args.stress_profile && !x.empty()) print_stress_profile(layout_pair_errors(before, 0, x, step_distance_ladder(before)));
                 if (args.phased && args.verbose >= 2) {
                     uint64_t kb = 0, ke = sgd_params.iter_max + 1;         // reference streams picked: the whole schedule is theirs
                     if (st.bundle == 64) { gfs_sgd_params cp = sgd_params.to_c(); gfs_phase_window(&cp, &kb, &ke); }
@@ -157,6 +181,10 @@ int main(int argc, char **argv) {
                     double stress = calculate_layout_stress(graph, layout, 10000);
                     char buf[64]; snprintf(buf, sizeof buf, "%.6f", stress);
                     std::cerr << "[gfasort] layout stress: " << buf << "\n";
+                }
+                if (args.stress_profile && layout.num_nodes) {
+                    FlatGraph f = graph.flatten();
+                    print_stress_profile(layout_pair_errors(f, layout.dimensions, layout.coords, step_distance_ladder(f)));
                 }
             }
             if (args.verbose >= 1 && st.iterations)

@@ -199,7 +199,8 @@ struct Lap {                                                        // GFS_TIMIN
 }  // namespace
 
 std::vector<Handle> path_sgd_sort(const BidirectedGraph &g, const PathSGDParams &p, const HipOptions &opt,
-                                  gfs_stats *stats) {
+                                  gfs_stats *stats, std::vector<double> *positions_out) {
+    if (positions_out) positions_out->clear();
     // same result as sorting path_linear_sgd's map (sgd.rs:641-672); the sort runs on the device
     std::vector<Handle> out;
     if (g.node_count() == 0) return out;                             // sgd.rs:242-244
@@ -222,12 +223,14 @@ std::vector<Handle> path_sgd_sort(const BidirectedGraph &g, const PathSGDParams 
     out.reserve(order.size());
     for (uint64_t idx : order) out.push_back(Handle::forward(f.node_ids[idx]));   // idx -> handle, sgd.rs:649-662
     lap("handles");
+    if (positions_out) *positions_out = std::move(x);
     return out;
 }
 
-void sgd_sort_only(BidirectedGraph &g, const PathSGDParams &p, uint8_t verbose, const HipOptions &opt, gfs_stats *stats) {
+void sgd_sort_only(BidirectedGraph &g, const PathSGDParams &p, uint8_t verbose, const HipOptions &opt, gfs_stats *stats,
+                   std::vector<double> *positions_out) {
     if (verbose >= 2) std::cerr << "[path_sgd] Starting path-guided SGD\n";
-    auto ordering = path_sgd_sort(g, p, opt, stats);
+    auto ordering = path_sgd_sort(g, p, opt, stats, positions_out);
     Lap lap;
     g.apply_ordering(ordering);
     lap("apply_ordering");
@@ -323,6 +326,37 @@ double calculate_layout_stress(const BidirectedGraph &g, const Layout &layout, s
         ++count;
     }
     return count ? std::sqrt(sum / (double)count) : 0.0;
+}
+
+// ---- exhaustive per-step-distance errors on the device (gfs_pair_errors) ----------------------------------------------
+std::vector<gfs_pair_error> layout_pair_errors(const FlatGraph &f, size_t dims, const std::vector<double> &positions,
+                                               const std::vector<uint64_t> &zs) {
+    const size_t want = dims ? f.node_len.size() * 2 * dims : f.node_len.size();
+    if (positions.size() != want) throw std::runtime_error("layout_pair_errors: positions do not match the graph");
+    std::vector<gfs_pair_error> out(zs.size());
+    gfs_graph_view v = f.view();
+    check(gfs_pair_errors(&v, dims, positions.data(), zs.data(), zs.size(), out.data()));
+    return out;
+}
+
+std::vector<gfs_pair_error> layout_pair_errors(const BidirectedGraph &g, const Layout &layout, const std::vector<uint64_t> &zs) {
+    return layout_pair_errors(g.flatten(), layout.dimensions, layout.coords, zs);
+}
+
+std::vector<gfs_pair_error> layout_pair_errors(const BidirectedGraph &g, const std::vector<double> &positions,
+                                               const std::vector<uint64_t> &zs) {
+    return layout_pair_errors(g.flatten(), 0, positions, zs);
+}
+
+std::vector<uint64_t> step_distance_ladder(const FlatGraph &f) {
+    uint64_t longest = 0;
+    for (size_t p = 0; p + 1 < f.path_first_step.size(); ++p) longest = std::max(longest, f.path_first_step[p + 1] - f.path_first_step[p]);
+    std::vector<uint64_t> zs;
+    for (unsigned k = 0; k < 63 && (1ull << k) < longest; ++k) {
+        zs.push_back(1ull << k);
+        if (k >= 1 && (3ull << (k - 1)) < longest) zs.push_back(3ull << (k - 1));
+    }
+    return zs;
 }
 
 }  // namespace gfasort

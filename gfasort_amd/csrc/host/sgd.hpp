@@ -4,6 +4,7 @@
 //   path_linear_sgd      src/sgd.rs:237           path_sgd_sort    src/sgd.rs:641
 //   sgd_sort_only        src/ygs.rs:195           path_linear_sgd_layout  src/sgd.rs:773
 //   calculate_layout_stress  src/sgd.rs:1196
+//   layout_pair_errors   (no reference equivalent) the same per-pair error over ALL pairs at given step distances, on the device
 // Same names, argument meaning and empty-result behaviour as the Rust functions.
 #pragma once
 #include <cstdint>
@@ -88,11 +89,13 @@ std::unordered_map<size_t, double> path_linear_sgd(const BidirectedGraph &g, con
                                                    const HipOptions &opt = {}, gfs_stats *stats = nullptr);
 // sgd.rs:641 — handles in ascending position order (ties keep node_order; the reference's tie
 // order is HashMap-random).
+// positions_out (nullable): the final positions by dense index of g as it is BEFORE the ordering is applied; empty when
+// there was nothing to do.
 std::vector<Handle> path_sgd_sort(const BidirectedGraph &g, const PathSGDParams &p, const HipOptions &opt = {},
-                                  gfs_stats *stats = nullptr);
+                                  gfs_stats *stats = nullptr, std::vector<double> *positions_out = nullptr);
 // ygs.rs:195 — path_sgd_sort + apply_ordering.
 void sgd_sort_only(BidirectedGraph &g, const PathSGDParams &p, uint8_t verbose, const HipOptions &opt = {},
-                   gfs_stats *stats = nullptr);
+                   gfs_stats *stats = nullptr, std::vector<double> *positions_out = nullptr);
 // sgd.rs:773.  Gaussian start of dims >= 1 is drawn here (Box-Muller on SplitMix64(seed); the
 // reference's rand_distr ziggurat stream is not reproduced).
 Layout path_linear_sgd_layout(const BidirectedGraph &g, const LayoutSGDParams &p, const HipOptions &opt = {},
@@ -100,5 +103,16 @@ Layout path_linear_sgd_layout(const BidirectedGraph &g, const LayoutSGDParams &p
 std::vector<double> default_layout_init(const FlatGraph &f, size_t dims, uint64_t seed);
 // sgd.rs:1196 (host, seed 12345)
 double calculate_layout_stress(const BidirectedGraph &g, const Layout &layout, size_t sample_count);
+
+// The error of calculate_layout_stress' formula over ALL pairs of path steps (s, s + z), one entry per step distance z, computed
+// on the device (gfs_pair_errors): exhaustive and deterministic, no sample.  dims = 0: positions is x by dense index (a sort's
+// result); otherwise Layout.coords.  Throws std::runtime_error on a HIP / argument error.
+std::vector<gfs_pair_error> layout_pair_errors(const FlatGraph &f, size_t dims, const std::vector<double> &positions,
+                                               const std::vector<uint64_t> &zs);
+std::vector<gfs_pair_error> layout_pair_errors(const BidirectedGraph &g, const Layout &layout, const std::vector<uint64_t> &zs);
+std::vector<gfs_pair_error> layout_pair_errors(const BidirectedGraph &g, const std::vector<double> &positions,
+                                               const std::vector<uint64_t> &zs);
+// z = 1, 2, 3, 4, 6, 8, 12, 16, ...: every 2^k and 3 * 2^(k-1) below the longest path's step count
+std::vector<uint64_t> step_distance_ladder(const FlatGraph &f);
 
 }  // namespace gfasort

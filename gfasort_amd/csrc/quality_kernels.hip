@@ -1,0 +1,241 @@
+// quality_kernels.hip — K7: how good are the positions that are in HBM now, read out on the device.
+//   K7a  exhaustive pairs of path steps (s, s + z), for a list of step distances z: the relative error of
+//        calculate_layout_stress (src/sgd.rs:1252-1275, Layout::distance) over ALL such pairs
+//   K7b  the same per-pair value for a caller's list of step pairs (the device half of the sampled stress)
+//   K7c  measure_layout_quality.rs:100-208 for the context's current 1D positions: rank order (K6), node lengths in rank
+//        order, exclusive scan (rocPRIM), one pass over adjacent step pairs — all integers
+// The kernels read step records and positions and write only their own output buffers.
+//
+// Determinism: the grid is a function of n_steps alone (quality_blocks), never of the device.  A thread accumulates its
+// grid-stride pairs in order; the wave reduction is a fixed butterfly, the workgroup's is a sum in wave order; every
+// workgroup stores its partials, and ONE thread per step distance sums them in workgroup order (reduce_partials_kernel).
+// No floating-point atomics anywhere.
+#include "sgd_host.h"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+namespace gfs {
+
+static constexpr unsigned Q_BLOCK = 256, Q_PAIRS_PER_THREAD = 8, Q_MAX_BLOCKS = 2048;
+static constexpr uint32_t Q_NO_NODE = 0xFFFFFFFFu;
+
+unsigned quality_blocks(uint64_t n_steps) {
+    const uint64_t per_block = (uint64_t)Q_BLOCK * Q_PAIRS_PER_THREAD;
+    const uint64_t b = (n_steps + per_block - 1) / per_block;
+    return (unsigned)(b < 1 ? 1 : (b > Q_MAX_BLOCKS ? Q_MAX_BLOCKS : b));
+}
+
+// ---- the one per-pair function (sgd.rs:1252-1275) ---------------------------------------------------------------------
+// step record: { slot | NO_NODE, path | rev << 31, pos lo, pos hi (23 bits) | crowding exponents } (index_kernels.hip)
+__device__ __forceinline__ uint64_t rec_pos(const uint4 r) { return (uint64_t)r.z | ((uint64_t)(r.w & 0x7FFFFFu) << 32); }
+__device__ __forceinline__ uint32_t rec_path(const uint4 r) { return r.y & 0x7FFFFFFFu; }
+
+// x: the context's position buffer in its own order — 1D x[slot] (dims = 0), nD the planes [end][dim][slot], of which the
+// '+' end (end 0) is planes 0..dims-1.  False: the pair is skipped (another path, d_path == 0, an absent node).
+__device__ __forceinline__ bool pair_error(const uint4 ra, const uint4 rb, const double *x, const uint64_t n_nodes, const uint32_t dims,
+                                           double &err, double &rel_sq) {
+    if (rec_path(ra) != rec_path(rb)) return false;
+    const double d_path = fabs((double)rec_pos(ra) - (double)rec_pos(rb));   // :1252-1254
+    if (d_path == 0.0) return false;                                         // :1256
+    if (ra.x == Q_NO_NODE || rb.x == Q_NO_NODE) return false;                // :1260-1267
+    double sum_sq = 0.0;                                                     // layout.rs:126-133
+    const uint32_t terms = dims ? dims : 1u;
+    for (uint32_t d = 0; d < terms; ++d) {
+        const double delta = x[(uint64_t)d * n_nodes + ra.x] - x[(uint64_t)d * n_nodes + rb.x];
+        sum_sq += delta * delta;
+    }
+    err = sqrt(sum_sq) - d_path;                                             // :1273
+    rel_sq = (err * err) / (d_path * d_path);                                // :1274
+    return true;
+}
+
+// ---- fixed-tree reductions ------------------------------------------------------------------------------------------------
+// Five 8-byte fields per accumulator; what a field is says how it is combined.
+enum FieldOp { SUM_U64, SUM_F64, MAX_F64 };
+struct PairFields {                                                        // pairs, sum_rel_sq, max_rel_sq, sum_abs, sum_sq
+    static __host__ __device__ constexpr FieldOp op(int f) { return f == 0 ? SUM_U64 : f == 2 ? MAX_F64 : SUM_F64; }
+};
+struct SortFields {                                                        // steps, abs_err_sum, genomic_sum, sq_err_sum, -
+    static __host__ __device__ constexpr FieldOp op(int f) { return f == 3 ? SUM_F64 : SUM_U64; }
+};
+
+__device__ __forceinline__ uint64_t combine(const FieldOp op, const uint64_t a, const uint64_t b) {
+    if (op == SUM_U64) return a + b;
+    const double x = __longlong_as_double((long long)a), y = __longlong_as_double((long long)b);
+    return (uint64_t)__double_as_longlong(op == SUM_F64 ? x + y : (y > x ? y : x));
+}
+
+// One workgroup's five fields -> partials[field][zi][block].  Butterfly over the wave (both partners of a step compute the
+// same commutative a + b), then thread 0 combines the waves in wave order.
+template <typename F>
+__device__ __forceinline__ void store_block_partials(uint64_t (&v)[5], uint64_t *partials, const uint32_t n_z, const uint32_t zi) {
+    __shared__ uint64_t wave_part[Q_BLOCK / 64][5];
+#pragma unroll
+    for (int f = 0; f < 5; ++f)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1)
+            v[f] = combine(F::op(f), v[f], (uint64_t)__shfl_xor((unsigned long long)v[f], off, 64));
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (lane == 0)
+#pragma unroll
+        for (int f = 0; f < 5; ++f) wave_part[wave][f] = v[f];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int f = 0; f < 5; ++f) {
+            uint64_t t = wave_part[0][f];
+            for (unsigned w = 1; w < Q_BLOCK / 64; ++w) t = combine(F::op(f), t, wave_part[w][f]);
+            partials[((uint64_t)f * n_z + zi) * gridDim.x + blockIdx.x] = t;
+        }
+    }
+}
+
+// partials[field][zi][0..n_blocks) -> out[zi][field], summed in workgroup order by thread 0; the others only stage a
+// tile of partials in LDS so that the serial chain runs at LDS latency.  One workgroup per step distance.
+template <typename F>
+__global__ void __launch_bounds__(Q_BLOCK) reduce_partials_kernel(const uint64_t *partials, const uint32_t n_blocks, uint64_t *out) {
+    __shared__ uint64_t tile[5][Q_BLOCK];
+    const uint32_t zi = blockIdx.x, n_z = gridDim.x;
+    uint64_t acc[5] = {0, 0, 0, 0, 0};                                     // (0 is +0.0 too)
+    for (uint32_t base = 0; base < n_blocks; base += Q_BLOCK) {
+        const uint32_t n = n_blocks - base < Q_BLOCK ? n_blocks - base : Q_BLOCK;
+        if (threadIdx.x < n)
+#pragma unroll
+            for (int f = 0; f < 5; ++f) tile[f][threadIdx.x] = partials[((uint64_t)f * n_z + zi) * n_blocks + base + threadIdx.x];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (uint32_t b = 0; b < n; ++b)
+#pragma unroll
+                for (int f = 0; f < 5; ++f) acc[f] = combine(F::op(f), acc[f], tile[f][b]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int f = 0; f < 5; ++f) out[(uint64_t)zi * 5 + f] = acc[f];
+}
+
+// ---- K7a ------------------------------------------------------------------------------------------------------------------
+// grid (quality_blocks(n_steps), n_z).  Reads step_rec[0..n_steps) only: s + z < n_steps.
+__global__ void __launch_bounds__(Q_BLOCK) pair_errors_kernel(const uint4 *step_rec, const uint64_t n_steps, const double *x, const uint64_t n_nodes,
+                                                              const uint32_t dims, const uint64_t *zs, uint64_t *partials) {
+    const uint32_t zi = blockIdx.y;
+    const uint64_t z = zs[zi];
+    uint64_t pairs = 0;
+    double sum_rel = 0.0, max_rel = 0.0, sum_abs = 0.0, sum_sq = 0.0;
+    if (z < n_steps) {
+        const uint64_t n = n_steps - z, stride = (uint64_t)gridDim.x * Q_BLOCK;
+        for (uint64_t s = (uint64_t)blockIdx.x * Q_BLOCK + threadIdx.x; s < n; s += stride) {
+            double err, rel;
+            if (!pair_error(step_rec[s], step_rec[s + z], x, n_nodes, dims, err, rel)) continue;
+            ++pairs;
+            sum_rel += rel;
+            max_rel = rel > max_rel ? rel : max_rel;
+            sum_abs += fabs(err);
+            sum_sq += err * err;
+        }
+    }
+    uint64_t v[5] = {pairs, (uint64_t)__double_as_longlong(sum_rel), (uint64_t)__double_as_longlong(max_rel),
+                     (uint64_t)__double_as_longlong(sum_abs), (uint64_t)__double_as_longlong(sum_sq)};
+    store_block_partials<PairFields>(v, partials, gridDim.y, zi);
+}
+
+// d_zs: n_z step distances; d_partials: 5 * n_z * quality_blocks(n_steps) words; d_out: n_z * 5 words
+// { pairs (u64), sum_rel_sq, max_rel_sq, sum_abs, sum_sq (f64 bits) }.  Asynchronous on st.
+hipError_t pair_errors_device(const uint4 *d_step_rec, uint64_t n_steps, const double *d_x, uint64_t n_nodes, uint32_t dims,
+                              const uint64_t *d_zs, uint32_t n_z, uint64_t *d_partials, uint64_t *d_out, hipStream_t st) {
+    if (n_z == 0) return hipSuccess;
+    const unsigned blocks = quality_blocks(n_steps);
+    hipLaunchKernelGGL(pair_errors_kernel, dim3(blocks, n_z), dim3(Q_BLOCK), 0, st, d_step_rec, n_steps, d_x, n_nodes, dims, d_zs, d_partials);
+    hipLaunchKernelGGL(reduce_partials_kernel<PairFields>, dim3(n_z), dim3(Q_BLOCK), 0, st, d_partials, blocks, d_out);
+    return hipGetLastError();
+}
+
+// ---- K7b ------------------------------------------------------------------------------------------------------------------
+// rel_sq[i] of the pair (step_a[i], step_b[i]); -1 where the pair is skipped (also: a step beyond the table)
+__global__ void __launch_bounds__(Q_BLOCK) pair_list_kernel(const uint4 *step_rec, const uint64_t n_steps, const double *x, const uint64_t n_nodes,
+                                                            const uint32_t dims, const uint64_t *step_a, const uint64_t *step_b, const uint64_t n,
+                                                            double *rel_sq) {
+    const uint64_t stride = (uint64_t)gridDim.x * Q_BLOCK;
+    for (uint64_t i = (uint64_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < n; i += stride) {
+        const uint64_t sa = step_a[i], sb = step_b[i];
+        double err, rel, out = -1.0;
+        if (sa < n_steps && sb < n_steps && pair_error(step_rec[sa], step_rec[sb], x, n_nodes, dims, err, rel)) out = rel;
+        rel_sq[i] = out;
+    }
+}
+hipError_t pair_list_device(const uint4 *d_step_rec, uint64_t n_steps, const double *d_x, uint64_t n_nodes, uint32_t dims,
+                            const uint64_t *d_step_a, const uint64_t *d_step_b, uint64_t n, double *d_rel_sq, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    const uint64_t b = (n + Q_BLOCK - 1) / Q_BLOCK;
+    hipLaunchKernelGGL(pair_list_kernel, dim3((unsigned)(b > Q_MAX_BLOCKS ? Q_MAX_BLOCKS : b)), dim3(Q_BLOCK), 0, st, d_step_rec, n_steps, d_x,
+                       n_nodes, dims, d_step_a, d_step_b, n, d_rel_sq);
+    return hipGetLastError();
+}
+
+// ---- K7c ------------------------------------------------------------------------------------------------------------------
+// length of the node of rank r (0 for r = n_nodes, so that the scan's last element is the total)
+struct RankLen {
+    const uint32_t *order, *node_len;
+    uint64_t n_nodes;
+    __host__ __device__ uint64_t operator()(uint64_t r) const { return r >= n_nodes ? 0ull : (uint64_t)node_len[order[r]]; }
+};
+// sorted position of every node, by slot: spos[perm[order[r]]] = prefix[r]
+__global__ void scatter_sorted_pos_kernel(const uint64_t *prefix, const uint32_t *order, const uint32_t *perm, uint64_t *spos, uint64_t n) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += stride) spos[perm[order[r]]] = prefix[r];
+}
+// adjacent steps of every path (measure_layout_quality.rs:130-160).  Reads step_rec[0..n_steps) only.
+__global__ void __launch_bounds__(Q_BLOCK) sort_quality_kernel(const uint4 *step_rec, const uint64_t n_steps, const uint64_t *spos, uint64_t *partials) {
+    uint64_t steps = 0, abs_sum = 0, gen_sum = 0;
+    double sq_sum = 0.0;
+    if (n_steps > 1) {
+        const uint64_t n = n_steps - 1, stride = (uint64_t)gridDim.x * Q_BLOCK;
+        for (uint64_t s = (uint64_t)blockIdx.x * Q_BLOCK + threadIdx.x; s < n; s += stride) {
+            const uint4 ra = step_rec[s], rb = step_rec[s + 1];
+            if (rec_path(ra) != rec_path(rb) || ra.x == Q_NO_NODE) continue;               // :139-144
+            const uint64_t gd = rec_pos(rb) - rec_pos(ra);                                 // = the first node's length
+            const uint64_t pa = spos[ra.x], pb = rb.x == Q_NO_NODE ? 0ull : spos[rb.x];    // :149-150 unwrap_or(0.0)
+            const uint64_t ld = pb > pa ? pb - pa : pa - pb;
+            const uint64_t ae = ld > gd ? ld - gd : gd - ld;
+            ++steps; abs_sum += ae; gen_sum += gd;
+            sq_sum += (double)ae * (double)ae;
+        }
+    }
+    uint64_t v[5] = {steps, abs_sum, gen_sum, (uint64_t)__double_as_longlong(sq_sum), 0};
+    store_block_partials<SortFields>(v, partials, 1, 0);
+}
+
+// d_order: rank -> dense index (sort_order_device).  d_prefix: n_nodes + 1 words, d_spos: n_nodes words, d_partials:
+// 5 * quality_blocks(n_steps) words, d_out: 5 words { steps, abs_err_sum, genomic_sum (u64), sq_err_sum (f64 bits), 0 }.
+// *total_len_out = the graph's length in bp; at 2^53 and beyond the pass is not run (the caller refuses).  Synchronous.
+hipError_t sort_quality_device(const uint4 *d_step_rec, uint64_t n_steps, const uint32_t *d_order, const uint32_t *d_node_len,
+                               const uint32_t *d_perm, uint64_t n_nodes, uint64_t *d_prefix, uint64_t *d_spos, uint64_t *d_partials,
+                               uint64_t *d_out, uint64_t *total_len_out, hipStream_t st) {
+    auto lens = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), RankLen{d_order, d_node_len, n_nodes});
+    size_t tmp_bytes = 0;
+    hipError_t e = rocprim::exclusive_scan(nullptr, tmp_bytes, lens, d_prefix, (uint64_t)0, (size_t)(n_nodes + 1), rocprim::plus<uint64_t>(), st);
+    if (e != hipSuccess) return e;
+    void *d_tmp = nullptr;
+    if ((e = hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 8)) != hipSuccess) return e;
+    e = rocprim::exclusive_scan(d_tmp, tmp_bytes, lens, d_prefix, (uint64_t)0, (size_t)(n_nodes + 1), rocprim::plus<uint64_t>(), st);
+    if (e == hipSuccess) e = hipMemcpyAsync(total_len_out, d_prefix + n_nodes, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(d_tmp);
+    if (e != hipSuccess || *total_len_out >= (1ull << 53)) return e;
+    const unsigned blocks = quality_blocks(n_steps);
+    hipLaunchKernelGGL(scatter_sorted_pos_kernel, dim3(1024), dim3(256), 0, st, d_prefix, d_order, d_perm, d_spos, n_nodes);
+    hipLaunchKernelGGL(sort_quality_kernel, dim3(blocks), dim3(Q_BLOCK), 0, st, d_step_rec, n_steps, d_spos, d_partials);
+    hipLaunchKernelGGL(reduce_partials_kernel<SortFields>, dim3(1), dim3(Q_BLOCK), 0, st, d_partials, blocks, d_out);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    return hipStreamSynchronize(st);
+}
+
+hipError_t warm_module_quality() {
+    hipFuncAttributes attr;
+    return hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&pair_errors_kernel));
+}
+
+}  // namespace gfs

@@ -48,6 +48,7 @@ hipError_t warm_module_nd();
 hipError_t warm_module_nd_team();
 hipError_t warm_module_nd_team_wide();
 hipError_t warm_module_index();
+hipError_t warm_module_quality();
 
 // index_kernels.hip
 hipError_t init_positions_device(const uint32_t *d_node_len, const uint32_t *d_perm, double *d_x, uint64_t n);
@@ -60,6 +61,23 @@ hipError_t build_path_index_device(const uint32_t *d_step_node, const uint8_t *d
                                    uint64_t n_steps, uint64_t n_nodes, uint64_t *d_tmp, uint4 *d_rec, uint64_t *d_path_len);
 hipError_t sort_order_device(const double *d_x_layout, const uint32_t *d_perm, uint64_t n, uint64_t stride_doubles,
                              void *d_tmp, uint32_t **d_order_out);
+
+// quality_kernels.hip (K7): read-outs of the resident positions.  They write their own output buffers only.
+// Workgroups of the step passes: a function of n_steps alone, so that a result does not depend on the device.
+unsigned quality_blocks(uint64_t n_steps);
+// K7a: all pairs of steps (s, s + z) for n_z step distances.  d_partials: 5 * n_z * quality_blocks(n_steps) words;
+// d_out: 5 words per distance { pairs (u64), sum_rel_sq, max_rel_sq, sum_abs, sum_sq (f64 bits) }.  Asynchronous.
+hipError_t pair_errors_device(const uint4 *d_step_rec, uint64_t n_steps, const double *d_x, uint64_t n_nodes, uint32_t dims,
+                              const uint64_t *d_zs, uint32_t n_z, uint64_t *d_partials, uint64_t *d_out, hipStream_t st);
+// K7b: d_rel_sq[i] of the pair (d_step_a[i], d_step_b[i]), -1 where it is skipped.  Asynchronous.
+hipError_t pair_list_device(const uint4 *d_step_rec, uint64_t n_steps, const double *d_x, uint64_t n_nodes, uint32_t dims,
+                            const uint64_t *d_step_a, const uint64_t *d_step_b, uint64_t n, double *d_rel_sq, hipStream_t st);
+// K7c: d_order from sort_order_device; d_prefix: n_nodes + 1 words, d_spos: n_nodes, d_partials: 5 * quality_blocks(n_steps),
+// d_out: 5 words { steps, abs_err_sum, genomic_sum (u64), sq_err_sum (f64 bits), 0 }; not run where *total_len_out >= 2^53.
+// Synchronous.
+hipError_t sort_quality_device(const uint4 *d_step_rec, uint64_t n_steps, const uint32_t *d_order, const uint32_t *d_node_len,
+                               const uint32_t *d_perm, uint64_t n_nodes, uint64_t *d_prefix, uint64_t *d_spos, uint64_t *d_partials,
+                               uint64_t *d_out, uint64_t *total_len_out, hipStream_t st);
 
 // sgd_kernels_1d.hip: the multi-GPU replica merge
 hipError_t launch_merge_prepare(const double *x, const double *x_prev, float *buf, uint64_t n, hipStream_t st);

@@ -79,6 +79,20 @@ class RankInfo(C.Structure):
                 ("windows", C.c_uint64), ("last_merge_kernels_ms", C.c_double), ("idle", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class PairError(C.Structure):
+    """gfs_pair_error: all pairs of steps (s, s + step_distance) of one path."""
+    _fields_ = [("step_distance", C.c_uint64), ("pairs", C.c_uint64), ("sum_rel_sq", C.c_double), ("max_rel_sq", C.c_double),
+                ("sum_abs", C.c_double), ("sum_sq", C.c_double)]
+
+
+class SortQuality(C.Structure):
+    """gfs_sort_quality: measure_layout_quality.rs on the graph sorted by the current 1D positions."""
+    _fields_ = [("steps", C.c_uint64), ("abs_err_sum", C.c_uint64), ("genomic_sum", C.c_uint64), ("sq_err_sum", C.c_double)]
+
+
+PAIR_ERROR_DTYPE = np.dtype([("step_distance", "<u8"), ("pairs", "<u8"), ("sum_rel_sq", "<f8"), ("max_rel_sq", "<f8"),
+                             ("sum_abs", "<f8"), ("sum_sq", "<f8")])
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p)
 MERGE_RULES = {"anneal": 0, "sum": 1, "mean": 2, "touch": 3}
 
@@ -100,6 +114,7 @@ EXPORTS = [
     "gfs_rank_bind_exchange_buffer", "gfs_rank_window_begin", "gfs_rank_window_end", "gfs_rank_finish_begin",
     "gfs_rank_finish_buffer", "gfs_rank_finish_end", "gfs_rank_run",
     "gfs_ctx_debug_step_records", "gfs_ctx_debug_kshift", "gfs_phase_window", "gfs_ctx_phase_window",
+    "gfs_ctx_pair_errors", "gfs_stress_sample_pairs", "gfs_ctx_stress_of_pairs", "gfs_ctx_sort_quality", "gfs_pair_errors",
 ]
 
 _lib = None
@@ -176,6 +191,11 @@ def lib():
         L.gfs_rank_finish_buffer.restype = C.c_void_p
         L.gfs_rank_finish_end.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.gfs_rank_run.argtypes = [C.c_void_p, ALLREDUCE_FN, C.c_void_p, C.c_void_p]
+        L.gfs_ctx_pair_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.gfs_stress_sample_pairs.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gfs_ctx_stress_of_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gfs_ctx_sort_quality.argtypes = [C.c_void_p, C.c_void_p]
+        L.gfs_pair_errors.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         _lib = L
     return _lib
 
@@ -288,6 +308,30 @@ def merge_prepare(x_ptr, x_prev_ptr, buf_ptr, n, stream=None):
 def merge_apply(x_ptr, x_prev_ptr, buf_ptr, n, divide_all_by=0.0, stream=None):
     check(lib().gfs_merge_apply(C.c_void_p(x_ptr), C.c_void_p(x_prev_ptr), C.c_void_p(buf_ptr), C.c_uint64(n),
                                 C.c_double(divide_all_by), C.c_void_p(stream or 0)))
+
+
+# ---- quality read-outs (K7) --------------------------------------------------------------------
+def stress_sample_pairs(g, samples=10000, seed=12345):
+    """gfs_stress_sample_pairs (host only): the step pairs (step_a, step_b) calculate_layout_stress draws, less those its
+    data-independent `continue`s drop."""
+    v, keep = make_view(g)
+    sa, sb = np.zeros(max(samples, 1), dtype=np.uint64), np.zeros(max(samples, 1), dtype=np.uint64)
+    n = C.c_uint64(0)
+    check(lib().gfs_stress_sample_pairs(C.byref(v), C.c_uint64(samples), C.c_uint64(seed), _ptr(sa), _ptr(sb), C.byref(n)))
+    return sa[:n.value].copy(), sb[:n.value].copy()
+
+
+def pair_errors(g, positions, zs, dims=0):
+    """gfs_pair_errors: the exhaustive per-step-distance errors of a finished result (dims = 0: x[n_nodes], else Layout.coords
+    order), measured on device 0.  Returns a PAIR_ERROR_DTYPE array, one row per z."""
+    v, keep = make_view(g)
+    x = np.ascontiguousarray(positions, dtype=np.float64)
+    if x.shape[0] != (g.n_nodes * 2 * dims if dims else g.n_nodes):
+        raise ValueError("positions length does not match the graph and dims")
+    zs = np.ascontiguousarray(zs, dtype=np.uint64)
+    out = np.zeros(zs.shape[0], dtype=PAIR_ERROR_DTYPE)
+    check(lib().gfs_pair_errors(C.byref(v), C.c_uint64(dims), _ptr(x), _ptr(zs), C.c_uint64(zs.shape[0]), _ptr(out)))
+    return out
 
 
 # ---- multi-device planning (host only) and the rank object -------------------------------------
@@ -510,6 +554,43 @@ class Context:
         counts = np.zeros(T, dtype=np.uint64)
         check(lib().gfs_ctx_trace(self._h, _ptr(out), T * k, _ptr(counts), T))
         return out.reshape(T, k), counts
+
+    # ---- quality read-outs of the resident positions (K7): nothing is downloaded, nothing is disturbed ----
+    def pair_errors(self, zs, stream=None):
+        """gfs_ctx_pair_errors: all pairs of steps (s, s + z) for every z of zs.  PAIR_ERROR_DTYPE array, one row per z."""
+        zs = np.ascontiguousarray(zs, dtype=np.uint64)
+        out = np.zeros(zs.shape[0], dtype=PAIR_ERROR_DTYPE)
+        check(lib().gfs_ctx_pair_errors(self._h, _ptr(zs), C.c_uint64(zs.shape[0]), _ptr(out), C.c_void_p(stream or 0)))
+        return out
+
+    def stress_of_pairs(self, step_a, step_b):
+        """gfs_ctx_stress_of_pairs.  Returns (stress, counted, rel_sq[n]) — rel_sq < 0 marks a skipped pair."""
+        sa = np.ascontiguousarray(step_a, dtype=np.uint64)
+        sb = np.ascontiguousarray(step_b, dtype=np.uint64)
+        if sa.shape != sb.shape:
+            raise ValueError("step_a and step_b differ in length")
+        rel = np.zeros(sa.shape[0], dtype=np.float64)
+        counted, stress = C.c_uint64(0), C.c_double(0.0)
+        check(lib().gfs_ctx_stress_of_pairs(self._h, _ptr(sa), _ptr(sb), C.c_uint64(sa.shape[0]), _ptr(rel), C.byref(counted),
+                                            C.byref(stress)))
+        return float(stress.value), int(counted.value), rel
+
+    def sampled_stress(self, samples=10000, seed=12345):
+        """calculate_layout_stress (sgd.rs:1196-1283) of the resident positions: the reference's sample stream, the pairs evaluated
+        on the device, summed in sample order — the reference's value bit for bit at seed 12345."""
+        sa, sb = stress_sample_pairs(self.graph, samples, seed)
+        return self.stress_of_pairs(sa, sb)[0]
+
+    def sort_quality(self):
+        """gfs_ctx_sort_quality (1D contexts): dict(steps, abs_err_sum, genomic_sum, sq_err_sum) and the figures
+        measure_layout_quality.rs derives from them (mse, rmse, mae, relative_error)."""
+        q = SortQuality()
+        check(lib().gfs_ctx_sort_quality(self._h, C.byref(q)))
+        steps, abs_sum, gen = int(q.steps), int(q.abs_err_sum), int(q.genomic_sum)
+        mse = q.sq_err_sum / steps if steps else 0.0
+        mae = abs_sum / steps if steps else 0.0
+        return dict(steps=steps, abs_err_sum=abs_sum, genomic_sum=gen, sq_err_sum=float(q.sq_err_sum), mse=mse,
+                    rmse=float(np.sqrt(mse)), mae=mae, relative_error=(mae / (gen / steps)) if gen > 0 else 0.0)
 
     # ---- test hooks ----
     def step_records(self):

@@ -9,6 +9,8 @@ diagnostic binaries, RNG-free wherever the reference is (SURVEY.md §8c(4), §7 
 * `stress_by_scale`  — the same relative error, but with the step distance drawn log-uniformly and reported per
                         octave, so that one can see WHERE (which path distances) two layouts differ; the plain sampled
                         stress draws uniform pairs and is dominated by the handful of short-range pairs it happens to hit.
+* `device_profile`   — the exhaustive relative error per step distance, computed ON THE DEVICE from a resident context
+                        (hip.Context.pair_errors, K7): the RNG-free replacement for `stress_by_scale`'s sampled octaves.
 * `kendall_tau`, `spearman_rho`, `oriented` — rank agreement of two sorts (a 1D layout is mirror-invariant).
 * `inversions_vs_chain` — exact count of adjacent inversions against a known chain order (P1 graphs).
 """
@@ -146,6 +148,39 @@ def stress_by_scale(g, coords, dims=0, samples=400000, seed=777, max_octaves=32,
         num[k] = int(m.sum())
         rms[k] = float(np.sqrt(e2[m].mean())) if num[k] else 0.0
     return np.exp2(np.arange(n_oct + 1)), rms, num
+
+
+# ---- the exhaustive profile, on the device ---------------------------------------------------------
+def step_distance_ladder(max_path_steps):
+    """z = 1, 2, 3, 4, 6, 8, 12, 16, ...: every 2^k and 3 * 2^(k-1) below the longest path's step count."""
+    zs, k = [], 0
+    while (1 << k) < max_path_steps:
+        zs.append(1 << k)
+        if k >= 1 and 3 << (k - 1) < max_path_steps:
+            zs.append(3 << (k - 1))
+        k += 1
+    return zs
+
+
+def profile_rows(pe):
+    """Per step distance: dict(z, pairs, rms_rel, max_rel, rmse, mae) from rows of gfs_pair_error sums."""
+    rows = []
+    for r in pe:
+        n = int(r["pairs"])
+        rows.append(dict(z=int(r["step_distance"]), pairs=n,
+                         rms_rel=float(np.sqrt(r["sum_rel_sq"] / n)) if n else 0.0, max_rel=float(np.sqrt(r["max_rel_sq"])),
+                         rmse=float(np.sqrt(r["sum_sq"] / n)) if n else 0.0, mae=float(r["sum_abs"] / n) if n else 0.0))
+    return rows
+
+
+def device_profile(ctx, zs=None):
+    """Relative and absolute error of ALL pairs of path steps (s, s + z) of the positions resident in `ctx` (a hip.Context),
+    one row per step distance: list of dict(z, pairs, rms_rel, max_rel, rmse, mae).  zs = None: step_distance_ladder of the
+    graph's longest path.  Exhaustive and deterministic — no sample, no seed — and nothing is downloaded but the sums."""
+    if zs is None:
+        g = ctx.graph
+        zs = step_distance_ladder(int(np.diff(g.path_first_step.astype(np.int64)).max()) if g.n_paths else 0)
+    return profile_rows(ctx.pair_errors(np.asarray(zs, dtype=np.uint64)))
 
 
 # ---- rank agreement ------------------------------------------------------------------------------

@@ -264,6 +264,58 @@ int   gfs_ctx_debug_kshift(gfs_ctx *ctx, int32_t set, int32_t *kshift_out);
  * up with the flag. */
 int   gfs_ctx_phase_window(gfs_ctx *ctx, int64_t set_begin, int64_t set_end, uint64_t *begin_out, uint64_t *end_out);
 
+/* ---- quality read-outs (K7): how good is what is in HBM now ----
+ * Every entry evaluates ONE per-pair formula, the reference's (calculate_layout_stress, sgd.rs:1252-1275, Layout::distance):
+ *   d_path = |(double)pos_a - (double)pos_b|, d_layout = sqrt(sum over dimensions, left to right, of (c_a - c_b)^2) between the
+ *   + ends of the two steps' nodes (1D: one term), err = d_layout - d_path, rel_sq = err*err / (d_path*d_path);
+ * a pair is skipped when d_path == 0, when either step's node is absent, or when the steps lie in different paths.  A pair's
+ * value is the reference's bit for bit.  The kernels write nothing but their own output: positions, records and RNG streams
+ * are left alone, so a read-out between two gfs_ctx_run_range calls does not change the run.  Results are deterministic and do
+ * not depend on the device: the launch shape is a function of n_steps, every reduction has a fixed order, no float atomics.
+ * On a rank's context (gfs_rank_ctx) a read-out covers that rank's shard of the paths, on that rank's replica. */
+typedef struct gfs_pair_error {
+    uint64_t step_distance;           /* z: pairs of steps (s, s + z) of one path                                   */
+    uint64_t pairs;                   /* pairs not skipped                                                          */
+    double   sum_rel_sq;              /* sum of rel_sq: rms relative error = sqrt(sum_rel_sq / pairs)               */
+    double   max_rel_sq;              /* exact (order-independent)                                                  */
+    double   sum_abs;                 /* sum of |err|, bp                                                           */
+    double   sum_sq;                  /* sum of err^2, bp^2                                                         */
+} gfs_pair_error;
+
+/* measure_layout_quality.rs:100-208 on the graph SORTED by the context's current 1D positions: a node's position is the prefix
+ * sum of node lengths in rank order; per pair of consecutive path steps the genomic distance is the first node's length and
+ * the layout distance |pos_b - pos_a|; a pair whose first node is absent is skipped, an absent second node counts as
+ * position 0.  mae = abs_err_sum / steps, rmse = sqrt(sq_err_sum / steps), relative_error = abs_err_sum / genomic_sum. */
+typedef struct gfs_sort_quality {
+    uint64_t steps;                   /* pairs counted                                                              */
+    uint64_t abs_err_sum;             /* exact                                                                      */
+    uint64_t genomic_sum;             /* exact                                                                      */
+    double   sq_err_sum;              /* every term exact, summed in a fixed order                                  */
+} gfs_sort_quality;
+
+/* all pairs (s, s + z) for each z = zs[0..n_z) (n_z <= 65535) in one launch on hip_stream; synchronises before returning.
+ * out[n_z].  GFS_E_ARG (before any device call) for null pointers or a z of 0, GFS_E_STATE on a context without positions.
+ * A z no path is long enough for gives pairs = 0 and zero sums. */
+int gfs_ctx_pair_errors(gfs_ctx *ctx, const uint64_t *zs, uint64_t n_z, gfs_pair_error *out, void *hip_stream);
+/* host only: the sample stream of calculate_layout_stress (sgd.rs:1218-1250) — one Xoshiro256+ seeded `seed` (the reference's is
+ * 12345), step a uniform over all steps, rank b uniform over its path, in the reference's draw order — less the candidates its
+ * data-independent `continue`s drop (paths of fewer than 2 steps, rank_a == rank_b).  step_a, step_b: [sample_count]; *n_out
+ * pairs are written.  A graph of fewer than 2 steps gives none (:1220). */
+int gfs_stress_sample_pairs(const gfs_graph_view *g, uint64_t sample_count, uint64_t seed, uint64_t *step_a, uint64_t *step_b,
+                            uint64_t *n_out);
+/* rel_sq of the pairs (step_a[i], step_b[i]), i < n, on the device; rel_sq_out (nullable, [n]) receives them, a skipped pair as
+ * -1.  *counted = pairs not skipped, *stress = sqrt(sum of rel_sq / counted) with the sum taken on the host in the order of
+ * the list — on gfs_stress_sample_pairs' list the reference's calculate_layout_stress bit for bit — or 0.0 where nothing was
+ * counted.  GFS_E_ARG for a step >= n_steps.  Synchronises. */
+int gfs_ctx_stress_of_pairs(gfs_ctx *ctx, const uint64_t *step_a, const uint64_t *step_b, uint64_t n, double *rel_sq_out /*nullable*/,
+                            uint64_t *counted, double *stress);
+/* 1D contexts only (GFS_E_STATE otherwise); the order is gfs_ctx_sort_order's.  GFS_E_UNSUPPORTED for a graph of 2^53 bp or more. */
+int gfs_ctx_sort_quality(gfs_ctx *ctx, gfs_sort_quality *out);
+/* one-shot, for a caller that holds a finished result and no context: builds a context on device 0, uploads, measures.
+ * dims = 0: positions is x[n_nodes] by dense index; dims = 1..GFS_MAX_DIMS: Layout.coords order, n_nodes*2*dims. */
+int gfs_pair_errors(const gfs_graph_view *g, uint64_t dims, const double *positions, const uint64_t *zs, uint64_t n_z,
+                    gfs_pair_error *out);
+
 /* ---- multi-device runs (no reference equivalent: the reference is one process, src/sgd.rs:413-593) ----
  * Paths are sharded over `world` ranks, one rank per GPU (one process per GPU, or one host thread per GPU); every rank
  * performs its share of an iteration's term updates on its own replica of the positions; after every window of
