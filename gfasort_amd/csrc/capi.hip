@@ -1392,6 +1392,104 @@ int gfs_ctx_sort_quality(gfs_ctx *c, gfs_sort_quality *out) {
     return GFS_OK;
 }
 
+// ---- K7d / K7e / K7f: per path, per stretched pair, per node ------------------------------------------------------------
+static int check_diagnosis(uint64_t z, double ratio) {
+    if (z == 0) return fail(GFS_E_ARG, "a step distance of 0");
+    if (!(ratio >= 0.0)) return fail(GFS_E_ARG, "ratio must be a number >= 0");
+    return GFS_OK;
+}
+// the duration of an entry's device work on stderr under GFS_TIMING (one HIP event pair, as gfs_ctx_pair_errors)
+struct QualityTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipStream_t st;
+    explicit QualityTimer(hipStream_t s) : st(s) {
+        if (!std::getenv("GFS_TIMING")) return;
+        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, st) != hipSuccess) done();
+    }
+    void stop() { if (e0 && hipEventRecord(e1, st) != hipSuccess) done(); }
+    void report(const char *what, uint64_t z, uint64_t n_steps) {            // after the stream was synchronised
+        float ms = 0.f;
+        if (e0 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess)
+            std::fprintf(stderr, "[%s] z = %llu, %llu steps: kernels %.4f ms\n", what, (unsigned long long)z, (unsigned long long)n_steps, ms);
+    }
+    void done() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); e0 = e1 = nullptr; }
+    ~QualityTimer() { done(); }
+};
+
+int gfs_ctx_path_errors(gfs_ctx *c, uint64_t z, double ratio, gfs_path_error *out, uint64_t n_paths, void *hip_stream) {
+    if (!c || (!out && n_paths)) return fail(GFS_E_ARG, "null argument");
+    int rc = check_diagnosis(z, ratio);
+    if (rc) return rc;
+    if (n_paths != c->n_paths) return fail(GFS_E_ARG, "n_paths does not match the context");
+    if (!c->d_x) return fail(GFS_E_STATE, "the context has no positions (not set up)");
+    if (n_paths == 0) return GFS_OK;
+    static_assert(sizeof(gfs_path_error) == 8 * 8, "K7d writes gfs_path_error as 8 words");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const uint64_t tiles = gfs::quality_tiles(c->n_steps);
+    rc = quality_scratch(c, 8 * n_paths + 10 * tiles);                     // [out | head partials | tail partials]
+    if (rc) return rc;
+    uint64_t *d_out = c->d_quality, *d_head = d_out + 8 * n_paths, *d_tail = d_head + 5 * tiles;
+    QualityTimer timer(st);
+    hipError_t e = gfs::path_errors_device(c->d_step_rec, c->n_steps, c->d_path_rec, n_paths, c->d_x, c->n_nodes, (uint32_t)c->dims, z, ratio,
+                                           d_head, d_tail, d_out, st);
+    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("path_errors_device: ") + hipGetErrorString(e));
+    timer.stop();
+    HIPCHK(hipMemcpyAsync(out, d_out, n_paths * sizeof(gfs_path_error), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    timer.report("gfs_ctx_path_errors", z, c->n_steps);
+    return GFS_OK;
+}
+
+int gfs_ctx_stretched_pairs(gfs_ctx *c, uint64_t z, double ratio, gfs_stretched_pair *out, uint64_t cap, uint64_t *total,
+                            void *hip_stream) {
+    if (!c || !total || (!out && cap)) return fail(GFS_E_ARG, "null argument");
+    *total = 0;
+    int rc = check_diagnosis(z, ratio);
+    if (rc) return rc;
+    if (!c->d_x) return fail(GFS_E_STATE, "the context has no positions (not set up)");
+    static_assert(sizeof(gfs_stretched_pair) == 5 * 8, "K7e writes gfs_stretched_pair as 5 words");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const uint64_t tiles = gfs::quality_tiles(c->n_steps), room = std::min(cap, c->n_steps);
+    rc = quality_scratch(c, 2 * (tiles + 1) + 5 * room);                   // [tile counts | offsets | list]
+    if (rc) return rc;
+    uint64_t *d_counts = c->d_quality, *d_offsets = d_counts + tiles + 1, *d_list = d_offsets + tiles + 1;
+    QualityTimer timer(st);
+    hipError_t e = gfs::stretched_pairs_device(c->d_step_rec, c->n_steps, c->d_x, c->n_nodes, (uint32_t)c->dims, z, ratio, d_counts, d_offsets,
+                                               room ? d_list : nullptr, room, total, st);
+    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("stretched_pairs_device: ") + hipGetErrorString(e));
+    timer.stop();
+    const uint64_t n = std::min(room, *total);
+    if (n) HIPCHK(hipMemcpyAsync(out, d_list, n * sizeof(gfs_stretched_pair), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    timer.report("gfs_ctx_stretched_pairs", z, c->n_steps);
+    return GFS_OK;
+}
+
+int gfs_ctx_node_errors(gfs_ctx *c, uint64_t z, double ratio, gfs_node_error *out, uint64_t n_nodes, void *hip_stream) {
+    if (!c || (!out && n_nodes)) return fail(GFS_E_ARG, "null argument");
+    int rc = check_diagnosis(z, ratio);
+    if (rc) return rc;
+    if (n_nodes != c->n_nodes) return fail(GFS_E_ARG, "n_nodes does not match the context");
+    if (!c->d_x) return fail(GFS_E_STATE, "the context has no positions (not set up)");
+    if (n_nodes == 0) return GFS_OK;
+    static_assert(sizeof(gfs_node_error) == 3 * 8, "K7f writes gfs_node_error as 3 words");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    rc = quality_scratch(c, 6 * n_nodes);                                  // [per slot: pairs | stretched | max] [out]
+    if (rc) return rc;
+    uint64_t *d_slots = c->d_quality, *d_out = d_slots + 3 * n_nodes;
+    QualityTimer timer(st);
+    hipError_t e = gfs::node_errors_device(c->d_step_rec, c->n_steps, c->d_x, c->d_perm, n_nodes, (uint32_t)c->dims, z, ratio, d_slots, d_out, st);
+    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("node_errors_device: ") + hipGetErrorString(e));
+    timer.stop();
+    HIPCHK(hipMemcpyAsync(out, d_out, n_nodes * sizeof(gfs_node_error), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    timer.report("gfs_ctx_node_errors", z, c->n_steps);
+    return GFS_OK;
+}
+
 // ---- multi-GPU replica merge helpers (device pointers, asynchronous on hip_stream) -----------------
 int gfs_merge_prepare(const double *x, const double *x_prev, float *buf2n, uint64_t n, void *hip_stream) {
     if (!x || !x_prev || !buf2n) return fail(GFS_E_ARG, "null argument");
@@ -1448,6 +1546,21 @@ static int one_shot(const gfs_graph_view *g, const gfs_sgd_params *p, int dims, 
 }
 
 // A finished result measured without a run: a context that holds positions and nothing else (no schedule, no streams).
+static int positions_only_ctx(const gfs_graph_view *g, uint64_t dims, const double *positions, gfs_ctx **out) {
+    gfs_ctx *c = nullptr;
+    int rc = gfs_ctx_create(g, 0, &c);
+    if (rc) return rc;
+    c->dims = (int)dims;
+    c->x_len = dims ? c->n_nodes * 2 * dims : c->n_nodes;
+    hipError_t e = hipMalloc(&c->d_x, c->x_len * 8);
+    if (e != hipSuccess) { gfs_ctx_destroy(c); return fail(GFS_E_HIP, std::string("hipMalloc positions: ") + hipGetErrorString(e)); }
+    c->x_owned = true;
+    rc = gfs_ctx_upload_positions(c, positions, c->x_len);
+    if (rc) { gfs_ctx_destroy(c); return rc; }
+    *out = c;
+    return GFS_OK;
+}
+
 int gfs_pair_errors(const gfs_graph_view *g, uint64_t dims, const double *positions, const uint64_t *zs, uint64_t n_z,
                     gfs_pair_error *out) {
     if (!g) return fail(GFS_E_ARG, "null argument");
@@ -1458,15 +1571,28 @@ int gfs_pair_errors(const gfs_graph_view *g, uint64_t dims, const double *positi
     if (g->n_nodes == 0) return GFS_NOTHING_TO_DO;
     if (!positions) return fail(GFS_E_ARG, "positions buffer is null");
     gfs_ctx *c = nullptr;
-    rc = gfs_ctx_create(g, 0, &c);
+    rc = positions_only_ctx(g, dims, positions, &c);
     if (rc) return rc;
-    c->dims = (int)dims;
-    c->x_len = dims ? c->n_nodes * 2 * dims : c->n_nodes;
-    hipError_t e = hipMalloc(&c->d_x, c->x_len * 8);
-    if (e != hipSuccess) { gfs_ctx_destroy(c); return fail(GFS_E_HIP, std::string("hipMalloc positions: ") + hipGetErrorString(e)); }
-    c->x_owned = true;
-    rc = gfs_ctx_upload_positions(c, positions, c->x_len);
-    if (!rc) rc = gfs_ctx_pair_errors(c, zs, n_z, out, nullptr);
+    rc = gfs_ctx_pair_errors(c, zs, n_z, out, nullptr);
+    gfs_ctx_destroy(c);
+    return rc;
+}
+
+int gfs_diagnose(const gfs_graph_view *g, uint64_t dims, const double *positions, uint64_t z, double ratio,
+                 gfs_path_error *paths_out, gfs_stretched_pair *pairs_out, uint64_t cap, uint64_t *total) {
+    if (!g || !total || (!paths_out && g->n_paths) || (!pairs_out && cap)) return fail(GFS_E_ARG, "null argument");
+    *total = 0;
+    int rc = check_diagnosis(z, ratio);
+    if (rc) return rc;
+    if (dims > GFS_MAX_DIMS) return fail(GFS_E_ARG, "dims must be 0 (1D positions) or 1..8");
+    for (uint64_t p = 0; p < g->n_paths; ++p) paths_out[p] = gfs_path_error{};
+    if (g->n_nodes == 0) return GFS_NOTHING_TO_DO;
+    if (!positions) return fail(GFS_E_ARG, "positions buffer is null");
+    gfs_ctx *c = nullptr;
+    rc = positions_only_ctx(g, dims, positions, &c);
+    if (rc) return rc;
+    rc = gfs_ctx_path_errors(c, z, ratio, paths_out, g->n_paths, nullptr);
+    if (!rc) rc = gfs_ctx_stretched_pairs(c, z, ratio, pairs_out, cap, total, nullptr);
     gfs_ctx_destroy(c);
     return rc;
 }

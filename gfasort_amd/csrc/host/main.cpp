@@ -25,6 +25,8 @@ struct Args {
     unsigned bundle = 0;                           // 0 = auto, 1 = reference streams, 4..64
     bool reference_sampler = false, phased = false;
     bool stress_profile = false;                   // after a Y or an L step: the exhaustive error per step distance
+    bool diagnose = false;                         // after a Y or an L step: errors per path and the stretched adjacent pairs
+    double diagnose_ratio = 10.0;
 };
 
 static void usage() {
@@ -47,6 +49,10 @@ static void usage() {
         "                                       one line per step distance z = 1, 2, 3, 4, 6, 8, 12, ... — exhaustive, computed on\n"
         "                                       the device from the step's final positions; the sampled `layout stress` of -v is\n"
         "                                       dominated by the few short-range pairs it happens to hit)\n"
+        "                   [--diagnose] [--diagnose-ratio R]   (after every Y or L step, on stderr, for adjacent path steps: per path\n"
+        "                                       its steps, forward and reverse steps, counted pairs, rms relative error and stretched\n"
+        "                                       pairs, then the first 20 stretched pairs — those whose layout distance is more than\n"
+        "                                       R (default 10) times their path distance; computed on the device)\n"
         "Pipeline characters: Y = path-guided SGD sort, L = nD layout (HIP engine).\n"
         "g, s, S, u exist in the reference but are not part of this build.\n";
 }
@@ -71,6 +77,8 @@ static bool parse_args(int argc, char **argv, Args &a) {
         else if (f == "--reference-sampler") { a.bundle = 1; a.reference_sampler = true; }
         else if (f == "--phased-sampler") { a.phased = true; }
         else if (f == "--stress-profile") { a.stress_profile = true; }
+        else if (f == "--diagnose") { a.diagnose = true; }
+        else if (f == "--diagnose-ratio") { if (!(v = need(i))) return false; a.diagnose_ratio = std::stod(v); }
         else if (f == "--hip-flags") { if (!(v = need(i))) return false; a.flags = (uint32_t)std::stoul(v); }
         else if (f == "-h" || f == "--help") { usage(); exit(0); }
         else { std::cerr << "error: unexpected argument '" << f << "'\n"; return false; }
@@ -109,6 +117,53 @@ static void print_stress_profile(const std::vector<gfs_pair_error> &rows) {
         snprintf(buf, sizeof buf, "[gfasort] stress profile: z=%llu pairs=%llu rms_rel=%.17g max_rel=%.17g rmse_bp=%.17g mae_bp=%.17g\n",
                  (unsigned long long)r.step_distance, (unsigned long long)r.pairs, r.pairs ? std::sqrt(r.sum_rel_sq / n) : 0.0,
                  std::sqrt(r.max_rel_sq), r.pairs ? std::sqrt(r.sum_sq / n) : 0.0, r.pairs ? r.sum_abs / n : 0.0);
+        std::cerr << buf;
+    }
+}
+
+// The report of the reference's sgd_diagnostics binary, for the positions a step ended with: z = 1.  f: the graph the positions
+// speak of (dense index); names: its paths'.
+static void print_diagnosis(const FlatGraph &f, const std::vector<BiPath> &paths, size_t dims, const std::vector<double> &positions,
+                            double ratio) {
+    const LayoutDiagnosis d = layout_diagnosis(f, dims, positions, 1, ratio, 20);
+    char buf[512];
+    std::cerr << "[gfasort] diagnosis: path orientation and adjacent-step errors\n";
+    for (size_t p = 0; p < d.paths.size(); ++p) {
+        const gfs_path_error &r = d.paths[p];
+        snprintf(buf, sizeof buf, "[gfasort] diagnosis:   %s: %llu steps, %llu forward, %llu reverse (%.1f%% reverse), %llu pairs, "
+                 "rms relative error %.6g, %llu stretched\n", p < paths.size() ? paths[p].name.c_str() : "?", (unsigned long long)r.steps,
+                 (unsigned long long)(r.steps - r.reverse_steps), (unsigned long long)r.reverse_steps,
+                 r.steps ? 100.0 * (double)r.reverse_steps / (double)r.steps : 0.0, (unsigned long long)r.pairs,
+                 r.pairs ? std::sqrt(r.sum_rel_sq / (double)r.pairs) : 0.0, (unsigned long long)r.stretched);
+        std::cerr << buf;
+    }
+    snprintf(buf, sizeof buf, "[gfasort] diagnosis: %llu adjacent pairs with layout distance > %g x path distance%s\n",
+             (unsigned long long)d.total, ratio, d.total > d.pairs.size() ? " (the first 20 follow)" : "");
+    std::cerr << buf;
+    auto handle = [&](uint64_t s) {
+        const uint32_t n = f.step_node[s];
+        return (n == GFS_NO_NODE ? std::string("?") : std::to_string(f.node_ids[n])) + (f.step_is_rev[s] ? "-" : "+");
+    };
+    auto bp = [&](const gfs_stretched_pair &q, uint64_t s) {             // bp position of step s inside its path
+        uint64_t pos = 0;
+        for (uint64_t k = f.path_first_step[q.path]; k < s; ++k) if (f.step_node[k] != GFS_NO_NODE) pos += f.node_len[f.step_node[k]];
+        return pos;
+    };
+    auto where = [&](uint64_t s) {                                       // the + end of the step's node
+        const size_t n = f.step_node[s];
+        std::string out;
+        for (size_t k = 0; k < (dims ? dims : 1); ++k) {
+            snprintf(buf, sizeof buf, "%s%.0f", k ? "," : "", positions[dims ? n * 2 * dims + k : n]);
+            out += buf;
+        }
+        return out;
+    };
+    for (const gfs_stretched_pair &q : d.pairs) {
+        const std::string name = q.path < paths.size() ? paths[q.path].name : "?";
+        snprintf(buf, sizeof buf, "[gfasort] diagnosis:   %s %s->%s: path positions %llu -> %llu (dist=%.0fbp), layout positions %s -> %s "
+                 "(dist=%.0f), ratio %.1fx\n", name.c_str(), handle(q.step_a).c_str(), handle(q.step_b).c_str(),
+                 (unsigned long long)bp(q, q.step_a), (unsigned long long)bp(q, q.step_b), q.d_path, where(q.step_a).c_str(),
+                 where(q.step_b).c_str(), q.d_layout, q.d_layout / q.d_path);
         std::cerr << buf;
     }
 }
@@ -165,9 +220,11 @@ int main(int argc, char **argv) {
                 // (the profile speaks the dense indices of the graph as it is before the sort reorders it)
                 FlatGraph before;
                 std::vector<double> x;
-                if (args.stress_profile) before = graph.flatten();
-                sgd_sort_only(graph, sgd_params, (uint8_t)args.verbose, opt_y, &st, args.stress_profile ? &x : nullptr);   // gfasort.rs:250-252
+                const bool measure = args.stress_profile || args.diagnose;
+                if (measure) before = graph.flatten();
+                sgd_sort_only(graph, sgd_params, (uint8_t)args.verbose, opt_y, &st, measure ? &x : nullptr);   // gfasort.rs:250-252
                 if (args.stress_profile && !x.empty()) print_stress_profile(layout_pair_errors(before, 0, x, step_distance_ladder(before)));
+                if (args.diagnose && !x.empty()) print_diagnosis(before, graph.paths, 0, x, args.diagnose_ratio);
                 if (args.phased && args.verbose >= 2) {
                     uint64_t kb = 0, ke = sgd_params.iter_max + 1;         // reference streams picked: the whole schedule is theirs
                     if (st.bundle == 64) { gfs_sgd_params cp = sgd_params.to_c(); gfs_phase_window(&cp, &kb, &ke); }
@@ -186,6 +243,7 @@ int main(int argc, char **argv) {
                     FlatGraph f = graph.flatten();
                     print_stress_profile(layout_pair_errors(f, layout.dimensions, layout.coords, step_distance_ladder(f)));
                 }
+                if (args.diagnose && layout.num_nodes) print_diagnosis(graph.flatten(), graph.paths, layout.dimensions, layout.coords, args.diagnose_ratio);
             }
             if (args.verbose >= 1 && st.iterations)
                 std::cerr << "[gfasort_hip] " << st.term_updates << " term updates in " << st.iterations << " iterations on "

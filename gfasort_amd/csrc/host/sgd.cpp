@@ -348,6 +348,19 @@ std::vector<gfs_pair_error> layout_pair_errors(const BidirectedGraph &g, const s
     return layout_pair_errors(g.flatten(), 0, positions, zs);
 }
 
+LayoutDiagnosis layout_diagnosis(const FlatGraph &f, size_t dims, const std::vector<double> &positions, uint64_t z, double ratio,
+                                 uint64_t cap) {
+    const size_t want = dims ? f.node_len.size() * 2 * dims : f.node_len.size();
+    if (positions.size() != want) throw std::runtime_error("layout_diagnosis: positions do not match the graph");
+    LayoutDiagnosis d;
+    d.paths.resize(f.path_first_step.size() - 1);
+    d.pairs.resize(cap);
+    gfs_graph_view v = f.view();
+    check(gfs_diagnose(&v, dims, positions.data(), z, ratio, d.paths.data(), cap ? d.pairs.data() : nullptr, cap, &d.total));
+    d.pairs.resize(std::min<uint64_t>(cap, d.total));
+    return d;
+}
+
 std::vector<uint64_t> step_distance_ladder(const FlatGraph &f) {
     uint64_t longest = 0;
     for (size_t p = 0; p + 1 < f.path_first_step.size(); ++p) longest = std::max(longest, f.path_first_step[p + 1] - f.path_first_step[p]);

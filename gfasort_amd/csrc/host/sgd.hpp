@@ -5,6 +5,7 @@
 //   sgd_sort_only        src/ygs.rs:195           path_linear_sgd_layout  src/sgd.rs:773
 //   calculate_layout_stress  src/sgd.rs:1196
 //   layout_pair_errors   (no reference equivalent) the same per-pair error over ALL pairs at given step distances, on the device
+//   layout_diagnosis     src/bin/sgd_diagnostics.rs: per path reverse steps and errors, the stretched pairs — of given positions, on the device
 // Same names, argument meaning and empty-result behaviour as the Rust functions.
 #pragma once
 #include <cstdint>
@@ -112,6 +113,15 @@ std::vector<gfs_pair_error> layout_pair_errors(const FlatGraph &f, size_t dims, 
 std::vector<gfs_pair_error> layout_pair_errors(const BidirectedGraph &g, const Layout &layout, const std::vector<uint64_t> &zs);
 std::vector<gfs_pair_error> layout_pair_errors(const BidirectedGraph &g, const std::vector<double> &positions,
                                                const std::vector<uint64_t> &zs);
+// Which paths and pairs carry the error at step distance z (gfs_diagnose): one gfs_path_error per path, and the first `cap` of the
+// pairs (s, s + z) whose layout distance is more than `ratio` times their path distance, in step order, with their exact total.
+struct LayoutDiagnosis {
+    std::vector<gfs_path_error> paths;
+    std::vector<gfs_stretched_pair> pairs;
+    uint64_t total = 0;
+};
+LayoutDiagnosis layout_diagnosis(const FlatGraph &f, size_t dims, const std::vector<double> &positions, uint64_t z = 1,
+                                 double ratio = 10.0, uint64_t cap = 20);
 // z = 1, 2, 3, 4, 6, 8, 12, 16, ...: every 2^k and 3 * 2^(k-1) below the longest path's step count
 std::vector<uint64_t> step_distance_ladder(const FlatGraph &f);
 

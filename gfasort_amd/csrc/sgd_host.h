@@ -78,6 +78,23 @@ hipError_t pair_list_device(const uint4 *d_step_rec, uint64_t n_steps, const dou
 hipError_t sort_quality_device(const uint4 *d_step_rec, uint64_t n_steps, const uint32_t *d_order, const uint32_t *d_node_len,
                                const uint32_t *d_perm, uint64_t n_nodes, uint64_t *d_prefix, uint64_t *d_spos, uint64_t *d_partials,
                                uint64_t *d_out, uint64_t *total_len_out, hipStream_t st);
+// K7d / K7e / K7f, for one step distance z; a counted pair is stretched when (err + d_path) / d_path > ratio.  K7d and K7e cut the
+// step table into tiles of a constant number of steps: quality_tiles(n_steps) of them.
+uint64_t quality_tiles(uint64_t n_steps);
+// K7d: d_path_rec as the SGD kernels read it; d_head, d_tail: 5 * quality_tiles(n_steps) words each; d_out: 8 words per path
+// { steps, reverse_steps, pairs (u64), sum_rel_sq, max_rel_sq, sum_abs, sum_sq (f64 bits), stretched (u64) }.  Asynchronous.
+hipError_t path_errors_device(const uint4 *d_step_rec, uint64_t n_steps, const uint4 *d_path_rec, uint64_t n_paths, const double *d_x,
+                              uint64_t n_nodes, uint32_t dims, uint64_t z, double ratio, uint64_t *d_head, uint64_t *d_tail, uint64_t *d_out,
+                              hipStream_t st);
+// K7e: d_counts, d_offsets: quality_tiles(n_steps) + 1 words each; d_list (nullable: count only): room for min(cap, n_steps)
+// entries { step_a, step_b, path (u64), d_path, d_layout (f64) }, of which the first min(cap, *total_out) are written, in
+// ascending step_a.  Synchronous.
+hipError_t stretched_pairs_device(const uint4 *d_step_rec, uint64_t n_steps, const double *d_x, uint64_t n_nodes, uint32_t dims, uint64_t z,
+                                  double ratio, uint64_t *d_counts, uint64_t *d_offsets, void *d_list, uint64_t cap, uint64_t *total_out,
+                                  hipStream_t st);
+// K7f: d_slots, d_out: 3 * n_nodes words each; d_out by dense index { pairs, stretched (u64), max_rel_sq (f64 bits) }.  Asynchronous.
+hipError_t node_errors_device(const uint4 *d_step_rec, uint64_t n_steps, const double *d_x, const uint32_t *d_perm, uint64_t n_nodes,
+                              uint32_t dims, uint64_t z, double ratio, uint64_t *d_slots, uint64_t *d_out, hipStream_t st);
 
 // sgd_kernels_1d.hip: the multi-GPU replica merge
 hipError_t launch_merge_prepare(const double *x, const double *x_prev, float *buf, uint64_t n, hipStream_t st);

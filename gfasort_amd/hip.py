@@ -93,6 +93,12 @@ class SortQuality(C.Structure):
 PAIR_ERROR_DTYPE = np.dtype([("step_distance", "<u8"), ("pairs", "<u8"), ("sum_rel_sq", "<f8"), ("max_rel_sq", "<f8"),
                              ("sum_abs", "<f8"), ("sum_sq", "<f8")])
 
+# gfs_path_error, gfs_stretched_pair, gfs_node_error (K7d, K7e, K7f)
+PATH_ERROR_DTYPE = np.dtype([("steps", "<u8"), ("reverse_steps", "<u8"), ("pairs", "<u8"), ("sum_rel_sq", "<f8"), ("max_rel_sq", "<f8"),
+                             ("sum_abs", "<f8"), ("sum_sq", "<f8"), ("stretched", "<u8")])
+STRETCHED_PAIR_DTYPE = np.dtype([("step_a", "<u8"), ("step_b", "<u8"), ("path", "<u8"), ("d_path", "<f8"), ("d_layout", "<f8")])
+NODE_ERROR_DTYPE = np.dtype([("pairs", "<u8"), ("stretched", "<u8"), ("max_rel_sq", "<f8")])
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p)
 MERGE_RULES = {"anneal": 0, "sum": 1, "mean": 2, "touch": 3}
 
@@ -115,6 +121,7 @@ EXPORTS = [
     "gfs_rank_finish_buffer", "gfs_rank_finish_end", "gfs_rank_run",
     "gfs_ctx_debug_step_records", "gfs_ctx_debug_kshift", "gfs_phase_window", "gfs_ctx_phase_window",
     "gfs_ctx_pair_errors", "gfs_stress_sample_pairs", "gfs_ctx_stress_of_pairs", "gfs_ctx_sort_quality", "gfs_pair_errors",
+    "gfs_ctx_path_errors", "gfs_ctx_stretched_pairs", "gfs_ctx_node_errors", "gfs_diagnose",
 ]
 
 _lib = None
@@ -196,6 +203,10 @@ def lib():
         L.gfs_ctx_stress_of_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gfs_ctx_sort_quality.argtypes = [C.c_void_p, C.c_void_p]
         L.gfs_pair_errors.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.gfs_ctx_path_errors.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.gfs_ctx_stretched_pairs.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.gfs_ctx_node_errors.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.gfs_diagnose.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         _lib = L
     return _lib
 
@@ -332,6 +343,21 @@ def pair_errors(g, positions, zs, dims=0):
     out = np.zeros(zs.shape[0], dtype=PAIR_ERROR_DTYPE)
     check(lib().gfs_pair_errors(C.byref(v), C.c_uint64(dims), _ptr(x), _ptr(zs), C.c_uint64(zs.shape[0]), _ptr(out)))
     return out
+
+
+def diagnose(g, positions, z=1, ratio=10.0, cap=1024, dims=0):
+    """gfs_diagnose: per-path errors and the stretched pairs of a finished result at step distance z, measured on device 0.
+    Returns (PATH_ERROR_DTYPE array by path, STRETCHED_PAIR_DTYPE array of the first min(cap, total) stretched pairs, total)."""
+    v, keep = make_view(g)
+    x = np.ascontiguousarray(positions, dtype=np.float64)
+    if x.shape[0] != (g.n_nodes * 2 * dims if dims else g.n_nodes):
+        raise ValueError("positions length does not match the graph and dims")
+    paths = np.zeros(g.n_paths, dtype=PATH_ERROR_DTYPE)
+    pairs = np.zeros(int(cap), dtype=STRETCHED_PAIR_DTYPE)
+    total = C.c_uint64(0)
+    check(lib().gfs_diagnose(C.byref(v), C.c_uint64(dims), _ptr(x), C.c_uint64(z), C.c_double(ratio), _ptr(paths),
+                             _ptr(pairs) if cap else None, C.c_uint64(int(cap)), C.byref(total)))
+    return paths, pairs[:min(int(cap), int(total.value))], int(total.value)
 
 
 # ---- multi-device planning (host only) and the rank object -------------------------------------
@@ -591,6 +617,36 @@ class Context:
         mae = abs_sum / steps if steps else 0.0
         return dict(steps=steps, abs_err_sum=abs_sum, genomic_sum=gen, sq_err_sum=float(q.sq_err_sum), mse=mse,
                     rmse=float(np.sqrt(mse)), mae=mae, relative_error=(mae / (gen / steps)) if gen > 0 else 0.0)
+
+    def path_errors(self, z=1, ratio=10.0, stream=None):
+        """gfs_ctx_path_errors: per path, its steps, reverse steps, K7a's sums over its pairs (s, s + z) and how many of them
+        are stretched (d_layout / d_path > ratio).  PATH_ERROR_DTYPE array, one row per path."""
+        out = np.zeros(self.graph.n_paths, dtype=PATH_ERROR_DTYPE)
+        check(lib().gfs_ctx_path_errors(self._h, C.c_uint64(z), C.c_double(ratio), _ptr(out), C.c_uint64(out.shape[0]),
+                                        C.c_void_p(stream or 0)))
+        return out
+
+    def stretched_pairs(self, z=1, ratio=10.0, cap=1024, out=None, stream=None):
+        """gfs_ctx_stretched_pairs: (the first min(cap, total) stretched pairs in ascending step_a as a STRETCHED_PAIR_DTYPE
+        array, total).  out: a caller's array of at least cap entries to write into (entries beyond the list stay as they are)."""
+        cap = int(cap)
+        if out is None and cap:
+            out = np.zeros(cap, dtype=STRETCHED_PAIR_DTYPE)
+        if cap and (out.dtype != STRETCHED_PAIR_DTYPE or out.shape[0] < cap or not out.flags.c_contiguous):
+            raise ValueError("out must be a contiguous STRETCHED_PAIR_DTYPE array of at least cap entries")
+        total = C.c_uint64(0)
+        check(lib().gfs_ctx_stretched_pairs(self._h, C.c_uint64(z), C.c_double(ratio), _ptr(out) if cap else None, C.c_uint64(cap),
+                                            C.byref(total), C.c_void_p(stream or 0)))
+        n = min(cap, int(total.value))
+        return (out[:n] if cap else np.zeros(0, dtype=STRETCHED_PAIR_DTYPE)), int(total.value)
+
+    def node_errors(self, z=1, ratio=10.0, stream=None):
+        """gfs_ctx_node_errors: per dense node, the counted pairs (s, s + z) touching it, the stretched ones among them and the
+        largest rel_sq.  NODE_ERROR_DTYPE array, one row per node."""
+        out = np.zeros(self.graph.n_nodes, dtype=NODE_ERROR_DTYPE)
+        check(lib().gfs_ctx_node_errors(self._h, C.c_uint64(z), C.c_double(ratio), _ptr(out), C.c_uint64(out.shape[0]),
+                                        C.c_void_p(stream or 0)))
+        return out
 
     # ---- test hooks ----
     def step_records(self):

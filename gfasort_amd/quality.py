@@ -183,6 +183,21 @@ def device_profile(ctx, zs=None):
     return profile_rows(ctx.pair_errors(np.asarray(zs, dtype=np.uint64)))
 
 
+def device_diagnosis(ctx, z=1, ratio=10.0, worst=10):
+    """Which paths carry the error of the positions resident in `ctx` (a hip.Context) at step distance z: dict(rows, worst).
+    rows: per path dict(path, steps, reverse_steps, pairs, rms_rel, max_rel, stretched), rms_rel = sqrt(sum_rel_sq / pairs);
+    worst: the indices of the `worst` paths with the largest rms_rel, largest first (ties: lower index first)."""
+    pe = ctx.path_errors(z, ratio)
+    rows = []
+    for p, r in enumerate(pe):
+        n = int(r["pairs"])
+        rows.append(dict(path=p, steps=int(r["steps"]), reverse_steps=int(r["reverse_steps"]), pairs=n,
+                         rms_rel=float(np.sqrt(r["sum_rel_sq"] / n)) if n else 0.0, max_rel=float(np.sqrt(r["max_rel_sq"])),
+                         stretched=int(r["stretched"])))
+    order = sorted(range(len(rows)), key=lambda p: (-rows[p]["rms_rel"], p))
+    return dict(rows=rows, worst=order[:worst])
+
+
 # ---- rank agreement ------------------------------------------------------------------------------
 def ranks_of(order):
     order = np.asarray(order, dtype=np.int64)

@@ -316,6 +316,55 @@ int gfs_ctx_sort_quality(gfs_ctx *ctx, gfs_sort_quality *out);
 int gfs_pair_errors(const gfs_graph_view *g, uint64_t dims, const double *positions, const uint64_t *zs, uint64_t n_z,
                     gfs_pair_error *out);
 
+/* ---- where the error sits (K7d, K7e, K7f): per path, per pair, per node, at ONE step distance z ----
+ * The pairs, the per-pair formula and its skips are those above.  With d_layout = err + d_path, a counted pair is STRETCHED when
+ * d_layout / d_path > ratio (one double division, one comparison); the reference's diagnostic binary (src/bin/sgd_diagnostics.rs)
+ * lists the stretched pairs at z = 1, ratio = 10 and counts each path's reverse steps.  Two departures from that binary:
+ *   - it measures positions that are prefix sums of node lengths in node-id order; these entries measure whatever the context
+ *     holds — after gfs_ctx_init_positions on a graph whose nodes are in id order that is the same thing;
+ *   - it gives a node it cannot find position 0; here the pair is skipped, as everywhere in K7.
+ * Same rules as above: nothing but the outputs is written, every figure is a function of graph, z, ratio and positions alone
+ * (the step table is cut into tiles of a constant number of steps, a tile is reduced by a fixed tree, a path's tiles are
+ * combined in tile order; per node only integer sums and a maximum are accumulated, which no order of arrival changes).
+ * GFS_E_ARG (before any device call) for a null pointer, z == 0, a ratio that is NaN or negative, or a length that does not match
+ * the context; GFS_E_STATE on a context without positions.  A z no path is long enough for gives zero figures and *total = 0.
+ * All entries run on hip_stream and synchronise before returning.  On a rank's context (gfs_rank_ctx): the rank's shard, in the
+ * shard's path numbering. */
+typedef struct gfs_path_error {
+    uint64_t steps;                   /* steps of the path                                                          */
+    uint64_t reverse_steps;           /* of which reverse                                                           */
+    uint64_t pairs;                   /* pairs (s, s + z) of the path not skipped                                   */
+    double   sum_rel_sq;              /* as gfs_pair_error, over this path's pairs                                  */
+    double   max_rel_sq;              /* exact                                                                      */
+    double   sum_abs;
+    double   sum_sq;
+    uint64_t stretched;               /* counted pairs with d_layout / d_path > ratio                               */
+} gfs_path_error;
+
+typedef struct gfs_stretched_pair {
+    uint64_t step_a, step_b;          /* step_b = step_a + z                                                        */
+    uint64_t path;
+    double   d_path, d_layout;
+} gfs_stretched_pair;
+
+typedef struct gfs_node_error {
+    uint64_t pairs;                   /* counted pairs with the node at either end; both ends on it: counted once   */
+    uint64_t stretched;               /* of which stretched                                                         */
+    double   max_rel_sq;              /* largest rel_sq of those pairs, exact                                       */
+} gfs_node_error;
+
+/* out[n_paths], by path index; n_paths must be the context's */
+int gfs_ctx_path_errors(gfs_ctx *ctx, uint64_t z, double ratio, gfs_path_error *out, uint64_t n_paths, void *hip_stream);
+/* the stretched pairs in ascending step_a: *total receives their exact number, out[0 .. min(cap, *total)) the first of them;
+ * entries beyond are left untouched.  out may be NULL when cap = 0.  The listed prefix is the same on every call. */
+int gfs_ctx_stretched_pairs(gfs_ctx *ctx, uint64_t z, double ratio, gfs_stretched_pair *out, uint64_t cap, uint64_t *total,
+                            void *hip_stream);
+/* out[n_nodes], by dense node index; n_nodes must be the context's */
+int gfs_ctx_node_errors(gfs_ctx *ctx, uint64_t z, double ratio, gfs_node_error *out, uint64_t n_nodes, void *hip_stream);
+/* one-shot, as gfs_pair_errors: paths_out[g->n_paths], pairs_out[cap] (NULL when cap = 0), *total */
+int gfs_diagnose(const gfs_graph_view *g, uint64_t dims, const double *positions, uint64_t z, double ratio,
+                 gfs_path_error *paths_out, gfs_stretched_pair *pairs_out, uint64_t cap, uint64_t *total);
+
 /* ---- multi-device runs (no reference equivalent: the reference is one process, src/sgd.rs:413-593) ----
  * Paths are sharded over `world` ranks, one rank per GPU (one process per GPU, or one host thread per GPU); every rank
  * performs its share of an iteration's term updates on its own replica of the positions; after every window of
