@@ -3,6 +3,8 @@
 // that stand where path_linear_sgd / path_linear_sgd_layout stand in the reference.
 #include "../../include/gfasort_hip.h"
 #include "sgd_kernel_common.h"
+#include "sgd_batch.h"
+#include "batch_plan.h"
 #include "sgd_host.h"
 
 #include <algorithm>
@@ -1614,6 +1616,249 @@ int gfs_path_linear_sgd_layout(const gfs_graph_view *g, const gfs_layout_params 
     if (!p) return fail(GFS_E_ARG, "params is null");
     if (p->dimensions < 1 || p->dimensions > GFS_MAX_DIMS) return fail(GFS_E_UNSUPPORTED, "dimensions must be 1..8");
     return one_shot(g, &p->sgd, (int)p->dimensions, cfg, etas, zetas, 0, coords_inout, stats);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// batches: many configured contexts in one persistent launch (K1f / K2f, sgd_kernels_batch.hip)
+// ---------------------------------------------------------------------------------------------
+struct BatchLaunch {
+    bool lds_tables = false;
+    size_t lds_bytes = 0;              // the largest among its items
+    uint64_t first = 0, count = 0;     // its items: run[first .. first + count)
+    uint64_t blocks = 0, block_offset = 0;   // workgroups; where its part of the block table starts
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+};
+struct gfs_batch {
+    int device = 0, dims = 0;
+    uint32_t block = 256;
+    std::vector<gfs_ctx *> ctxs;       // as given
+    std::vector<uint64_t> run;         // indices into ctxs of the items with something to do, in launch order
+    std::vector<BatchLaunch> launches;
+    std::vector<uint64_t> pool_offset; // by position in run: first word of the item's counters in d_pool
+    std::vector<uint64_t> item_blocks, item_iters;   // by position in run: workgroups and iter_max + 1 as planned at create,
+    std::vector<size_t> item_lds;                    // and lds_bytes (0 without LDS tables)
+    uint64_t pool_words = 0, total_blocks = 0;
+    std::vector<gfs::BatchItem> h_items; std::vector<uint32_t> h_block_item;    // staging of the two tables
+    gfs::BatchItem *d_items = nullptr; uint32_t *d_block_item = nullptr; uint32_t *d_pool = nullptr;
+    uint64_t launches_done = 0, blocks_done = 0;
+    double kernel_ms = 0.0, total_ms = 0.0;
+};
+
+static bool batch_item_idle(const gfs_ctx *c) { return !c->valid_paths || c->n_nodes == 0; }
+
+extern "C" {
+
+int gfs_batch_plan(const uint64_t *blocks_of_item, uint64_t n, uint64_t max_blocks, uint32_t *launch_of_item, uint32_t *n_launches) {
+    if (!n_launches || (n && (!blocks_of_item || !launch_of_item))) return fail(GFS_E_ARG, "null argument");
+    const uint64_t bad = gfs::batch_plan(blocks_of_item, n, max_blocks, launch_of_item, n_launches);
+    if (bad < n)
+        return fail(GFS_E_UNSUPPORTED, "batch item " + std::to_string(bad) + ": its " + std::to_string(blocks_of_item[bad]) +
+                                           " workgroups exceed the " + std::to_string(max_blocks) + " of one launch");
+    return GFS_OK;
+}
+
+void gfs_batch_destroy(gfs_batch *b) {
+    if (!b) return;
+    (void)hipSetDevice(b->device);
+    for (auto &l : b->launches) { if (l.e0) (void)hipEventDestroy(l.e0); if (l.e1) (void)hipEventDestroy(l.e1); }
+    if (b->d_items) (void)hipFree(b->d_items);
+    if (b->d_block_item) (void)hipFree(b->d_block_item);
+    if (b->d_pool) (void)hipFree(b->d_pool);
+    delete b;
+}
+
+int gfs_batch_create(gfs_ctx *const *ctxs, uint64_t n, const gfs_batch_config *cfg, gfs_batch **out) {
+    if (!out) return fail(GFS_E_ARG, "out is null");
+    *out = nullptr;
+    if (!ctxs || n == 0) return fail(GFS_E_ARG, "a batch needs at least one context");
+    for (uint64_t i = 0; i < n; ++i) if (!ctxs[i]) return fail(GFS_E_ARG, "batch item " + std::to_string(i) + " is null");
+    {
+        std::vector<gfs_ctx *> sorted(ctxs, ctxs + n);
+        std::sort(sorted.begin(), sorted.end());
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end()) {
+            const uint64_t first = (uint64_t)(std::find(ctxs, ctxs + n, *dup) - ctxs);
+            const uint64_t second = (uint64_t)(std::find(ctxs + first + 1, ctxs + n, *dup) - ctxs);
+            return fail(GFS_E_ARG, "batch item " + std::to_string(second) + " is the same context as item " + std::to_string(first));
+        }
+    }
+    for (uint64_t i = 0; i < n; ++i)
+        if (!ctxs[i]->configured) return fail(GFS_E_STATE, "batch item " + std::to_string(i) + ": context not set up");
+    gfs_batch *b = new (std::nothrow) gfs_batch();
+    if (!b) return fail(GFS_E_NOMEM, "out of memory");
+    auto refuse = [&](int code, uint64_t i, const std::string &why) {
+        delete b;
+        return fail(code, "batch item " + std::to_string(i) + ": " + why);
+    };
+    b->ctxs.assign(ctxs, ctxs + n);
+    b->device = ctxs[0]->device; b->dims = ctxs[0]->dims;
+    bool have_block = false;
+    std::vector<uint64_t> with_lds, without_lds;
+    for (uint64_t i = 0; i < n; ++i) {
+        const gfs_ctx *c = ctxs[i];
+        if (c->device != b->device) return refuse(GFS_E_UNSUPPORTED, i, "on device " + std::to_string(c->device) + ", item 0 on device " + std::to_string(b->device));
+        if (c->dims != b->dims)
+            return refuse(GFS_E_UNSUPPORTED, i, "dims=" + std::to_string(c->dims) + ", item 0 has dims=" + std::to_string(b->dims) +
+                                                    " (a batch is all 1D sorts or all layouts of one dimension)");
+        if (batch_item_idle(c)) continue;                                  // counted, not run
+        if (!gfs::batch_fused_kernel(c->dims, true))
+            return refuse(GFS_E_UNSUPPORTED, i, "no batch kernel is built for dims=" + std::to_string(c->dims) + " (1D sorts, layouts of 2 and 3 dimensions)");
+        if (c->bundle != 1 || c->phased || !c->plan.fused || !c->plan.pooled || c->cfg.trace_per_stream || !c->d_its_all)
+            return refuse(GFS_E_UNSUPPORTED, i, "its plan is not the pooled fused reference-stream kernel (bundle=" + std::to_string(c->bundle) +
+                                                    " phased=" + std::to_string(c->phased) + " fused=" + std::to_string(c->plan.fused != nullptr) +
+                                                    " trace=" + std::to_string(c->cfg.trace_per_stream != 0) + ")");
+        if (c->params.iter_max + 1 > 4096 || c->params.iter_max + 1 == 0)
+            return refuse(GFS_E_UNSUPPORTED, i, "iter_max + 1 exceeds the 4096 iterations of one fused launch");
+        if (have_block && c->block != b->block)
+            return refuse(GFS_E_UNSUPPORTED, i, "block size " + std::to_string(c->block) + ", earlier items have " + std::to_string(b->block));
+        b->block = c->block; have_block = true;
+        (c->lds_tables ? with_lds : without_lds).push_back(i);
+    }
+    // ---- device from here on ----
+    auto bail = [&](const char *what, hipError_t e) {
+        const std::string m = std::string(what) + ": " + hipGetErrorString(e);
+        gfs_batch_destroy(b);
+        return fail(GFS_E_HIP, m);
+    };
+    hipError_t e = hipSetDevice(b->device);
+    if (e != hipSuccess) return bail("hipSetDevice", e);
+    for (const std::vector<uint64_t> *group : {&with_lds, &without_lds}) {
+        if (group->empty()) continue;
+        const bool lds_tables = group == &with_lds;
+        size_t lds_max = 0;
+        std::vector<uint64_t> blocks;
+        for (uint64_t i : *group) {
+            lds_max = std::max(lds_max, ctxs[i]->lds_bytes);
+            blocks.push_back((ctxs[i]->n_streams + b->block - 1) / b->block);
+        }
+        // Every workgroup of a launch is resident at once: a graph whose workgroups start late would walk its early, large-eta
+        // iterations after the others have finished theirs (plan_launches has the measurement for the team kernels).
+        uint64_t max_blocks = cfg ? cfg->max_blocks_per_launch : 0;
+        if (!max_blocks) {
+            int per_cu = 0;
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gfs::batch_fused_kernel(b->dims, lds_tables), (int)b->block, lds_max);
+            if (e != hipSuccess) return bail("hipOccupancyMaxActiveBlocksPerMultiprocessor", e);
+            max_blocks = (uint64_t)std::max(per_cu, 0) * (uint64_t)ctxs[0]->cu_count;
+        }
+        max_blocks = std::min<uint64_t>(max_blocks, 0x7FFFFFFFull);        // a grid's x dimension
+        std::vector<uint32_t> launch_of(blocks.size());
+        uint32_t n_launches = 0;
+        const uint64_t bad = gfs::batch_plan(blocks.data(), blocks.size(), max_blocks, launch_of.data(), &n_launches);
+        if (bad < blocks.size()) {
+            const uint64_t i = (*group)[bad];
+            const std::string why = "its " + std::to_string(blocks[bad]) + " workgroups exceed the " + std::to_string(max_blocks) + " one launch may hold";
+            gfs_batch_destroy(b);
+            return fail(GFS_E_UNSUPPORTED, "batch item " + std::to_string(i) + ": " + why);
+        }
+        const size_t base = b->launches.size();
+        b->launches.resize(base + n_launches);
+        for (size_t k = 0; k < blocks.size(); ++k) {
+            BatchLaunch &l = b->launches[base + launch_of[k]];
+            if (l.count == 0) { l.first = b->run.size(); l.lds_tables = lds_tables; l.block_offset = b->total_blocks; }
+            l.count++; l.blocks += blocks[k];
+            if (lds_tables) l.lds_bytes = std::max(l.lds_bytes, ctxs[(*group)[k]]->lds_bytes);
+            b->run.push_back((*group)[k]);
+            b->pool_offset.push_back(b->pool_words);
+            b->item_blocks.push_back(blocks[k]);
+            b->item_iters.push_back(ctxs[(*group)[k]]->params.iter_max + 1);
+            b->item_lds.push_back(lds_tables ? ctxs[(*group)[k]]->lds_bytes : 0);
+            b->pool_words += gfs::pool_bytes(ctxs[(*group)[k]]->params.iter_max + 1) / sizeof(uint32_t);
+            b->total_blocks += blocks[k];
+        }
+    }
+    if (!b->run.empty()) {
+        b->h_items.resize(b->run.size());
+        b->h_block_item.resize(b->total_blocks);
+        if ((e = hipMalloc(&b->d_items, b->run.size() * sizeof(gfs::BatchItem))) != hipSuccess) return bail("hipMalloc items", e);
+        if ((e = hipMalloc(&b->d_block_item, b->total_blocks * sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc block table", e);
+        if ((e = hipMalloc(&b->d_pool, b->pool_words * sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc pools", e);
+        for (auto &l : b->launches) {
+            if ((e = hipEventCreate(&l.e0)) != hipSuccess || (e = hipEventCreate(&l.e1)) != hipSuccess) return bail("hipEventCreate", e);
+        }
+    }
+    *out = b;
+    return GFS_OK;
+}
+
+int gfs_batch_run(gfs_batch *b, void *hip_stream) {
+    if (!b) return fail(GFS_E_ARG, "batch is null");
+    for (size_t i = 0; i < b->ctxs.size(); ++i)
+        if (!b->ctxs[i]->configured) return fail(GFS_E_STATE, "batch item " + std::to_string(i) + ": context not set up");
+    if (b->run.empty()) return GFS_NOTHING_TO_DO;
+    // the launches, the block table and the pools were sized at create: a context set up again since then no longer fits them
+    for (size_t r = 0; r < b->run.size(); ++r) {
+        const gfs_ctx *c = b->ctxs[b->run[r]];
+        const bool same_plan = c->dims == b->dims && c->block == b->block && c->bundle == 1 && !c->phased && c->plan.fused && c->plan.pooled &&
+                               !c->cfg.trace_per_stream && c->d_its_all && !batch_item_idle(c) &&
+                               (c->lds_tables ? c->lds_bytes : 0) == b->item_lds[r];
+        if (!same_plan || (c->n_streams + b->block - 1) / b->block != b->item_blocks[r] || c->params.iter_max + 1 != b->item_iters[r])
+            return fail(GFS_E_STATE, "batch item " + std::to_string(b->run[r]) + ": set up again since the batch was created (" +
+                                         std::to_string(c->n_streams) + " streams, iter_max " + std::to_string(c->params.iter_max) + ")");
+    }
+    auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    // the two tables, from the contexts as they are now (positions may have been bound anew since the last run)
+    for (const BatchLaunch &l : b->launches) {
+        uint64_t block = 0;
+        for (uint64_t r = l.first; r < l.first + l.count; ++r) {
+            const gfs_ctx *c = b->ctxs[b->run[r]];
+            gfs::BatchItem &it = b->h_items[r];
+            it = gfs::BatchItem{};
+            fill_kargs(c, it.a);
+            iter_consts(c, 0, it.a.it);
+            it.its = c->d_its_all;
+            it.pool = b->d_pool + b->pool_offset[r];
+            it.n_iters = (uint32_t)(c->params.iter_max + 1);
+            it.first_block = (uint32_t)block;
+            const uint64_t nb = b->item_blocks[r];
+            for (uint64_t k = 0; k < nb; ++k) b->h_block_item[l.block_offset + block + k] = (uint32_t)r;
+            block += nb;
+        }
+    }
+    HIPCHK(hipMemcpyAsync(b->d_items, b->h_items.data(), b->h_items.size() * sizeof(gfs::BatchItem), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_block_item, b->h_block_item.data(), b->h_block_item.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    // work pools (sgd_kernel_common.h pool_walk): every item's counters, zeroed per run
+    HIPCHK(hipMemsetAsync(b->d_pool, 0, b->pool_words * sizeof(uint32_t), st));
+    for (BatchLaunch &l : b->launches) {
+        const gfs::BatchItem *items = b->d_items;
+        const uint32_t *block_item = b->d_block_item + l.block_offset;
+        void *args[] = {&items, &block_item};
+        HIPCHK(hipEventRecord(l.e0, st));                  // (the event pair brackets the kernel alone)
+        hipError_t e = hipLaunchKernel(gfs::batch_fused_kernel(b->dims, l.lds_tables), dim3((unsigned)l.blocks), dim3(b->block), args, l.lds_bytes, st);
+        if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch kernel launch: ") + hipGetErrorString(e));
+        HIPCHK(hipEventRecord(l.e1, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    for (BatchLaunch &l : b->launches) {
+        float t = 0.f;
+        if (hipEventElapsedTime(&t, l.e0, l.e1) == hipSuccess) b->kernel_ms += t;
+        b->launches_done++; b->blocks_done += l.blocks;
+    }
+    for (uint64_t r : b->run) {                            // each context as if it had been run alone (its kernel_ms apart)
+        gfs_ctx *c = b->ctxs[r];
+        c->iterations += c->params.iter_max + 1;
+        c->launches++;
+    }
+    b->total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return GFS_OK;
+}
+
+int gfs_batch_get_stats(gfs_batch *b, gfs_batch_stats *out) {
+    if (!b || !out) return fail(GFS_E_ARG, "null argument");
+    std::memset(out, 0, sizeof *out);
+    out->items = b->ctxs.size(); out->items_run = b->run.size();
+    out->launches = b->launches_done; out->blocks = b->blocks_done;
+    out->kernel_ms = b->kernel_ms; out->total_ms = b->total_ms;
+    for (uint64_t r : b->run) {
+        gfs_stats st;
+        int rc = gfs_ctx_stats(b->ctxs[r], &st);
+        if (rc) return rc;
+        out->term_updates += st.term_updates; out->attempts += st.attempts;
+    }
+    return GFS_OK;
 }
 
 }  // extern "C"

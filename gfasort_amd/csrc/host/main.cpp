@@ -19,6 +19,8 @@ using namespace gfasort;
 
 struct Args {
     std::string input, output, pipeline = "sYgs", layout_out;
+    std::string layout_option;                     // the last of --dimensions / --layout-out / --layout-iter given: -p L only
+    std::string batch_list;                        // --batch: a file of in.gfa<TAB>out.gfa lines, all sorted in one invocation
     size_t iter_max = 100, threads = 1, dimensions = 2, layout_iter = 30;
     unsigned verbose = 1;
     uint64_t streams = 0; uint32_t flags = 0;      // HIP launch shape (extra, not in the reference)
@@ -53,6 +55,10 @@ static void usage() {
         "                                       its steps, forward and reverse steps, counted pairs, rms relative error and stretched\n"
         "                                       pairs, then the first 20 stretched pairs — those whose layout distance is more than\n"
         "                                       R (default 10) times their path distance; computed on the device)\n"
+        "       gfasort_hip --batch LIST -p Y [the options above, except -i, -o and those of -p L]\n"
+        "                   (LIST: one in.gfa<TAB>out.gfa per line; every graph is sorted as a -i/-o run sorts it, the small ones —\n"
+        "                    those that run reference streams — together in one persistent launch that fills the device, the\n"
+        "                    others alone)\n"
         "Pipeline characters: Y = path-guided SGD sort, L = nD layout (HIP engine).\n"
         "g, s, S, u exist in the reference but are not part of this build.\n";
 }
@@ -64,13 +70,14 @@ static bool parse_args(int argc, char **argv, Args &a) {
         const char *v;
         if (f == "-i" || f == "--input") { if (!(v = need(i))) return false; a.input = v; }
         else if (f == "-o" || f == "--output") { if (!(v = need(i))) return false; a.output = v; }
+        else if (f == "--batch") { if (!(v = need(i))) return false; a.batch_list = v; }
         else if (f == "-p" || f == "--pipeline") { if (!(v = need(i))) return false; a.pipeline = v; }
         else if (f == "--iter-max") { if (!(v = need(i))) return false; a.iter_max = std::stoull(v); }
         else if (f == "-t" || f == "--threads") { if (!(v = need(i))) return false; a.threads = std::stoull(v); }
         else if (f == "-v" || f == "--verbose") { if (!(v = need(i))) return false; a.verbose = (unsigned)std::stoul(v); }
-        else if (f == "--dimensions") { if (!(v = need(i))) return false; a.dimensions = std::stoull(v); }
-        else if (f == "--layout-out") { if (!(v = need(i))) return false; a.layout_out = v; }
-        else if (f == "--layout-iter") { if (!(v = need(i))) return false; a.layout_iter = std::stoull(v); }
+        else if (f == "--dimensions") { if (!(v = need(i))) return false; a.dimensions = std::stoull(v); a.layout_option = f; }
+        else if (f == "--layout-out") { if (!(v = need(i))) return false; a.layout_out = v; a.layout_option = f; }
+        else if (f == "--layout-iter") { if (!(v = need(i))) return false; a.layout_iter = std::stoull(v); a.layout_option = f; }
         else if (f == "--io-threads") { if (!(v = need(i))) return false; set_io_threads(std::stoull(v)); }
         else if (f == "--streams") { if (!(v = need(i))) return false; a.streams = std::stoull(v); }
         else if (f == "--bundle") { if (!(v = need(i))) return false; a.bundle = std::string(v) == "auto" ? 0u : (unsigned)std::stoul(v); }
@@ -87,6 +94,12 @@ static bool parse_args(int argc, char **argv, Args &a) {
         std::cerr << "error: --phased-sampler switches between the reference sampler and bundles of 64: not with --reference-sampler or --bundle "
                   << a.bundle << "\n";
         return false;
+    }
+    if (!a.batch_list.empty()) {
+        if (!a.input.empty() || !a.output.empty()) { std::cerr << "error: --batch takes its inputs and outputs from LIST: not with -i / -o\n"; return false; }
+        if (!a.layout_option.empty()) { std::cerr << "error: --batch sorts (-p Y): " << a.layout_option << " belongs to -p L\n"; return false; }
+        if (a.pipeline != "Y") { std::cerr << "error: --batch sorts many graphs in one launch: it needs -p Y exactly, not -p " << a.pipeline << "\n"; return false; }
+        return true;
     }
     if (a.input.empty() || a.output.empty()) { std::cerr << "error: -i and -o are required\n"; return false; }
     return true;
@@ -168,10 +181,88 @@ static void print_diagnosis(const FlatGraph &f, const std::vector<BiPath> &paths
     }
 }
 
+static void print_run_stats(const gfs_stats &st) {
+    std::cerr << "[gfasort_hip] " << st.term_updates << " term updates in " << st.iterations << " iterations on "
+              << st.n_streams << " streams (bundle " << st.bundle << "); kernels " << st.kernel_ms << " ms ("
+              << (st.kernel_ms > 0 ? (double)st.term_updates / st.kernel_ms / 1e6 : 0.0) << " G updates/s), call "
+              << st.total_ms << " ms\n";
+}
+
+// --batch LIST -p Y: every graph of the list gets its own YgsParams::from_graph, as a -i/-o run gives it; those that run reference
+// streams are sorted in one batch, the others alone; every output is what the single run writes.
+static int run_batch(const Args &args) {
+    std::thread warm([] { (void)gfs_warmup(0); });
+    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{warm};
+    std::vector<std::pair<std::string, std::string>> files;
+    {
+        std::ifstream list(args.batch_list);
+        if (!list) { std::cerr << "Error reading file: " << args.batch_list << ": " << std::strerror(errno) << "\n"; return 1; }
+        std::string line;
+        size_t n = 0;
+        while (std::getline(list, line)) {
+            ++n;
+            if (!line.empty() && line.back() == '\r') line.pop_back();
+            if (line.empty()) continue;
+            const size_t tab = line.find('\t');
+            if (tab == std::string::npos || tab == 0 || tab + 1 == line.size() || line.find('\t', tab + 1) != std::string::npos) {
+                std::cerr << "Error: " << args.batch_list << " line " << n << ": expected in.gfa<TAB>out.gfa\n";
+                return 1;
+            }
+            files.emplace_back(line.substr(0, tab), line.substr(tab + 1));
+        }
+    }
+    if (files.empty()) { std::cerr << "Error: " << args.batch_list << " lists no graph\n"; return 1; }
+    std::vector<BidirectedGraph> graphs(files.size());
+    std::vector<BatchSortItem> items(files.size());
+    for (size_t i = 0; i < files.size(); ++i) {
+        if (args.verbose >= 1) std::cerr << "[gfasort] reading " << files[i].first << "\n";
+        try { graphs[i] = parse_gfa(read_file(files[i].first)); }
+        catch (const std::exception &e) { std::cerr << "Error reading " << files[i].first << ": " << e.what() << "\n"; return 1; }
+        items[i].graph = &graphs[i];
+        items[i].params = YgsParams::from_graph(graphs[i], (uint8_t)args.verbose, args.threads).path_sgd;
+        items[i].params.iter_max = args.iter_max;
+    }
+    HipOptions opt; opt.cfg.n_streams = args.streams; opt.cfg.flags = args.flags | GFS_F_BUNDLE(args.bundle);
+    if (args.phased) opt.cfg.flags |= GFS_F_PHASED;
+    gfs_batch_stats bs{};
+    try {
+        bs = sgd_sort_batch(items, (uint8_t)args.verbose, opt, args.stress_profile || args.diagnose);
+        for (size_t i = 0; i < items.size(); ++i) {
+            const BatchSortItem &it = items[i];
+            if (args.verbose >= 1) {
+                std::cerr << "[gfasort_hip] " << files[i].first << ": " << graphs[i].node_count() << " nodes, "
+                          << (it.batched ? "in the batch" : it.stats.iterations ? "alone" : "nothing to do") << "\n";
+                if (it.stats.iterations) print_run_stats(it.stats);
+            }
+            if (args.stress_profile && !it.positions.empty()) print_stress_profile(layout_pair_errors(it.before, 0, it.positions, step_distance_ladder(it.before)));
+            if (args.diagnose && !it.positions.empty()) print_diagnosis(it.before, graphs[i].paths, 0, it.positions, args.diagnose_ratio);
+        }
+        if (args.verbose >= 1)
+            std::cerr << "[gfasort_hip] batch: " << bs.items_run << " graphs in " << bs.launches << (bs.launches == 1 ? " launch" : " launches")
+                      << " of " << bs.blocks << " workgroups; kernels " << bs.kernel_ms << " ms ("
+                      << (bs.kernel_ms > 0 ? (double)bs.term_updates / bs.kernel_ms / 1e6 : 0.0) << " G updates/s), run " << bs.total_ms << " ms\n";
+    } catch (const std::exception &e) {
+        std::cerr << "Error: " << e.what() << "\n";
+        return 1;
+    }
+    for (size_t i = 0; i < files.size(); ++i) {
+        if (args.verbose >= 1) std::cerr << "[gfasort] writing " << files[i].second << "\n";
+        std::ofstream f(files[i].second, std::ios::binary);
+        if (!f) { std::cerr << "Error writing output file: " << std::strerror(errno) << "\n"; return 1; }
+        graphs[i].write_gfa(f);
+        f.close();                                                                    // (a full disk shows here at the latest)
+        if (!f) { std::cerr << "Error writing output file " << files[i].second << ": " << std::strerror(errno) << "\n"; return 1; }
+    }
+    if (warm.joinable()) warm.join();
+    std::cerr.flush(); std::cout.flush();
+    std::_Exit(0);
+}
+
 int main(int argc, char **argv) {
     Args args;
     if (!parse_args(argc, argv, args)) { usage(); return 2; }
     if (validate_pipeline(args.pipeline)) return 1;
+    if (!args.batch_list.empty()) return run_batch(args);
     auto t_start = std::chrono::steady_clock::now();
     auto since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
     double t_read = 0, t_parse = 0, t_steps = 0, t_write = 0;
@@ -245,11 +336,7 @@ int main(int argc, char **argv) {
                 }
                 if (args.diagnose && layout.num_nodes) print_diagnosis(graph.flatten(), graph.paths, layout.dimensions, layout.coords, args.diagnose_ratio);
             }
-            if (args.verbose >= 1 && st.iterations)
-                std::cerr << "[gfasort_hip] " << st.term_updates << " term updates in " << st.iterations << " iterations on "
-                          << st.n_streams << " streams (bundle " << st.bundle << "); kernels " << st.kernel_ms << " ms ("
-                          << (st.kernel_ms > 0 ? (double)st.term_updates / st.kernel_ms / 1e6 : 0.0) << " G updates/s), call "
-                          << st.total_ms << " ms\n";
+            if (args.verbose >= 1 && st.iterations) print_run_stats(st);
         }
     } catch (const std::exception &e) {
         std::cerr << "Error: " << e.what() << "\n";

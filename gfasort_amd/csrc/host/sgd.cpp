@@ -237,6 +237,79 @@ void sgd_sort_only(BidirectedGraph &g, const PathSGDParams &p, uint8_t verbose, 
     if (verbose >= 2) std::cerr << "[path_sgd] Complete\n";
 }
 
+gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbose, const HipOptions &opt, bool keep_positions) {
+    struct Slot { gfs_ctx *ctx = nullptr; FlatGraph f; };
+    std::vector<Slot> slots(items.size());
+    struct Cleanup {
+        std::vector<Slot> &s; gfs_batch *b = nullptr;
+        ~Cleanup() { if (b) gfs_batch_destroy(b); for (auto &x : s) if (x.ctx) gfs_ctx_destroy(x.ctx); }
+    } cleanup{slots};
+    gfs_batch_stats bs{};
+    // run, read back, reorder the graph, free the context
+    auto finish = [&](size_t i, bool alone) {
+        BatchSortItem &it = items[i];
+        gfs_ctx *c = slots[i].ctx;
+        if (alone) check(gfs_ctx_run(c, nullptr));
+        const FlatGraph &f = slots[i].f;
+        std::vector<double> x(f.node_len.size());
+        std::vector<uint64_t> order(x.size());
+        check(gfs_ctx_download_positions(c, x.data(), x.size()));
+        check(gfs_ctx_sort_order(c, order.data(), order.size()));
+        check(gfs_ctx_stats(c, &it.stats));
+        gfs_ctx_destroy(c); slots[i].ctx = nullptr;
+        std::vector<Handle> ordering;
+        ordering.reserve(order.size());
+        for (uint64_t idx : order) ordering.push_back(Handle::forward(f.node_ids[idx]));   // idx -> handle, sgd.rs:649-662
+        it.graph->apply_ordering(ordering);
+        if (keep_positions) { it.positions = std::move(x); it.before = std::move(slots[i].f); }
+    };
+    std::vector<size_t> together;                                                     // indices into items: the batch's candidates
+    for (size_t i = 0; i < items.size(); ++i) {
+        BatchSortItem &it = items[i];
+        it.stats = gfs_stats{}; it.batched = false; it.positions.clear();
+        if (!it.graph || it.graph->node_count() == 0) continue;                       // sgd.rs:242-244
+        slots[i].f = it.graph->flatten();
+        gfs_graph_view v = slots[i].f.view();
+        gfs_sgd_params cp = it.params.to_c();
+        check(gfs_ctx_create(&v, 0, &slots[i].ctx));
+        const int rc = gfs_ctx_setup_1d(slots[i].ctx, &cp, &opt.cfg, nullptr, nullptr);
+        check(rc);
+        if (rc == GFS_NOTHING_TO_DO) {
+            std::cerr << "[path_sgd] No paths with multiple steps found\n";          // sgd.rs:259
+            gfs_ctx_destroy(slots[i].ctx); slots[i].ctx = nullptr;
+            continue;
+        }
+        check(gfs_ctx_init_positions(slots[i].ctx));
+        check(gfs_ctx_stats(slots[i].ctx, &it.stats));
+        if (it.stats.bundle == 1) together.push_back(i);                              // stays resident until the batch has run
+        else finish(i, true);                                                         // a team-kernel graph: alone, now
+    }
+    // A graph the batch refuses (flags that rule the fused launch out, more workgroups than one launch holds) is named by the
+    // error: it is taken out and runs alone, the others still run together.
+    std::vector<size_t> refused;
+    while (!together.empty() && !cleanup.b) {
+        std::vector<gfs_ctx *> ctxs;
+        for (size_t i : together) ctxs.push_back(slots[i].ctx);
+        const int rc = gfs_batch_create(ctxs.data(), ctxs.size(), nullptr, &cleanup.b);
+        if (rc != GFS_E_UNSUPPORTED) { check(rc); break; }
+        const std::string why = gfs_last_error();
+        unsigned long long named = 0;
+        const size_t at = why.find("batch item ");
+        if (at == std::string::npos || std::sscanf(why.c_str() + at, "batch item %llu", &named) != 1 || named >= together.size()) check(rc);
+        if (verbose >= 1) std::cerr << "[gfasort_hip] batch: graph " << together[named] << " runs alone (" << why << ")\n";
+        refused.push_back(together[named]);
+        together.erase(together.begin() + (std::ptrdiff_t)named);
+    }
+    if (cleanup.b) {
+        check(gfs_batch_run(cleanup.b, nullptr));
+        check(gfs_batch_get_stats(cleanup.b, &bs));
+        gfs_batch_destroy(cleanup.b); cleanup.b = nullptr;                            // (before its contexts go)
+        for (size_t i : together) { items[i].batched = true; finish(i, false); }
+    }
+    for (size_t i : refused) finish(i, true);
+    return bs;
+}
+
 static uint64_t splitmix64(uint64_t &s) {
     uint64_t z = (s += 0x9E3779B97F4A7C15ull);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

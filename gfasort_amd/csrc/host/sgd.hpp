@@ -97,6 +97,21 @@ std::vector<Handle> path_sgd_sort(const BidirectedGraph &g, const PathSGDParams 
 // ygs.rs:195 — path_sgd_sort + apply_ordering.
 void sgd_sort_only(BidirectedGraph &g, const PathSGDParams &p, uint8_t verbose, const HipOptions &opt = {},
                    gfs_stats *stats = nullptr, std::vector<double> *positions_out = nullptr);
+// sgd_sort_only over MANY graphs (no reference equivalent; gfasort_hip --batch).  Graphs for which the policy picks reference streams
+// (fewer than 16384 nodes) run together as one gfs_batch — one persistent launch, or as few as fit the device —, the others alone,
+// one after the other; every graph is then reordered exactly as sgd_sort_only reorders it.  A graph that gfs_batch_create refuses
+// (its error names the item) is taken out and runs alone; the rest still run together.  Only the batch's graphs are resident on
+// the device at once: a graph that runs alone for its bundle is run, read back and freed before the next one is set up.
+struct BatchSortItem {
+    BidirectedGraph *graph = nullptr;      // reordered in place
+    PathSGDParams params;
+    gfs_stats stats{};                     // the graph's own (a batched graph's kernel_ms is the batch's: 0 here)
+    bool batched = false;
+    FlatGraph before;                      // keep_positions: the graph as it was flattened before the sort ...
+    std::vector<double> positions;         // ... and the final positions by its dense index; empty where there was nothing to do
+};
+// Returns the batch's figures (all zero where no graph was batched).  Throws std::runtime_error on a HIP / argument error.
+gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbose, const HipOptions &opt = {}, bool keep_positions = false);
 // sgd.rs:773.  Gaussian start of dims >= 1 is drawn here (Box-Muller on SplitMix64(seed); the
 // reference's rand_distr ziggurat stream is not reproduced).
 Layout path_linear_sgd_layout(const BidirectedGraph &g, const LayoutSGDParams &p, const HipOptions &opt = {},

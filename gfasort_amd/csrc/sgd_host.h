@@ -38,6 +38,10 @@ const void *fused_kernel_nd(const KernelShape &s, bool pooled);             // s
 const void *fused_kernel_nd_team(const KernelShape &s, bool pooled);        // sgd_kernels_nd_team.hip: K2c, D = 2, 3
 const void *fused_kernel_nd_team_wide(const KernelShape &s, bool pooled);   // sgd_kernels_nd_team_wide.hip: K2c, D = 4..8
 
+// Many contexts per launch, kernel(const BatchItem *items, const uint32_t *block_item) (sgd_batch.h): K1d's body (dims 0) or K2d's
+// (dims 2, 3) on the item that block_item[blockIdx.x] names.  Null for other dimensions.
+const void *batch_fused_kernel(int dims, bool lds_tables);                  // sgd_kernels_batch.hip: K1f, K2f
+
 size_t pool_bytes(uint64_t n_iters);                      // sgd_kernels_1d.hip
 int nd_team_waves(int dims);                              // sgd_kernels_nd_team.hip: waves per SIMD the layout team kernels are built for
 

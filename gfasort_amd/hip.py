@@ -90,6 +90,17 @@ class SortQuality(C.Structure):
     _fields_ = [("steps", C.c_uint64), ("abs_err_sum", C.c_uint64), ("genomic_sum", C.c_uint64), ("sq_err_sum", C.c_double)]
 
 
+class BatchConfig(C.Structure):
+    """gfs_batch_config."""
+    _fields_ = [("max_blocks_per_launch", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
+class BatchStats(C.Structure):
+    """gfs_batch_stats: kernel_ms is the batch's (a batch does not advance its contexts' kernel_ms)."""
+    _fields_ = [("items", C.c_uint64), ("items_run", C.c_uint64), ("launches", C.c_uint64), ("blocks", C.c_uint64),
+                ("term_updates", C.c_uint64), ("attempts", C.c_uint64), ("kernel_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 PAIR_ERROR_DTYPE = np.dtype([("step_distance", "<u8"), ("pairs", "<u8"), ("sum_rel_sq", "<f8"), ("max_rel_sq", "<f8"),
                              ("sum_abs", "<f8"), ("sum_sq", "<f8")])
 
@@ -122,6 +133,7 @@ EXPORTS = [
     "gfs_ctx_debug_step_records", "gfs_ctx_debug_kshift", "gfs_phase_window", "gfs_ctx_phase_window",
     "gfs_ctx_pair_errors", "gfs_stress_sample_pairs", "gfs_ctx_stress_of_pairs", "gfs_ctx_sort_quality", "gfs_pair_errors",
     "gfs_ctx_path_errors", "gfs_ctx_stretched_pairs", "gfs_ctx_node_errors", "gfs_diagnose",
+    "gfs_batch_plan", "gfs_batch_create", "gfs_batch_run", "gfs_batch_get_stats", "gfs_batch_destroy",
 ]
 
 _lib = None
@@ -207,6 +219,12 @@ def lib():
         L.gfs_ctx_stretched_pairs.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.gfs_ctx_node_errors.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p]
         L.gfs_diagnose.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.gfs_batch_plan.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.gfs_batch_create.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.gfs_batch_run.argtypes = [C.c_void_p, C.c_void_p]
+        L.gfs_batch_get_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.gfs_batch_destroy.argtypes = [C.c_void_p]
+        L.gfs_batch_destroy.restype = None
         _lib = L
     return _lib
 
@@ -668,6 +686,50 @@ class Context:
         b, e = C.c_uint64(0), C.c_uint64(0)
         check(lib().gfs_ctx_phase_window(self._h, C.c_int64(int(set_begin)), C.c_int64(int(set_end)), C.byref(b), C.byref(e)))
         return int(b.value), int(e.value)
+
+
+# ---- batches: many configured contexts in one persistent launch -----------------------------------
+def batch_plan(blocks, max_blocks):
+    """gfs_batch_plan (host only): (launch_of_item as a list, n_launches) for items of `blocks` workgroups each, greedy in order."""
+    blocks = np.ascontiguousarray(blocks, dtype=np.uint64)
+    launch_of = np.zeros(max(blocks.shape[0], 1), dtype=np.uint32)
+    n = C.c_uint32(0)
+    check(lib().gfs_batch_plan(_ptr(blocks), C.c_uint64(blocks.shape[0]), C.c_uint64(int(max_blocks)), _ptr(launch_of), C.byref(n)))
+    return launch_of[:blocks.shape[0]].tolist(), int(n.value)
+
+
+class Batch:
+    """gfs_batch: set-up Contexts run together, every item's whole schedule in one launch (or as few as fit the device).  The
+    contexts are borrowed: keep them alive and do not set them up again while the batch exists.  After run() each context is as
+    if its own run() had been called (download(), sort_order(), the read-outs and stats() per item), except that the kernel time
+    is the batch's."""
+
+    def __init__(self, contexts, max_blocks_per_launch=0):
+        self._h = C.c_void_p()
+        self.contexts = list(contexts)
+        n = len(self.contexts)
+        arr = (C.c_void_p * max(n, 1))(*[c._h for c in self.contexts])
+        cfg = BatchConfig(int(max_blocks_per_launch), (C.c_uint64 * 3)())
+        check(lib().gfs_batch_create(arr if n else None, C.c_uint64(n), C.byref(cfg), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().gfs_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, stream=None):
+        return check(lib().gfs_batch_run(self._h, C.c_void_p(stream or 0)))
+
+    def stats(self):
+        st = BatchStats()
+        check(lib().gfs_batch_get_stats(self._h, C.byref(st)))
+        return st
 
 
 # ---- one-shot entry points ---------------------------------------------------------------------

@@ -6,6 +6,7 @@ and the layout arm (src/bin/gfasort.rs:265-274 -> src/sgd.rs:773-1188).
 Same names, argument meaning and empty-result behaviour; positions are indexed by the dense
 node index (position in node_order) exactly like the reference's HashMap<usize,f64> keys.
 """
+import re
 from typing import Optional, Tuple
 
 import numpy as np
@@ -66,3 +67,65 @@ def path_linear_sgd_layout(graph: FlatGraph, params: LayoutSGDParams, init: Opti
     rc, coords, st = hip.path_linear_sgd_layout_raw(graph, params, init, cfg=cfg)
     lay = Layout(D, graph.n_nodes, coords if rc == hip.OK else None)
     return (lay, st) if return_stats else lay
+
+
+def path_sgd_sort_batch(graphs, params, cfg=None, max_blocks_per_launch: int = 0, device: int = 0):
+    """path_sgd_sort over MANY graphs: the ones whose plan is the fused reference-stream kernel (graphs of fewer than 16384
+    nodes under the default policy) run together as one hip.Batch — one persistent launch, or as few as fit the device —
+    and the others alone, one after the other.  A graph the batch refuses (hip.Batch names it) is taken out and runs alone;
+    the rest still run together.  Only the batch's graphs are resident at once: a graph that runs alone for its bundle is run,
+    read back and closed before the next one is set up.  params: one PathSGDParams for all, or one per graph; cfg likewise (or
+    None).  Returns one dict per graph, in order: positions (float64[n_nodes]; empty where the reference returns an empty map),
+    order (uint64 dense indices in ascending position order; empty likewise), stats (hip.Stats of the graph's context, None for
+    an empty graph) and batched (whether it ran in the batch); and the batch's hip.BatchStats (None when nothing was batched)."""
+    graphs = list(graphs)
+    per_graph = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * len(graphs)
+    params, cfgs = per_graph(params), per_graph(cfg)
+    if len(params) != len(graphs) or len(cfgs) != len(graphs):
+        raise ValueError("params / cfg: one for all graphs or one per graph")
+    result = lambda ctx, batched: dict(positions=ctx.download(), order=ctx.sort_order(), stats=ctx.stats(), batched=batched)
+    out = [None] * len(graphs)
+    held = {}                                                  # graph index -> its Context, for the batch's candidates
+    try:
+        for i, (g, p, c) in enumerate(zip(graphs, params, cfgs)):
+            out[i] = dict(positions=np.zeros(0), order=np.zeros(0, dtype=np.uint64), stats=None, batched=False)
+            if g.n_nodes == 0:
+                continue
+            ctx = hip.Context(g, device=device)
+            try:
+                rc = ctx.setup_1d(p, c)
+                if rc != hip.OK:                               # nothing to do
+                    out[i]["stats"] = ctx.stats()
+                    continue
+                ctx.init_positions()
+                if ctx.stats().bundle == 1:
+                    held[i], ctx = ctx, None
+                    continue
+                ctx.run()
+                out[i] = result(ctx, False)
+            finally:
+                if ctx is not None:
+                    ctx.close()
+        batched, batch, batch_stats = sorted(held), None, None
+        while batched and batch is None:
+            try:
+                batch = hip.Batch([held[i] for i in batched], max_blocks_per_launch)
+            except hip.GfsError as e:
+                named = re.search(r"batch item (\d+)", str(e))
+                if e.code != -5 or not named:                  # GFS_E_UNSUPPORTED names the item: that one runs alone
+                    raise
+                del batched[int(named.group(1))]
+        if batch is not None:
+            try:
+                batch.run()
+                batch_stats = batch.stats()
+            finally:
+                batch.close()
+        for i, ctx in held.items():
+            if i not in batched:
+                ctx.run()
+            out[i] = result(ctx, i in batched)
+        return out, batch_stats
+    finally:
+        for ctx in held.values():
+            ctx.close()

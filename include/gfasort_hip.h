@@ -365,6 +365,48 @@ int gfs_ctx_node_errors(gfs_ctx *ctx, uint64_t z, double ratio, gfs_node_error *
 int gfs_diagnose(const gfs_graph_view *g, uint64_t dims, const double *positions, uint64_t z, double ratio,
                  gfs_path_error *paths_out, gfs_stretched_pair *pairs_out, uint64_t cap, uint64_t *total);
 
+/* ---- batches: many small graphs in one persistent launch (no reference equivalent) ----
+ * A graph of fewer than 16384 nodes runs reference streams, at most one per 4 nodes: a few workgroups on a chip of hundreds of
+ * CUs.  A batch runs the whole schedule of many configured contexts in one launch whose grid is the concatenation of theirs; every
+ * workgroup works on its own context's buffers exactly as a launch of that context alone does.  After gfs_batch_run each context
+ * is as if gfs_ctx_run had run it alone — positions, RNG streams and counters advanced, iterations += iter_max + 1, launches += 1 —
+ * so gfs_ctx_download_positions, gfs_ctx_sort_order, the quality read-outs and gfs_ctx_stats work per item; one stream per item is
+ * bit for bit the solo run.  A context's kernel_ms is NOT advanced by a batch: the time belongs to the batch (gfs_batch_stats).
+ * Running a batch again continues every item's streams, as a second gfs_ctx_run does.
+ * A batch BORROWS its contexts: they must outlive it and must not be set up again while it exists (gfs_batch_run returns
+ * GFS_E_STATE, naming the item, where a context's workgroups, iterations, LDS use or plan are no longer those the batch's launches
+ * were cut for).  All items: one device; one
+ * kind (all 1D sorts, or all layouts of the same 2 or 3 dimensions); set up so that their plan is the pooled fused reference-stream
+ * kernel (bundle 1 — chosen or GFS_F_BUNDLE(1) —, no trace, no GFS_F_NO_FUSE, no GFS_F_PHASED window in effect); one block size;
+ * iter_max + 1 <= 4096.  Otherwise GFS_E_UNSUPPORTED; GFS_E_ARG for null, n == 0 or the same context twice; GFS_E_STATE for a
+ * context that is not set up; the text names the item; these checks come before any device call.  Items keep their own parameters,
+ * schedules (iter_max may differ), quotas, seeds and stream counts.  A context with nothing to do is skipped and left alone.
+ * Items with and without LDS tables go into separate launches; a launch's dynamic LDS is the largest among its items. */
+typedef struct gfs_batch gfs_batch;
+typedef struct gfs_batch_config {
+    uint64_t max_blocks_per_launch;   /* 0 = what the device holds at once (occupancy of the batch kernel at the launch's
+                                         block size and largest LDS table, times the CU count); a smaller value is a test
+                                         hook and a way to leave room for other work */
+    uint64_t reserved[3];
+} gfs_batch_config;
+typedef struct gfs_batch_stats {
+    uint64_t items, items_run;        /* contexts given / contexts that had something to do */
+    uint64_t launches;
+    uint64_t blocks;                  /* workgroups over all launches */
+    uint64_t term_updates, attempts;  /* sums over the items, from their own counters */
+    double   kernel_ms, total_ms;     /* HIP events around the batch launches / wall time inside gfs_batch_run */
+} gfs_batch_stats;
+
+/* host only, no device: items in the given order, a new launch where the next item would not fit (an exact fit is taken); an item
+ * never straddles two launches.  launch_of_item[n]; *n_launches.  GFS_E_UNSUPPORTED if one item alone exceeds max_blocks.
+ * gfs_batch_create cuts its launches with it, so that every workgroup of a launch is resident at once: a graph whose
+ * workgroups start late drifts in its schedule. */
+int  gfs_batch_plan(const uint64_t *blocks_of_item, uint64_t n, uint64_t max_blocks, uint32_t *launch_of_item, uint32_t *n_launches);
+int  gfs_batch_create(gfs_ctx *const *ctxs, uint64_t n, const gfs_batch_config *cfg /*nullable*/, gfs_batch **out);
+int  gfs_batch_run(gfs_batch *b, void *hip_stream);      /* every item's k = 0..=iter_max, then synchronises */
+int  gfs_batch_get_stats(gfs_batch *b, gfs_batch_stats *out);   /* synchronises */
+void gfs_batch_destroy(gfs_batch *b);
+
 /* ---- multi-device runs (no reference equivalent: the reference is one process, src/sgd.rs:413-593) ----
  * Paths are sharded over `world` ranks, one rank per GPU (one process per GPU, or one host thread per GPU); every rank
  * performs its share of an iteration's term updates on its own replica of the positions; after every window of
