@@ -1,10 +1,12 @@
-// capi.hip — the C ABI of libgfasort_hip.so (include/gfasort_hip.h): host tables, the resident
-// context (device mirror of PathIndex + positions + RNG streams) and the one-shot entry points
-// that stand where path_linear_sgd / path_linear_sgd_layout stand in the reference.
+// capi.hip — the device plumbing of the C ABI of libgfasort_hip.so (include/gfasort_hip.h): the resident
+// context (device mirror of PathIndex + positions + RNG streams), its launches and read-outs, batches, and the one-shot entry
+// points that stand where path_linear_sgd / path_linear_sgd_layout stand in the reference.  What a context launches is decided in
+// launch_policy.h; the host tables are host_tables.hip's.
 #include "../../include/gfasort_hip.h"
 #include "sgd_kernel_common.h"
 #include "sgd_batch.h"
 #include "batch_plan.h"
+#include "launch_policy.h"
 #include "sgd_host.h"
 
 #include <algorithm>
@@ -18,9 +20,7 @@
 #include <string>
 #include <vector>
 
-static thread_local std::string g_err;
-static int fail(int code, const std::string &msg) { g_err = msg; return code; }
-int gfs_set_error(int code, const std::string &msg) { return fail(code, msg); }      // for multi.hip
+static int fail(int code, const std::string &msg) { return gfs_set_error(code, msg); }   // (the error slot: host_tables.hip)
 #define HIPCHK(expr)                                                                           \
     do {                                                                                       \
         hipError_t _e = (expr);                                                                \
@@ -28,46 +28,9 @@ int gfs_set_error(int code, const std::string &msg) { return fail(code, msg); } 
             return fail(GFS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));         \
     } while (0)
 
-// ---- host restatements (bit-exact; this TU is built with -ffp-contract=off) ----------------
-static inline int32_t h_sat_i32(double v) {
-    if (v != v) return 0;
-    if (v <= -2147483648.0) return INT32_MIN;
-    if (v >= 2147483647.0) return INT32_MAX;
-    return (int32_t)v;
-}
-static double h_fpp(double a, double b) {                                  // sgd.rs:155-182
-    int32_t e = h_sat_i32(b);
-    uint64_t bits; std::memcpy(&bits, &a, 8);
-    int32_t high = (int32_t)(bits >> 32);
-    int32_t diff = (int32_t)((uint32_t)high - 1072632447u);
-    int32_t new_high = h_sat_i32((b - (double)e) * (double)diff + 1072632447.0);
-    uint64_t fb = ((uint64_t)(uint32_t)new_high) << 32;
-    double frac; std::memcpy(&frac, &fb, 8);
-    double base = a, r = 1.0;
-    int32_t ex = e;
-    if (ex < 0) return std::nan("");     // the reference would loop forever (b < 0 never occurs for theta in [0,1))
-    while (ex != 0) { if (ex & 1) r *= base; base *= base; ex >>= 1; }
-    return r * frac;
-}
-static uint64_t splitmix64(uint64_t &s) {
-    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-static int check_params(const gfs_sgd_params *p) {
-    if (!p) return fail(GFS_E_ARG, "params is null");
-    if (!(p->theta >= 0.0 && p->theta < 1.0)) return fail(GFS_E_ARG, "theta must be in [0,1)");
-    if (p->space_quantization_step == 0) return fail(GFS_E_ARG, "space_quantization_step must be > 0");
-    if (!(p->eta_max > 0.0)) return fail(GFS_E_ARG, "eta_max must be > 0");
-    return GFS_OK;
-}
-
 extern "C" {
 
 const char *gfs_version(void) { return "gfasort_hip 0.1.0 (gfx950)"; }
-const char *gfs_last_error(void) { return g_err.c_str(); }
 int gfs_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -121,195 +84,19 @@ int gfs_warmup(int device) {
     return GFS_OK;
 }
 
-double gfs_fast_precise_pow(double a, double b) { return h_fpp(a, b); }
-
-int gfs_sgd_schedule(const gfs_sgd_params *p, double *etas) {              // sgd.rs:300-308,617-638
-    if (!p || !etas) return fail(GFS_E_ARG, "null argument");
-    double w_min = 1.0 / p->eta_max, w_max = 1.0;
-    double eta_max = 1.0 / w_min;
-    double eta_min = p->eps / w_max;
-    double lambda = std::log(eta_max / eta_min) / ((double)p->iter_max - 1.0);
-    for (uint64_t t = 0; t <= p->iter_max; ++t) {
-        int64_t d = (int64_t)t - (int64_t)p->iter_with_max_learning_rate;
-        if (d < 0) d = -d;
-        etas[t] = eta_max * std::exp(-lambda * (double)d);
-    }
-    return GFS_OK;
-}
-
-// The default window of GFS_F_PHASED: around the reference's switch to the cooling phase (sgd.rs:297: cooling for
-// k > first_cooling = floor(cooling_start * iter_max)), scaled with iter_max.  [first_cooling + 1 + lo, first_cooling + 1 + hi)
-// with lo, hi in thousandths of iter_max (hi = kPhaseWindowToEnd: to the end of the schedule), clipped to [0, iter_max + 1).
-// Chosen on DRB1-3123 x120 and a 525k-node bubble graph (profiles/r05/phased_window_probe.log).
-static constexpr int64_t kPhaseWindowLo = 0, kPhaseWindowToEnd = INT64_MAX, kPhaseWindowHi = kPhaseWindowToEnd;
-int gfs_phase_window(const gfs_sgd_params *p, uint64_t *k_begin, uint64_t *k_end) {
-    if (!p || !k_begin || !k_end) return fail(GFS_E_ARG, "null argument");
-    const unsigned __int128 n = p->iter_max, last = n + 1;                 // iterations 0..=iter_max
-    const double fc = std::floor(p->cooling_start * (double)p->iter_max);   // as iter_consts
-    const unsigned __int128 f1 = (!(fc > 0.0) ? 0 : (fc >= 18446744073709551616.0 ? (unsigned __int128)UINT64_MAX : (unsigned __int128)(uint64_t)fc)) + 1;
-    auto at = [&](int64_t per_mille) -> unsigned __int128 {                // f1 + per_mille * iter_max / 1000, clipped to [0, last]
-        if (per_mille == kPhaseWindowToEnd) return last;
-        const unsigned __int128 off = n * (unsigned __int128)(per_mille < 0 ? -per_mille : per_mille) / 1000;
-        const unsigned __int128 v = per_mille < 0 ? (off >= f1 ? 0 : f1 - off) : f1 + off;
-        return v < last ? v : last;
-    };
-    const unsigned __int128 e = at(kPhaseWindowHi), b = std::min(at(kPhaseWindowLo), e);
-    const unsigned __int128 cap = (unsigned __int128)UINT64_MAX;           // (iter_max = 2^64 - 1: iter_max + 1 does not fit)
-    *k_begin = (uint64_t)std::min(b, cap); *k_end = (uint64_t)std::min(e, cap);
-    return GFS_OK;
-}
-
-uint64_t gfs_zeta_table_len(const gfs_sgd_params *p) {                     // sgd.rs:311-315
-    if (!p || p->space_quantization_step == 0) return 0;
-    uint64_t n = p->space <= p->space_max
-                     ? p->space
-                     : p->space_max + (p->space - p->space_max) / p->space_quantization_step + 1;
-    return n + 1;
-}
-
-int gfs_zeta_table(const gfs_sgd_params *p, double *zetas) {               // sgd.rs:317-331
-    if (!p || !zetas) return fail(GFS_E_ARG, "null argument");
-    uint64_t len = gfs_zeta_table_len(p);
-    if (!len) return fail(GFS_E_ARG, "bad zeta parameters");
-    for (uint64_t k = 0; k < len; ++k) zetas[k] = 0.0;
-    double zeta_tmp = 0.0;
-    for (uint64_t i = 1; i <= p->space; ++i) {
-        zeta_tmp += h_fpp(1.0 / (double)i, p->theta);
-        if (i <= p->space_max) zetas[i] = zeta_tmp;
-        if (i >= p->space_max && (i - p->space_max) % p->space_quantization_step == 0) {
-            uint64_t idx = p->space_max + 1 + (i - p->space_max) / p->space_quantization_step;
-            if (idx < len) zetas[idx] = zeta_tmp;
-        }
-    }
-    return GFS_OK;
-}
-
-int gfs_init_positions(const gfs_graph_view *g, double *x) {               // sgd.rs:271-294
-    if (!g || (!x && g->n_nodes)) return fail(GFS_E_ARG, "null argument");
-    uint64_t len = 0;
-    for (uint64_t i = 0; i < g->n_nodes; ++i) { x[i] = (double)len; len += g->node_len[i]; }
-    return GFS_OK;
-}
-
-int gfs_init_layout_dim0(const gfs_graph_view *g, uint64_t D, double *c) { // sgd.rs:832-853
-    if (!g || (!c && g->n_nodes) || D == 0) return fail(GFS_E_ARG, "bad argument");
-    uint64_t len = 0;
-    for (uint64_t i = 0; i < g->n_nodes; ++i) {
-        c[i * 2 * D + 0] = (double)len;
-        c[i * 2 * D + D] = (double)(len + g->node_len[i]);
-        len += g->node_len[i];
-    }
-    return GFS_OK;
-}
-
-// rand_distr 0.5 StandardNormal (f64) on Xoshiro256+ — the 256-layer ziggurat, restated from the crate's published
-// algorithm; its tables are rebuilt by the construction of the crate's generator script (R, V below).  PARITY UNPINNED
-// (DESIGN.md §5): neither the crate nor its table literals are in the container.
-namespace {
-constexpr double kZigR = 3.6541528853610088, kZigV = 0.00492867323399;
-struct ZigTables {
-    double x[257], f[257];
-    ZigTables() {
-        x[0] = kZigV / std::exp(-kZigR * kZigR / 2.0);
-        x[1] = kZigR;
-        for (int i = 1; i < 256; ++i) x[i + 1] = std::sqrt(-2.0 * std::log(kZigV / x[i] + std::exp(-x[i] * x[i] / 2.0)));
-        x[256] = 0.0;
-        for (int i = 0; i <= 256; ++i) f[i] = std::exp(-x[i] * x[i] / 2.0);
-    }
-};
-struct Xo256p {                                                            // rand_xoshiro 0.7 Xoshiro256Plus
-    uint64_t s[4];
-    explicit Xo256p(uint64_t seed) { for (auto &w : s) w = splitmix64(seed); }   // seed_from_u64
-    uint64_t next() {
-        const uint64_t r = s[0] + s[3], t = s[1] << 17;
-        s[2] ^= s[0]; s[3] ^= s[1]; s[1] ^= s[2]; s[0] ^= s[3]; s[2] ^= t; s[3] = (s[3] << 45) | (s[3] >> 19);
-        return r;
-    }
-    uint64_t uniform_usize(uint64_t n) {                                       // rand 0.9 Uniform<usize>::new(0, n): the u32 sampler
-        if (n <= 0xFFFFFFFFull) {                                              // where n fits, widening multiply and rejection
-            const uint32_t range = (uint32_t)n, thresh = (uint32_t)(0u - range) % range;
-            for (;;) { const uint64_t m = (uint64_t)(uint32_t)(next() >> 32) * range; if ((uint32_t)m >= thresh) return m >> 32; }
-        }
-        const uint64_t thresh = (0ull - n) % n;
-        for (;;) { const unsigned __int128 m = (unsigned __int128)next() * n; if ((uint64_t)m >= thresh) return (uint64_t)(m >> 64); }
-    }
-};
-inline double float_with_exponent(uint64_t fraction52, int e) {
-    const uint64_t b = fraction52 | ((uint64_t)(1023 + e) << 52);
-    double d; std::memcpy(&d, &b, 8); return d;
-}
-inline double open01(Xo256p &g) { return float_with_exponent(g.next() >> 12, 0) - (1.0 - 2.220446049250313e-16 / 2.0); }
-double standard_normal(Xo256p &g) {
-    static const ZigTables T;
-    for (;;) {
-        const uint64_t bits = g.next();
-        const unsigned i = (unsigned)(bits & 0xff);
-        const double u = float_with_exponent(bits >> 12, 1) - 3.0;               // [-1, 1)
-        const double x = u * T.x[i];
-        if (std::fabs(x) < T.x[i + 1]) return x;
-        if (i == 0) {                                                          // the tail beyond R
-            double tx = 1.0, ty = 0.0;
-            while (-2.0 * ty < tx * tx) {
-                const double x_ = open01(g), y_ = open01(g);
-                tx = std::log(x_) / kZigR; ty = std::log(y_);
-            }
-            return u < 0.0 ? tx - kZigR : kZigR - tx;
-        }
-        const double r = (double)(g.next() >> 11) * (1.0 / 9007199254740992.0);  // rng.random::<f64>()
-        if (T.f[i + 1] + (T.f[i] - T.f[i + 1]) * r < std::exp(-x * x / 2.0)) return x;
-    }
-}
-}  // namespace
-
-// The whole start of path_linear_sgd_layout (sgd.rs:829-853): one generator seeded `seed`; per node the + end's
-// dimensions 1..D-1, then the - end's, each StandardNormal * sqrt(2N); dimension 0 as gfs_init_layout_dim0.
-int gfs_init_layout(const gfs_graph_view *g, uint64_t D, uint64_t seed, double *c) {
-    if (!g || (!c && g->n_nodes) || D == 0) return fail(GFS_E_ARG, "bad argument");
-    Xo256p rng(seed);                                                          // :829
-    const double sqrt_n = std::sqrt((double)g->n_nodes * 2.0);                 // :836
-    uint64_t len = 0;
-    for (uint64_t i = 0; i < g->n_nodes; ++i) {
-        c[i * 2 * D + 0] = (double)len;                                        // :839
-        for (uint64_t d = 1; d < D; ++d) c[i * 2 * D + d] = standard_normal(rng) * sqrt_n;          // :840-843
-        c[i * 2 * D + D] = (double)(len + g->node_len[i]);                     // :846
-        for (uint64_t d = 1; d < D; ++d) c[i * 2 * D + D + d] = standard_normal(rng) * sqrt_n;      // :847-850
-        len += g->node_len[i];
-    }
-    return GFS_OK;
-}
-
-int gfs_sort_order(const double *x, uint64_t n, uint64_t *order) {         // sgd.rs:665-671
-    if ((!x || !order) && n) return fail(GFS_E_ARG, "null argument");
-    std::iota(order, order + n, (uint64_t)0);
-    // partial_cmp(..).unwrap_or(Equal) + stable sort: ascending, -0.0 == +0.0, ties keep the index
-    // order.  NaNs (never produced by a finite run) are placed after all numbers so that the order
-    // is total; the device version (gfs_ctx_sort_order) uses the same rule.
-    std::stable_sort(order, order + n, [x](uint64_t a, uint64_t b) {
-        const double xa = x[a], xb = x[b];
-        if (xa != xa) return false;
-        if (xb != xb) return true;
-        return xa < xb;
-    });
-    return GFS_OK;
-}
-
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
 // resident context
 // ---------------------------------------------------------------------------------------------
-static constexpr size_t kCounterBytes = 1024 * 8 * sizeof(unsigned long long);   // gfs::COUNTER_SLOTS lines of 64 B
+static constexpr size_t kCounterBytes = gfs::COUNTER_SLOTS * 8 * sizeof(unsigned long long);   // lines of 64 B
 
-// What a configured context launches: everything of gfs_ctx_run_iteration / gfs_ctx_run_range that does not depend on the
-// call, resolved once by setup_common (plan_launches).
+// The kernels of a configured context, resolved once by setup_common for the shape the policy decided (gfs_ctx::shape,
+// launch_policy.h): everything of gfs_ctx_run_iteration / gfs_ctx_run_range that does not depend on the call.
 struct LaunchPlan {
     const void *iteration = nullptr;         // K1 / K1b, K2 / K2b: one iteration per launch
     const void *window_iteration = nullptr;  // GFS_F_PHASED: K1, for the iterations of the window
     const void *fused = nullptr;             // K1c / K1d / K1e / K2c / K2d: a range of iterations per launch; null: one launch per iteration
-    bool pooled = false;                     // ... drawing from work pools (false: GFS_F_DBG_FREE_RUNNING's fixed quotas)
-    bool fuse_one = false;                   // a range of ONE iteration is a fused launch too, in chunks of one_chunk
-    bool fuse_one_probe = false;             // ... or would be if GFS_DBG_ONE_CHUNK asked for it
-    uint32_t one_chunk = 0;
 };
 
 struct gfs_ctx {
@@ -332,7 +119,7 @@ struct gfs_ctx {
     gfs_sgd_params params{};
     gfs_launch_config cfg{};
     std::vector<double> etas;
-    double *d_zetas = nullptr; uint64_t zlen_full = 0, zlen_staged = 0;
+    double *d_zetas = nullptr;
     double *d_x = nullptr; bool x_owned = false; uint64_t x_len = 0;
     uint64_t *d_rng = nullptr;
     uint32_t *d_lead = nullptr;      // team kernels: the waves' partly expanded passes, [8][n_streams]
@@ -341,20 +128,9 @@ struct gfs_ctx {
     gfs::IterConsts *d_its = nullptr; uint64_t its_cap = 0;   // schedule slice of a fused launch (arbitrary lists)
     gfs::IterConsts *d_its_all = nullptr;                     // constants of iterations 0..=iter_max, resident
     uint32_t *d_pool = nullptr; uint64_t pool_cap = 0;        // fused launch: per-iteration work pool counters (sgd_kernels_1d.hip)
-    uint64_t n_streams = 0, quota_total = 0;
-    uint64_t fused_resident_blocks = 0; // workgroups of the fused team kernel the chip holds at once (block size, LDS table)
+    gfs::LaunchShape shape;            // streams, bundle, run length, phase window, LDS tables, what a range launches (launch_policy.h)
     LaunchPlan plan;
-    uint32_t block = 256;
-    uint32_t bundle = 1;               // lanes per sampling bundle actually used (1 = reference streams)
-    uint32_t partners = 1;             // partner draws per leader (2: 1D team kernel at B = 64)
-    uint32_t chain = 1;                // longest run in trips (sgd_device.h run_trips); 1 = a run is one trip
-    bool lds_tables = true, atomic_loads = true;
-    size_t lds_bytes = 0;
     int32_t kshift_override = -1;      // test hook gfs_ctx_debug_kshift: >= 0 replaces the crowding onset of fill_kargs
-    // GFS_F_PHASED (K1e, sgd_kernels_1d_phased.hip): iterations [win_begin, win_end) run reference streams, the others the team
-    // sampler at B = 64.  phased is false where the flag is a no-op (the auto policy picked another bundle).
-    bool phased = false;
-    uint64_t win_begin = 0, win_end = 0;
     uint64_t *d_quality = nullptr; uint64_t quality_cap = 0;   // K7 read-outs: scratch in 8-byte words, kept between calls
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -385,11 +161,11 @@ static void free_sgd_state(gfs_ctx *c) {
 
 static int seed_streams(gfs_ctx *c) {
     // stream t <- Xoshiro256Plus::seed_from_u64(seed + stream_base + t)   (sgd.rs:431-432)
-    const uint64_t T = c->n_streams;
+    const uint64_t T = c->shape.n_streams;
     std::vector<uint64_t> st(4 * T);
     for (uint64_t t = 0; t < T; ++t) {
         uint64_t sm = c->params.seed + c->cfg.stream_base + t;
-        for (int k = 0; k < 4; ++k) st[(uint64_t)k * T + t] = splitmix64(sm);
+        for (int k = 0; k < 4; ++k) st[(uint64_t)k * T + t] = gfs::splitmix64(sm);
     }
     HIPCHK(hipMemcpy(c->d_rng, st.data(), st.size() * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemset(c->d_counters, 0, kCounterBytes));
@@ -399,57 +175,35 @@ static int seed_streams(gfs_ctx *c) {
 }
 
 // The zeta table of sgd.rs:311-331 on the device.  Only indices reachable from
-// jump <= min(space, max_path_steps-1) are ever read (sgd.rs:462-469); when the table is computed here
+// jump <= min(space, max_path_steps-1) are ever read (sgd.rs:462-469: shape.zlen_staged of them); when the table is computed here
 // the running sum — which is order-dependent and must be accumulated exactly as the reference does —
 // stops at the largest i that feeds a reachable entry (space is the longest path in bp: 1.3e6 for C3,
 // of which 1.6e5 matter).
 static int upload_zeta_table(gfs_ctx *c, const gfs_sgd_params *p, const double *zetas) {
-    c->zlen_full = gfs_zeta_table_len(p);
-    if (c->zlen_full > 0xFFFFFFFFull) return fail(GFS_E_UNSUPPORTED, "zeta table too long");
-    const uint64_t maxjump = std::min<uint64_t>(p->space, c->max_path_steps ? c->max_path_steps - 1 : 0);
-    const uint64_t last_idx = maxjump > p->space_max
-                                  ? p->space_max + (maxjump - p->space_max) / p->space_quantization_step + 1
-                                  : maxjump;
-    c->zlen_staged = std::min<uint64_t>(last_idx + 1, c->zlen_full);
+    const uint64_t zlen_full = c->shape.zlen_full;
     std::vector<double> ztab;
     if (!zetas) {
-        const uint64_t m = c->zlen_staged - 1;                      // last staged index
+        const uint64_t m = c->shape.zlen_staged - 1;                // last staged index
         const uint64_t need_i = m <= p->space_max ? m : p->space_max + (m - p->space_max - 1) * p->space_quantization_step;
         gfs_sgd_params q = *p;
         q.space = std::min<uint64_t>(p->space, std::max<uint64_t>(need_i, 1));
         std::vector<double> part(gfs_zeta_table_len(&q));
         gfs_zeta_table(&q, part.data());
-        ztab.assign(c->zlen_full, 0.0);
+        ztab.assign(zlen_full, 0.0);
         std::copy(part.begin(), part.begin() + std::min<size_t>(part.size(), ztab.size()), ztab.begin());
         zetas = ztab.data();
     }
-    HIPCHK(hipMalloc(&c->d_zetas, c->zlen_full * 8));
-    HIPCHK(hipMemcpy(c->d_zetas, zetas, c->zlen_full * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc(&c->d_zetas, zlen_full * 8));
+    HIPCHK(hipMemcpy(c->d_zetas, zetas, zlen_full * 8, hipMemcpyHostToDevice));
     return GFS_OK;
 }
 
-static void iter_consts(const gfs_ctx *c, uint64_t k, gfs::IterConsts &it) {
-    const gfs_sgd_params &p = c->params;
-    double fc = std::floor(p.cooling_start * (double)p.iter_max);          // sgd.rs:297
-    uint64_t first_cooling = !(fc > 0.0) ? 0 : (fc >= 18446744073709551616.0 ? UINT64_MAX : (uint64_t)fc);
-    bool cooling = k > first_cooling;                                      // sgd.rs:393-396
-    double theta = cooling ? 0.001 : p.theta;
-    it.eta = c->etas[k];
-    it.cooling = cooling ? 1 : 0;
-    it.zeta2theta = 1.0 + h_fpp(0.5, theta);                               // sgd.rs:471 (== :143 bound)
-    double omt = 1.0 - theta;                                              // sgd.rs:133
-    it.omt_e = h_sat_i32(omt); it.omt_fb = omt - (double)it.omt_e;
-    double alpha = 1.0 / (1.0 - theta);                                    // sgd.rs:132
-    it.alpha_e = h_sat_i32(alpha); it.alpha_fb = alpha - (double)it.alpha_e;
-    it._pad = (c->phased && k >= c->win_begin && k < c->win_end) ? 1 : 0;   // K1e: a window iteration (the other kernels ignore it)
-}
-
-static bool in_window(const gfs_ctx *c, uint64_t k) { return c->phased && k >= c->win_begin && k < c->win_end; }
+static gfs::IterConsts iter_consts(const gfs_ctx *c, uint64_t k) { return gfs::iter_consts(c->params, c->etas, c->shape, k); }
 
 // The resident table of the whole schedule's constants (d_its_all); again whenever the phase window moves, whose marks it carries.
 static int upload_schedule(gfs_ctx *c) {
     std::vector<gfs::IterConsts> all(c->params.iter_max + 1);
-    for (uint64_t k = 0; k <= c->params.iter_max; ++k) iter_consts(c, k, all[k]);
+    for (uint64_t k = 0; k <= c->params.iter_max; ++k) all[k] = iter_consts(c, k);
     HIPCHK(hipMemcpy(c->d_its_all, all.data(), all.size() * sizeof(gfs::IterConsts), hipMemcpyHostToDevice));
     return GFS_OK;
 }
@@ -466,18 +220,13 @@ static const void *fused_kernel(const gfs::KernelShape &s, bool pooled) {
     if (s.bundle <= 1) return gfs::fused_kernel_nd(s, pooled);
     return s.dims <= 3 ? gfs::fused_kernel_nd_team(s, pooled) : gfs::fused_kernel_nd_team_wide(s, pooled);
 }
-// "This context has a fused team kernel": K1c (K1e where phased) at the sort's widest bundles, K2c for layouts of 2 and more
-// dimensions at B = 64.  Such a context is bounded by residency, keeps the schedule's constants resident and draws two partners
-// per leader at B = 64 (choose_bundle).
-static bool has_fused_team_kernel(int dims, uint32_t bundle) { return (dims == 0 && bundle >= 16) || (dims >= 2 && bundle == 64); }
-
 // Workgroups of `fn` one CU holds at once with this context's block size and LDS table (registers, waves per SIMD and the table
 // all count).  Also: the first launch of a kernel function costs the host ~0.1 ms (the runtime materialises the function
 // lazily), and a caller that brackets its launch with events pays that inside the bracket; this resolves the function at setup.
 static int resident_blocks_per_cu(const gfs_ctx *c, const void *fn, int *per_cu) {
     hipFuncAttributes attr;
     HIPCHK(hipFuncGetAttributes(&attr, fn));
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, fn, (int)c->block, c->lds_bytes));
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, fn, (int)c->shape.block, c->shape.lds_bytes));
     return GFS_OK;
 }
 
@@ -485,171 +234,49 @@ static int resident_blocks_per_cu(const gfs_ctx *c, const void *fn, int *per_cu)
 static hipError_t launch(const gfs_ctx *c, const void *fn, gfs::KArgs &a, const gfs::IterConsts *its, uint32_t n_iters, uint32_t *pool,
                          hipStream_t st) {
     void *args[] = {&a, &its, &n_iters, &pool};                            // (a per-iteration kernel reads args[0] only)
-    const dim3 block(c->block), grid((unsigned)((c->n_streams + c->block - 1) / c->block));
-    return hipLaunchKernel(fn, grid, block, args, c->lds_bytes, st);
+    const gfs::LaunchShape &s = c->shape;
+    const dim3 block(s.block), grid((unsigned)((s.n_streams + s.block - 1) / s.block));
+    return hipLaunchKernel(fn, grid, block, args, s.lds_bytes, st);
 }
 
-// Resolves c->plan — and bounds the automatic stream count by residency.  Needs the bundle, the flags and lds_bytes.
+// Resolves c->plan for c->shape as shape_before_residency left it, asks the runtime for the fused team kernel's residency and
+// lets shape_after_residency finish the shape (which may lower n_streams).
 static int plan_launches(gfs_ctx *c) {
+    gfs::LaunchShape &s = c->shape;
     LaunchPlan &pl = c->plan;
     pl = LaunchPlan{};
-    c->fused_resident_blocks = 0;
-    const bool trace = c->cfg.trace_per_stream != 0;
-    const gfs::KernelShape shape{c->dims, c->bundle, c->lds_tables, c->atomic_loads, trace};
-    const bool team = has_fused_team_kernel(c->dims, c->bundle), ref = c->bundle == 1;
-    const bool free_running = (c->cfg.flags & GFS_F_DBG_FREE_RUNNING) != 0;
+    const gfs::KernelShape shape{s.dims, s.bundle, s.lds_tables, s.atomic_loads, s.trace};
+    const bool team = s.team, ref = s.bundle == 1;
+    const bool free_running = (s.flags & GFS_F_DBG_FREE_RUNNING) != 0;
     pl.iteration = iteration_kernel(shape);
-    if (c->phased) pl.window_iteration = iteration_kernel({0, 1, c->lds_tables, c->atomic_loads, trace});
-    const void *pooled_kernel = c->phased ? gfs::phased_fused_kernel(c->lds_tables) : (team || ref) ? fused_kernel(shape, true) : nullptr;
-    const void *free_kernel = team && !c->phased && free_running ? fused_kernel(shape, false) : nullptr;   // (K1e, K1d, K2d: pools only)
-    if (!pl.iteration || (c->phased && !pl.window_iteration) || ((team || ref) && !pooled_kernel) ||
-        (team && !c->phased && free_running && !free_kernel))
-        return fail(GFS_E_UNSUPPORTED, "no kernel is built for dims=" + std::to_string(c->dims) + " bundle=" + std::to_string(c->bundle) +
-                                           " lds_tables=" + std::to_string(c->lds_tables) + " atomic_loads=" + std::to_string(c->atomic_loads) +
-                                           " trace=" + std::to_string(trace) + " phased=" + std::to_string(c->phased));
-    if (team) {
-        // The fused launch has no grid barrier: a workgroup that does not fit on the chip beside the others would walk
-        // its whole schedule, early large-eta iterations included, after they have finished theirs — on a 525k-node graph
-        // 5 such waves of 4101 were enough to wreck the layout (relative error 64 at path distance 1:
-        // profiles/r02/streams_5_waves.log).  So the fused team kernel (sort and layout alike) is only launched with every
-        // workgroup resident: ask the runtime how many fit per CU with this block size and LDS table (33 KB of zeta table = 4
-        // blocks of 256 per CU, not 5), bound the automatic stream count by it, and run one launch per iteration when a caller
-        // asks for more streams.
-        int per_cu = 0;
+    if (s.phased) pl.window_iteration = iteration_kernel({0, 1, s.lds_tables, s.atomic_loads, s.trace});
+    const void *pooled_kernel = s.phased ? gfs::phased_fused_kernel(s.lds_tables) : (team || ref) ? fused_kernel(shape, true) : nullptr;
+    const void *free_kernel = team && !s.phased && free_running ? fused_kernel(shape, false) : nullptr;   // (K1e, K1d, K2d: pools only)
+    if (!pl.iteration || (s.phased && !pl.window_iteration) || ((team || ref) && !pooled_kernel) ||
+        (team && !s.phased && free_running && !free_kernel))
+        return fail(GFS_E_UNSUPPORTED, "no kernel is built for dims=" + std::to_string(s.dims) + " bundle=" + std::to_string(s.bundle) +
+                                           " lds_tables=" + std::to_string(s.lds_tables) + " atomic_loads=" + std::to_string(s.atomic_loads) +
+                                           " trace=" + std::to_string(s.trace) + " phased=" + std::to_string(s.phased));
+    int per_cu = 0;
+    if (team) {                                                            // (the measurement behind it: shape_after_residency)
         int rc = resident_blocks_per_cu(c, pooled_kernel, &per_cu);
         if (rc) return rc;
-        c->fused_resident_blocks = (uint64_t)std::max(per_cu, 0) * c->cu_count;
-        const uint64_t resident = c->fused_resident_blocks * c->block;
-        if (!c->cfg.n_streams && c->n_streams > resident && resident >= 64) c->n_streams = resident;
     }
-    // One persistent launch for a range where a fused kernel exists: the team kernels above and reference streams in any
-    // dimension (K1d / K2d).  The waves of a fused launch draw an iteration's updates from a work pool (a share per counter
-    // beyond 2^31 — 3e10 updates per iteration — cannot be pooled: one launch per iteration then, unless the diagnostic
-    // GFS_F_DBG_FREE_RUNNING asks for round 1's fixed quotas).  The team kernel is only fused with every workgroup resident —
-    // which assumes this context has the device to itself: concurrent streams or a second rank on the same device can delay a
-    // workgroup, harmlessly under pools (a late wave finds the counters exhausted and leaves), not so with fixed quotas.
-    const uint64_t n_waves = (c->n_streams + 63) / 64;
-    // (layouts draw an iteration from ONE counter, sgd_nd_team.h K2c: the whole iteration must stay below 2^31)
-    const bool pool_ok = n_waves <= 0xFFFFFFFFull &&
-                         c->quota_total / (c->dims != 0 && c->bundle > 1 ? 1u : gfs::pool_slots((uint32_t)n_waves)) < (1ull << 31);
-    const bool team_fusable = team && (c->phased ? pool_ok && !free_running : pool_ok || free_running) &&
-                              (c->n_streams + c->block - 1) / c->block <= c->fused_resident_blocks;   // every workgroup resident
-    pl.pooled = pool_ok && !(free_running && c->bundle > 1);
-    if ((team_fusable || (ref && pool_ok)) && c->atomic_loads && !trace && !(c->cfg.flags & GFS_F_NO_FUSE))
-        pl.fused = pl.pooled ? pooled_kernel : free_kernel;
-    // A range of ONE layout iteration is drawn from the pool too where it is at least four chunks per wave: with fixed quotas a layout
-    // launch's waves finish as far apart as their leaders' costs are (C4: 2.33 ms per iteration against 2.21 pooled, 2.04 inside
-    // a fused range).  Not with shorter chunks for smaller iterations: the layout pool is ONE counter, and it takes ~2e7 claims/s
-    // comfortably and 4e7 not (C4 in chunks of 1024 / 512 / 256: 2.41 / 3.05 / 5.24 ms).  Not for the sort either: its launches of
-    // one iteration are short (C3: 0.16 ms with fixed quotas, 0.15 pooled in chunks of 1024, 0.10 inside a fused range)
-    // (profiles/r03/one_iteration_launch_probe.log, launch_overhead_probe.log).
-    pl.one_chunk = c->dims ? gfs::ND_TEAM_CHUNK : gfs::TEAM_CHUNK;
-    pl.fuse_one_probe = team_fusable && pool_ok;
-    pl.fuse_one = pl.fuse_one_probe && c->dims != 0 && c->quota_total / n_waves >= 4ull * pl.one_chunk;
-    return GFS_OK;
-}
-
-// Streams per launch when the caller leaves it to the library.
-static uint64_t auto_stream_count(const gfs_ctx *c, bool team) {
-    // Lanes per CU: each wave is a serial chain of memory round trips, so more chains raise throughput until the memory-side
-    // atomic units saturate.  Round 1 (profiles/r01/sweep_streams_final.log, defer_probe.log): C3 69.1 / 78.7 / 80.2 G
-    // updates/s at 512 / 768 / 976 lanes per CU, C4 layout flat from 768 up; reference streams flat within 5 % from 512 up.
-    // Round 2: the 1D team kernels run 4 waves per SIMD (128 VGPRs; twin trips keep three blocks of a trip in flight) = 1024
-    // lanes per CU; 5 waves (96 VGPRs) spill 58 registers and are slower (profiles/r02/two_partners.log).  The fused launch
-    // further bounds the count by the workgroups that are resident at once (setup_common).
-    // The layout team kernels live on registers (a twin trip holds six records and three ends' coordinates): built for 3 waves
-    // per SIMD (165 VGPRs at D = 2, nothing spilled) = 768 lanes per CU, for 2 from D = 3 up (176 at D = 3, 192-246 at D = 4..8)
-    // = 512 (sgd_nd_team.h nd_waves_for; round 2's kernel needed 203 and ran two).
-    const uint64_t chip = (uint64_t)c->cu_count * ((team && c->dims == 0) ? 1024 : (team && c->dims >= 2) ? 256u * (unsigned)gfs::nd_team_waves(c->dims) : 976);
-    // keep >= 8 updates per stream per batch on small graphs
-    const uint64_t by_work = ((c->quota_total + 7) / 8 + 63) / 64 * 64;
-    // and never more than one stream per 4 nodes (<= 0.5 in-flight terms per node): every in-flight
-    // term corrects its two nodes from positions read before the others landed, so with ~2 concurrent
-    // terms per node and mu clamped at 1 the corrections overshoot — a 6000-node graph of short paths
-    // diverged (stress 1e8) under 6784 reference streams and converges under 1024
-    // (profiles/r01/stream_cap_probe.log).  The team kernels tolerate three streams per 4 nodes: with the work pools of the
-    // fused launch, bubble graphs of 26k / 79k / 197k nodes keep their relative error at path distance 1 (0.194 / 0.206 /
-    // 0.192-0.197 against 0.198 / 0.208 / 0.191 at one stream per 2 nodes; reference streams 0.192 / 0.201 / 0.190) up to
-    // one stream per node and lose it at two (0.224 / 0.248 / 0.220), at 2.0 / 1.65 / 1.2 times the rate
-    // (profiles/r02/stream_cap_pools.log; round 1 allowed one per 2 nodes, measured with free-running waves whose drift
-    // cost precision by itself).  An explicit n_streams overrides this.
-    // Round 3 re-measured the bound (medium graphs leave the chip partly empty under it).  Bubble graphs of 66k / 131k / 302k
-    // nodes keep every octave of the relative error within 4 % of reference streams up to 1.5 streams per node and lose distance
-    // 1 at 2.0 (profiles/r03/stream_cap_probe.log) — but a window graph whose 16 paths each cover 5/8 of its 200k nodes loses its
-    // exact chain order at 1.0 per node (3-115 inversions) and is scrambled at 1.25 (profiles/r03/chain_cap_probe.log), where
-    // three per 4 nodes is exact on every graph tried.  The bound stays.
-    const uint64_t by_nodes = (team ? c->n_nodes * 3 / 4 : c->n_nodes / 4) / 64 * 64;
-    return std::max<uint64_t>(64, std::min(chip, std::min(by_work, by_nodes)));
-}
-
-// Sampling bundle: flags bits 16..23: 0 = auto, 1 = reference streams, 4..64 explicit (sgd_device.h).
-static int choose_bundle(gfs_ctx *c, int dims) {
-    const uint64_t T = c->n_streams;
-    uint32_t b = (c->cfg.flags >> 16) & 0xFFu;
-    const bool b_auto = b == 0;
-    if (b > 1 && (T % 64 != 0 || (b != 4 && b != 8 && b != 16 && b != 32 && b != 64)))
-        return fail(GFS_E_ARG, "bundled sampling needs n_streams % 64 == 0 and a bundle of 4, 8, 16, 32 or 64");
-    if (b > 1 && dims != 0 && b == 4)
-        return fail(GFS_E_UNSUPPORTED, "bundled layout kernels exist for 1..8 dimensions and bundles of 8..64");
-    if (b == 0) {
-        // auto (measured: profiles/r03/policy_sweep.log — bubble graphs of 16k...300k nodes, three seeds per cell, the relative
-        // error per octave of path distance against reference streams): on graphs of >= 16 384 nodes the widest bundle for
-        // which >= 95 % of the steps lie in paths of at least 4*B steps.  B = 64 with long runs is within 2-7 % of reference
-        // streams in every octave from 16k nodes up and 2-10 times faster; narrower bundles and runs of one trip are both slower
-        // and worse (+16...42 % at 64-127 steps from 131k nodes up: a run's two blocks move rigidly and leave a step at their edges,
-        // short runs have more edges).  Round 2's extra condition — ">= 4096 independent leader draws per iteration" — is gone:
-        // graphs with 37-99 leader draws per iteration are in that table and are as good as those with thousands; the run
-        // length, not the number of leaders, is what the quality follows (bounded below by a floor of 64 leaders, see K).
-        // Smaller graphs run reference streams: DRB1 (5k nodes) converged visibly slower with bundles (round 1).
-        // Layouts of 4..8 dimensions keep reference streams: their team kernels (sgd_kernels_nd_team_wide.hip) are reached with an
-        // explicit GFS_F_BUNDLE; whether auto should pick them rests on their rates and quality and is not decided here.
-        b = 1;
-        if (T % 64 == 0 && dims <= 3 && c->n_nodes >= 16384) {
-            for (uint32_t cand : {64u, 32u, 16u, 8u, 4u}) {
-                if (cand == 4u && dims != 0) continue;
-                uint64_t long_steps = 0;
-                for (uint32_t cnt : c->path_counts) if (cnt >= 4 * cand) long_steps += cnt;
-                if ((double)long_steps >= 0.95 * (double)c->n_steps) { b = cand; break; }
-            }
-        }
-    }
-    c->bundle = b;
-    // Long runs (sgd_device.h run_trips): flags bits 24..31, 0 = auto.  Only the team kernels at B = 64 chain trips;
-    // auto = 64 trips (runs of up to 4096 steps, adapted per path): the relative error of the layout, measured per octave
-    // of path distance, is then within 10 % of reference streams on bubble graphs of 0.5M and 2M nodes — below it at
-    // short distances — for the oracle's mirror and on the GPU (profiles/r02/quality_probe_long_runs.log).
-    uint32_t k = (c->cfg.flags >> 24) & 0xFFu;
-    if (k > 64 || (k & (k - 1))) return fail(GFS_E_ARG, "GFS_F_CHAIN: the run length in trips must be a power of two <= 64");
-    // (layout kernels: 16 — on C4 runs of 64 trips cost 13 % of the rate, 30.8 against 34.2-35.5 G updates/s, and the error
-    // profile of the 2-D layout is already below reference streams' at 16: profiles/r02/quality_probe_layout_k.log)
-    const bool k_auto = k == 0;
-    if (k == 0) k = dims ? 16 : 64;
-    // Two partners per leader (sgd_device.h Leader): the team kernels at B = 64 (1D; layouts of 2 and more dimensions), unless
-    // GFS_F_ONE_PARTNER
-    c->partners = (b == 64 && has_fused_team_kernel(dims, b) && !(c->cfg.flags & GFS_F_ONE_PARTNER)) ? 2u : 1u;
-    // ... auto: and short enough that an iteration still draws >= 64 leaders (a leader stands for up to 64 * K * partners
-    // terms): at 16k nodes runs of 32 trips left 37 leaders per iteration and +6 % at path distance 1, runs of 16 (74 leaders)
-    // +1 %; from 32k nodes up 37 leaders were within 3 % (same table).  Binds only below ~500k steps.
-    // (only where the library picked the bundle as well: an explicit GFS_F_BUNDLE(64) keeps 64 / 16)
-    if (k_auto && b_auto && b == 64) while (k > 1 && c->quota_total / (64ull * k * c->partners) < 64) k >>= 1;
-    c->chain = b == 64 ? k : 1;
+    gfs::shape_after_residency(per_cu, gfs::DeviceFacts{c->cu_count}, &s);
+    if (s.fused) pl.fused = s.pooled ? pooled_kernel : free_kernel;
     return GFS_OK;
 }
 
 static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs_launch_config *cfg,
                         const double *etas, const double *zetas) {
     if (!c) return fail(GFS_E_ARG, "ctx is null");
-    int rc = check_params(p);
-    if (rc) return rc;
-    if (dims < 0 || dims > GFS_MAX_DIMS) return fail(GFS_E_UNSUPPORTED, "dimensions must be 1..8");
-    if (cfg && (cfg->flags & GFS_F_PHASED)) {
-        if (dims != 0) return fail(GFS_E_ARG, "GFS_F_PHASED is a sampler of the 1D sort: layouts have none");
-        const uint32_t b = (cfg->flags >> 16) & 0xFFu;
-        if (b != 0 && b != 64) return fail(GFS_E_ARG, "GFS_F_PHASED switches between reference streams and bundles of 64: GFS_F_BUNDLE must be 0 or 64");
-    }
+    std::string err;
+    int rc = gfs::check_setup_args(p, dims, cfg, &err);                    // (refused before the context is touched)
+    if (rc) return fail(rc, err);
     HIPCHK(hipSetDevice(c->device));
     free_sgd_state(c);
-    c->phased = false; c->win_begin = c->win_end = 0;
+    c->shape = gfs::LaunchShape{};
+    c->plan = LaunchPlan{};
     c->params = *p;
     c->cfg = cfg ? *cfg : gfs_launch_config{};
     c->dims = dims;
@@ -665,6 +292,14 @@ static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs
     c->x_owned = true;
     if (!c->valid_paths) { c->configured = true; return GFS_NOTHING_TO_DO; }
 
+    // launch shape (launch_policy.h): decided before anything of the run's state is allocated
+    const gfs::GraphFacts graph{c->n_nodes, c->n_steps, c->n_paths, c->max_path_steps, c->valid_paths, c->path_counts.data()};
+    rc = gfs::shape_before_residency(graph, gfs::DeviceFacts{c->cu_count}, p, dims, cfg, &c->shape, &err);
+    if (rc) return fail(rc, err);
+    rc = plan_launches(c);                                               // (may lower n_streams)
+    if (rc) return rc;
+    const uint64_t n_streams = c->shape.n_streams;
+
     // eta schedule and zeta table (host, bit-exact) unless supplied
     c->etas.resize(p->iter_max + 1);
     if (etas) std::copy(etas, etas + p->iter_max + 1, c->etas.begin());
@@ -672,50 +307,20 @@ static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs
     rc = upload_zeta_table(c, p, zetas);
     if (rc) return rc;
 
-    // launch shape
-    c->quota_total = c->cfg.term_updates_per_iteration ? c->cfg.term_updates_per_iteration : p->min_term_updates;
-    c->block = c->cfg.block_size ? c->cfg.block_size : 256;
-    if (c->block % 64 || c->block > 1024) return fail(GFS_E_ARG, "block_size must be a multiple of 64, <= 1024");
-    uint64_t T = c->cfg.n_streams ? c->cfg.n_streams : auto_stream_count(c, false);
-    if (T > 0x7FFFFFFFull) return fail(GFS_E_ARG, "n_streams too large");
-    c->n_streams = T;
-    if (c->quota_total / T + 1 > 0xFFFFFFFFull) return fail(GFS_E_UNSUPPORTED, "per-stream quota exceeds 2^32");
-    if (c->cfg.attempt_factor == 0) c->cfg.attempt_factor = 64;
-    if (c->cfg.attempt_factor > 0xFFFFFFFFull) return fail(GFS_E_ARG, "attempt_factor too large");
-    rc = choose_bundle(c, dims);
-    if (rc) return rc;
-    if (!c->cfg.n_streams && c->bundle > 1) c->n_streams = T = auto_stream_count(c, true);   // both counts are multiples of 64
-    if (c->cfg.flags & GFS_F_PHASED) {
-        // the phased sampler where the team sampler at B = 64 runs; where the policy picked reference streams every iteration is
-        // theirs already (the window is the whole schedule, the run the default's), and other bundles have no phased kernel
-        c->phased = c->bundle == 64;
-        if (c->phased) gfs_phase_window(p, &c->win_begin, &c->win_end);
-        else if (c->bundle == 1) { c->win_begin = 0; c->win_end = p->iter_max + 1; }
-    }
-    if (dims != 0 && c->bundle > 1 && c->block > 256)
-        return fail(GFS_E_ARG, "the layout team kernels are built for workgroups of at most 256 lanes");
-    c->atomic_loads = !(c->cfg.flags & GFS_F_PLAIN_LOADS);
-    size_t lds = (size_t)c->n_paths * sizeof(uint4) + (size_t)c->zlen_staged * 8;
-    c->lds_tables = !(c->cfg.flags & GFS_F_NO_LDS_TABLES) && lds <= 48 * 1024;
-    c->lds_bytes = c->lds_tables ? lds : 0;
-    rc = plan_launches(c);                                               // (may lower n_streams)
-    if (rc) return rc;
-    T = c->n_streams;
-
-    HIPCHK(hipMalloc(&c->d_rng, 4 * T * 8));
-    if (c->bundle > 1) {                                                 // team kernels, sort and layout
-        HIPCHK(hipMalloc(&c->d_lead, 8 * T * sizeof(uint32_t)));
-        HIPCHK(hipMemset(c->d_lead, 0, 8 * T * sizeof(uint32_t)));      // trips left = 0: no pass yet
+    HIPCHK(hipMalloc(&c->d_rng, 4 * n_streams * 8));
+    if (c->shape.bundle > 1) {                                           // team kernels, sort and layout
+        HIPCHK(hipMalloc(&c->d_lead, 8 * n_streams * sizeof(uint32_t)));
+        HIPCHK(hipMemset(c->d_lead, 0, 8 * n_streams * sizeof(uint32_t)));      // trips left = 0: no pass yet
     }
     HIPCHK(hipMalloc(&c->d_counters, kCounterBytes));
     if (c->cfg.trace_per_stream) {
-        HIPCHK(hipMalloc(&c->d_trace, T * c->cfg.trace_per_stream * sizeof(gfs_term)));
-        HIPCHK(hipMemset(c->d_trace, 0, T * c->cfg.trace_per_stream * sizeof(gfs_term)));
-        HIPCHK(hipMalloc(&c->d_trace_cnt, T * sizeof(uint32_t)));
+        HIPCHK(hipMalloc(&c->d_trace, n_streams * c->cfg.trace_per_stream * sizeof(gfs_term)));
+        HIPCHK(hipMemset(c->d_trace, 0, n_streams * c->cfg.trace_per_stream * sizeof(gfs_term)));
+        HIPCHK(hipMalloc(&c->d_trace_cnt, n_streams * sizeof(uint32_t)));
     }
     rc = seed_streams(c);
     if (rc) return rc;
-    if ((has_fused_team_kernel(dims, c->bundle) || c->bundle == 1) && c->params.iter_max < (1u << 20)) {
+    if ((c->shape.team || c->shape.bundle == 1) && c->params.iter_max < (1u << 20)) {
         // the whole schedule's per-iteration constants, for fused launches over consecutive iterations
         HIPCHK(hipMalloc(&c->d_its_all, (c->params.iter_max + 1) * sizeof(gfs::IterConsts)));
         rc = upload_schedule(c);
@@ -958,7 +563,7 @@ int gfs_ctx_reset_streams(gfs_ctx *c) {
     if (!c || !c->d_rng) return fail(GFS_E_STATE, "context not set up");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipDeviceSynchronize());
-    if (c->d_lead) HIPCHK(hipMemset(c->d_lead, 0, 8 * c->n_streams * sizeof(uint32_t)));
+    if (c->d_lead) HIPCHK(hipMemset(c->d_lead, 0, 8 * c->shape.n_streams * sizeof(uint32_t)));
     return seed_streams(c);
 }
 
@@ -967,36 +572,31 @@ static void fill_kargs(const gfs_ctx *c, gfs::KArgs &a) {
     a.zetas = c->d_zetas; a.x = c->d_x; a.rng = c->d_rng; a.counters = c->d_counters;
     a.trace = c->d_trace; a.trace_cnt = c->d_trace_cnt; a.lead = c->d_lead;
     a.n_steps = c->n_steps;
-    const bool wide = c->n_steps > 0xFFFFFFFFull || (c->cfg.flags & GFS_F_DBG_WIDE_INDEX);
+    const bool wide = gfs::wide_index(c->n_steps, c->cfg.flags);
     a.steps_thresh = wide ? (0ull - c->n_steps) % c->n_steps
                           : (uint64_t)((uint32_t)(0u - (uint32_t)c->n_steps) % (uint32_t)c->n_steps);
     a.n_paths = (uint32_t)c->n_paths;
-    a.zlen_full = (uint32_t)c->zlen_full; a.zlen_staged = (uint32_t)c->zlen_staged;
-    a.n_streams = (uint32_t)c->n_streams;
-    a.quota_base = (uint32_t)(c->quota_total / c->n_streams);
-    a.quota_rem = (uint32_t)(c->quota_total % c->n_streams);
-    a.attempt_factor = (uint32_t)c->cfg.attempt_factor;
+    a.zlen_full = (uint32_t)c->shape.zlen_full; a.zlen_staged = (uint32_t)c->shape.zlen_staged;
+    a.n_streams = (uint32_t)c->shape.n_streams;
+    a.quota_base = (uint32_t)(c->shape.quota_total / c->shape.n_streams);
+    a.quota_rem = (uint32_t)(c->shape.quota_total % c->shape.n_streams);
+    a.attempt_factor = (uint32_t)c->shape.attempt_factor;
     a.trace_per_stream = (uint32_t)c->cfg.trace_per_stream;
     a.space = (uint32_t)std::min<uint64_t>(c->params.space, 0xFFFFFFFFull);
     a.space_max = (uint32_t)std::min<uint64_t>(c->params.space_max, 0xFFFFFFFFull);
     a.space_q = (uint32_t)std::min<uint64_t>(c->params.space_quantization_step, 0xFFFFFFFFull);
     a.dbg = (c->cfg.flags >> 8) & 0x7Fu;             // bit 0x40 = GFS_F_DBG_WIDE_INDEX >> 8
     if (c->cfg.flags & GFS_F_DBG_NO_FUSED_TRIP) a.dbg |= 0x100u;     // (GFS_F_DBG_NO_TWIN_TRIP 0x400 arrives as dbg bit 0x04)
-    a.bundle = c->bundle;
-    a.chain = c->chain;
-    a.partners = c->partners;
+    a.bundle = c->shape.bundle;
+    a.chain = c->shape.chain;
+    a.partners = c->shape.partners;
     a.dbg2 = 0;
     if (const char *e = std::getenv("GFS_DBG2")) a.dbg2 = (uint32_t)std::atol(e);
     a.chunk = c->dims ? gfs::ND_TEAM_CHUNK : gfs::TEAM_CHUNK;
     a.ref_chunk = gfs::REF_CHUNK_PER_LANE;
     if (const char *e = std::getenv("GFS_DBG_REF_CHUNK")) { const long v = std::atol(e); if (v >= 1 && v <= 4096) a.ref_chunk = (uint32_t)v; }   // probe knob (scripts/ref_fused_probe.py)
     a.n_nodes = (uint32_t)c->n_nodes;
-    {   // crowding onset (sgd_device.h crowd_shift): four times the concurrency of an average node
-        const uint64_t per = c->n_steps / std::max<uint64_t>(2 * c->n_streams, 1);
-        int lg = 0; while ((per >> (lg + 1)) != 0) ++lg;               // floor(log2(max(per, 1)))
-        a.kshift = lg + 2;
-    }
-    if (c->kshift_override >= 0) a.kshift = c->kshift_override;
+    a.kshift = c->kshift_override >= 0 ? c->kshift_override : gfs::crowd_kshift(c->n_steps, c->shape.n_streams);
 }
 
 static int next_event_pair(gfs_ctx *c, std::pair<hipEvent_t, hipEvent_t> *&ev) {
@@ -1028,8 +628,8 @@ int gfs_ctx_run_iteration(gfs_ctx *c, uint64_t k, void *hip_stream) {
     hipStream_t st = (hipStream_t)hip_stream;
     gfs::KArgs a{};
     fill_kargs(c, a);
-    iter_consts(c, k, a.it);
-    const bool window = in_window(c, k);                                   // GFS_F_PHASED: the window's iterations are K1's
+    a.it = iter_consts(c, k);
+    const bool window = gfs::in_window(c->shape, k);                                 // GFS_F_PHASED: the window's iterations are K1's
     if (window) a.bundle = 1;
     std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
     int rc = next_event_pair(c, ev);
@@ -1045,19 +645,19 @@ int gfs_ctx_run_iteration(gfs_ctx *c, uint64_t k, void *hip_stream) {
 
 // A range of iterations ks[0..n) (each in 0..=iter_max): ONE fused launch for the team kernels (sgd1d_team_fused_kernel; layouts of 2
 // and more dimensions at B = 64: sgdnd_team_fused_kernel) and for reference streams (sgd1d_fused_kernel, sgdnd_fused_kernel); otherwise one
-// launch per iteration.  Which of the two, with which kernel, is the context's plan (plan_launches); only the length of the range
-// and the probe knobs are looked at here.
+// launch per iteration.  Which of the two, with which kernel, is the context's shape and plan (launch_policy.h, plan_launches); only
+// the length of the range and the probe knobs are looked at here.
 int gfs_ctx_run_range(gfs_ctx *c, const uint64_t *ks, uint64_t n, void *hip_stream) {
     if (!c || (!ks && n)) return fail(GFS_E_ARG, "null argument");
     if (!c->configured) return fail(GFS_E_STATE, "context not set up");
     if (!c->valid_paths || c->n_nodes == 0) return GFS_NOTHING_TO_DO;
     for (uint64_t i = 0; i < n; ++i) if (ks[i] > c->params.iter_max) return fail(GFS_E_ARG, "iteration beyond iter_max");
     const LaunchPlan &pl = c->plan;
-    uint32_t one_chunk = pl.one_chunk;
-    bool fuse_one = pl.fuse_one;
+    uint32_t one_chunk = c->shape.one_chunk;
+    bool fuse_one = c->shape.fuse_one;
     if (const char *e = std::getenv("GFS_DBG_ONE_CHUNK")) {               // probe knob (scripts/one_iteration_launch_probe.py): also for the sort
         const long v = std::atol(e);
-        if (v >= 64 && v <= 4096 && !(v & (v - 1))) { one_chunk = (uint32_t)v; fuse_one = pl.fuse_one_probe; }
+        if (v >= 64 && v <= 4096 && !(v & (v - 1))) { one_chunk = (uint32_t)v; fuse_one = c->shape.fuse_one_probe; }
     }
     if (!pl.fused || n == 0 || (n == 1 && !fuse_one) || n > 0xFFFFFFFFull) {
         for (uint64_t i = 0; i < n; ++i) { int rc = gfs_ctx_run_iteration(c, ks[i], hip_stream); if (rc) return rc; }
@@ -1083,7 +683,7 @@ int gfs_ctx_run_range(gfs_ctx *c, const uint64_t *ks, uint64_t n, void *hip_stre
         d_slice = c->d_its_all + ks[0];               // resident table: nothing to upload, nothing to wait for
     } else {
         std::vector<gfs::IterConsts> its(n);
-        for (uint64_t i = 0; i < n; ++i) iter_consts(c, ks[i], its[i]);
+        for (uint64_t i = 0; i < n; ++i) its[i] = iter_consts(c, ks[i]);
         if (c->its_cap < n) {
             if (c->d_its) HIPCHK(hipFree(c->d_its));
             c->d_its = nullptr; c->its_cap = 0;
@@ -1096,15 +696,15 @@ int gfs_ctx_run_range(gfs_ctx *c, const uint64_t *ks, uint64_t n, void *hip_stre
     }
     gfs::KArgs a{};
     fill_kargs(c, a);
-    if (n == 1 && c->bundle > 1) a.chunk = one_chunk;
+    if (n == 1 && c->shape.bundle > 1) a.chunk = one_chunk;
     if (const char *e = std::getenv("GFS_DBG_CHUNK")) {                    // probe knob: the chunk of every fused team launch
         const long v = std::atol(e);
-        if (c->bundle > 1 && v >= 64 && v <= 16384 && !(v & (v - 1))) a.chunk = (uint32_t)v;
+        if (c->shape.bundle > 1 && v >= 64 && v <= 16384 && !(v & (v - 1))) a.chunk = (uint32_t)v;
     }
-    iter_consts(c, ks[0], a.it);
+    a.it = iter_consts(c, ks[0]);
     // work pools (sgd_kernel_common.h pool_walk): the waves draw an iteration's updates from shared counters, zeroed per launch
     uint32_t *pool = nullptr;
-    if (pl.pooled) {
+    if (c->shape.pooled) {
         if (c->pool_cap < n) {
             if (c->d_pool) HIPCHK(hipFree(c->d_pool));
             c->d_pool = nullptr; c->pool_cap = 0;
@@ -1159,7 +759,7 @@ int gfs_ctx_stats(gfs_ctx *c, gfs_stats *out) {
     std::vector<unsigned long long> cnt(kCounterBytes / 8);
     HIPCHK(hipMemcpy(cnt.data(), c->d_counters, kCounterBytes, hipMemcpyDeviceToHost));
     for (size_t s = 0; s < cnt.size(); s += 8) { out->term_updates += cnt[s]; out->attempts += cnt[s + 1]; }
-    out->iterations = c->iterations; out->n_streams = c->n_streams; out->bundle = c->bundle; out->run_trips = c->chain;
+    out->iterations = c->iterations; out->n_streams = c->shape.n_streams; out->bundle = c->shape.bundle; out->run_trips = c->shape.chain;
     double ms = c->kernel_ms_harvested;
     for (size_t k = 0; k < c->events_used; ++k) {
         float t = 0.f;
@@ -1172,7 +772,7 @@ int gfs_ctx_stats(gfs_ctx *c, gfs_stats *out) {
 int gfs_ctx_trace(gfs_ctx *c, gfs_term *out, uint64_t n_terms, uint64_t *counts, uint64_t n_streams) {
     if (!c || !out) return fail(GFS_E_ARG, "null argument");
     if (!c->d_trace) return fail(GFS_E_STATE, "trace_per_stream was 0");
-    if (n_terms != c->n_streams * c->cfg.trace_per_stream) return fail(GFS_E_ARG, "trace length mismatch");
+    if (n_terms != c->shape.n_streams * c->cfg.trace_per_stream) return fail(GFS_E_ARG, "trace length mismatch");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, c->d_trace, n_terms * sizeof(gfs_term), hipMemcpyDeviceToHost));
@@ -1185,10 +785,10 @@ int gfs_ctx_trace(gfs_ctx *c, gfs_term *out, uint64_t n_terms, uint64_t *counts,
         }
     }
     if (counts) {
-        if (n_streams != c->n_streams) return fail(GFS_E_ARG, "counts length mismatch");
-        std::vector<uint32_t> tmp(c->n_streams);
+        if (n_streams != c->shape.n_streams) return fail(GFS_E_ARG, "counts length mismatch");
+        std::vector<uint32_t> tmp(c->shape.n_streams);
         HIPCHK(hipMemcpy(tmp.data(), c->d_trace_cnt, tmp.size() * 4, hipMemcpyDeviceToHost));
-        for (uint64_t t = 0; t < c->n_streams; ++t) counts[t] = tmp[t];
+        for (uint64_t t = 0; t < c->shape.n_streams; ++t) counts[t] = tmp[t];
     }
     return GFS_OK;
 }
@@ -1207,7 +807,7 @@ int gfs_ctx_debug_kshift(gfs_ctx *c, int32_t set, int32_t *kshift_out) {
     if (!c) return fail(GFS_E_ARG, "ctx is null");
     if (set >= -1) c->kshift_override = set;                              // (set < -1: a query only)
     if (kshift_out) {
-        if (!c->configured || !c->n_streams) return fail(GFS_E_STATE, "context not set up");
+        if (!c->configured || !c->shape.n_streams) return fail(GFS_E_STATE, "context not set up");
         gfs::KArgs a{};
         fill_kargs(c, a);
         *kshift_out = a.kshift;
@@ -1221,8 +821,8 @@ int gfs_ctx_phase_window(gfs_ctx *c, int64_t set_begin, int64_t set_end, uint64_
     if (set_begin >= 0 || set_end >= 0) {
         if (set_begin < 0 || set_end < 0 || set_begin > set_end || (uint64_t)set_end > c->params.iter_max + 1)
             return fail(GFS_E_ARG, "phase window: need 0 <= begin <= end <= iter_max + 1");
-        if (!c->phased) return fail(GFS_E_STATE, "GFS_F_PHASED is a no-op on this context (the auto policy did not pick bundles of 64)");
-        c->win_begin = (uint64_t)set_begin; c->win_end = (uint64_t)set_end;
+        if (!c->shape.phased) return fail(GFS_E_STATE, "GFS_F_PHASED is a no-op on this context (the auto policy did not pick bundles of 64)");
+        c->shape.win_begin = (uint64_t)set_begin; c->shape.win_end = (uint64_t)set_end;
         if (c->d_its_all) {                                                // the resident schedule carries the window's marks
             HIPCHK(hipSetDevice(c->device));
             HIPCHK(hipDeviceSynchronize());
@@ -1230,8 +830,8 @@ int gfs_ctx_phase_window(gfs_ctx *c, int64_t set_begin, int64_t set_end, uint64_
             if (rc) return rc;
         }
     }
-    if (begin_out) *begin_out = c->win_begin;
-    if (end_out) *end_out = c->win_end;
+    if (begin_out) *begin_out = c->shape.win_begin;
+    if (end_out) *end_out = c->shape.win_end;
     return GFS_OK;
 }
 
@@ -1270,6 +870,24 @@ static int check_step_distances(const uint64_t *zs, uint64_t n_z, const gfs_pair
     for (uint64_t k = 0; k < n_z; ++k) if (zs[k] == 0) return fail(GFS_E_ARG, "a step distance of 0");
     return GFS_OK;
 }
+// the duration of an entry's device work on stderr under GFS_TIMING (one HIP event pair, destroyed however the entry returns)
+struct QualityTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipStream_t st;
+    explicit QualityTimer(hipStream_t s) : st(s) {
+        if (!std::getenv("GFS_TIMING")) return;
+        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, st) != hipSuccess) done();
+    }
+    void stop() { if (e0 && hipEventRecord(e1, st) != hipSuccess) done(); }
+    bool elapsed(float *ms) const { return e0 && hipEventElapsedTime(ms, e0, e1) == hipSuccess; }   // after the stream was synchronised
+    void report(const char *what, uint64_t z, uint64_t n_steps) const {
+        float ms = 0.f;
+        if (elapsed(&ms))
+            std::fprintf(stderr, "[%s] z = %llu, %llu steps: kernels %.4f ms\n", what, (unsigned long long)z, (unsigned long long)n_steps, ms);
+    }
+    void done() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); e0 = e1 = nullptr; }
+    ~QualityTimer() { done(); }
+};
 
 int gfs_ctx_pair_errors(gfs_ctx *c, const uint64_t *zs, uint64_t n_z, gfs_pair_error *out, void *hip_stream) {
     if (!c) return fail(GFS_E_ARG, "ctx is null");
@@ -1285,55 +903,23 @@ int gfs_ctx_pair_errors(gfs_ctx *c, const uint64_t *zs, uint64_t n_z, gfs_pair_e
     if (rc) return rc;
     uint64_t *d_zs = c->d_quality, *d_out = d_zs + n_z, *d_partials = d_out + 5 * n_z;
     HIPCHK(hipMemcpyAsync(d_zs, zs, n_z * 8, hipMemcpyHostToDevice, st));
-    const bool timing = std::getenv("GFS_TIMING") != nullptr;             // the kernels' duration on stderr (HIP events)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timing) { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventRecord(e0, st)); }
+    QualityTimer timer(st);
     hipError_t e = gfs::pair_errors_device(c->d_step_rec, c->n_steps, c->d_x, c->n_nodes, (uint32_t)c->dims, d_zs, (uint32_t)n_z,
                                            d_partials, d_out, st);
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("pair_errors_device: ") + hipGetErrorString(e));
-    if (timing) HIPCHK(hipEventRecord(e1, st));
+    timer.stop();
     std::vector<uint64_t> w(5 * n_z);
     HIPCHK(hipMemcpyAsync(w.data(), d_out, w.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (timing) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
+    float ms = 0.f;
+    if (timer.elapsed(&ms))
         std::fprintf(stderr, "[gfs_ctx_pair_errors] %llu step distances, %llu steps: kernels %.4f ms\n", (unsigned long long)n_z,
                      (unsigned long long)c->n_steps, ms);
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    }
     for (uint64_t k = 0; k < n_z; ++k) {
         out[k].step_distance = zs[k]; out[k].pairs = w[5 * k];
         std::memcpy(&out[k].sum_rel_sq, &w[5 * k + 1], 8); std::memcpy(&out[k].max_rel_sq, &w[5 * k + 2], 8);
         std::memcpy(&out[k].sum_abs, &w[5 * k + 3], 8); std::memcpy(&out[k].sum_sq, &w[5 * k + 4], 8);
     }
-    return GFS_OK;
-}
-
-// the step-drawing half of calculate_layout_stress (sgd.rs:1218-1250); host only
-int gfs_stress_sample_pairs(const gfs_graph_view *g, uint64_t sample_count, uint64_t seed, uint64_t *step_a, uint64_t *step_b,
-                            uint64_t *n_out) {
-    if (!g || !n_out || ((!step_a || !step_b) && sample_count)) return fail(GFS_E_ARG, "null argument");
-    *n_out = 0;
-    if (g->n_steps < 2) return GFS_OK;                                     // :1220
-    if (!g->path_first_step || g->n_paths == 0 || g->path_first_step[0] != 0 || g->path_first_step[g->n_paths] != g->n_steps)
-        return fail(GFS_E_ARG, "path_first_step must start at 0 and end at n_steps");
-    for (uint64_t p = 0; p < g->n_paths; ++p)
-        if (g->path_first_step[p + 1] < g->path_first_step[p]) return fail(GFS_E_ARG, "path_first_step not monotone");
-    Xo256p rng(seed);                                                      // :1218
-    uint64_t n = 0;
-    for (uint64_t k = 0; k < sample_count; ++k) {
-        const uint64_t a = rng.uniform_usize(g->n_steps);                  // :1230
-        // the path of step a: the last p with path_first_step[p] <= a (empty paths share a boundary)
-        const uint64_t p = (uint64_t)(std::upper_bound(g->path_first_step, g->path_first_step + g->n_paths, a) - g->path_first_step) - 1;
-        const uint64_t first = g->path_first_step[p], cnt = g->path_first_step[p + 1] - first;
-        if (cnt < 2) continue;                                             // :1234
-        const uint64_t rank_a = a - first, rank_b = rng.uniform_usize(cnt);   // :1238-1240
-        if (rank_a == rank_b) continue;                                    // :1242
-        step_a[n] = first + rank_a; step_b[n] = first + rank_b;
-        ++n;
-    }
-    *n_out = n;
     return GFS_OK;
 }
 
@@ -1400,24 +986,6 @@ static int check_diagnosis(uint64_t z, double ratio) {
     if (!(ratio >= 0.0)) return fail(GFS_E_ARG, "ratio must be a number >= 0");
     return GFS_OK;
 }
-// the duration of an entry's device work on stderr under GFS_TIMING (one HIP event pair, as gfs_ctx_pair_errors)
-struct QualityTimer {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipStream_t st;
-    explicit QualityTimer(hipStream_t s) : st(s) {
-        if (!std::getenv("GFS_TIMING")) return;
-        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, st) != hipSuccess) done();
-    }
-    void stop() { if (e0 && hipEventRecord(e1, st) != hipSuccess) done(); }
-    void report(const char *what, uint64_t z, uint64_t n_steps) {            // after the stream was synchronised
-        float ms = 0.f;
-        if (e0 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess)
-            std::fprintf(stderr, "[%s] z = %llu, %llu steps: kernels %.4f ms\n", what, (unsigned long long)z, (unsigned long long)n_steps, ms);
-    }
-    void done() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); e0 = e1 = nullptr; }
-    ~QualityTimer() { done(); }
-};
-
 int gfs_ctx_path_errors(gfs_ctx *c, uint64_t z, double ratio, gfs_path_error *out, uint64_t n_paths, void *hip_stream) {
     if (!c || (!out && n_paths)) return fail(GFS_E_ARG, "null argument");
     int rc = check_diagnosis(z, ratio);
@@ -1647,17 +1215,11 @@ struct gfs_batch {
 };
 
 static bool batch_item_idle(const gfs_ctx *c) { return !c->valid_paths || c->n_nodes == 0; }
+static bool batch_eligible(const gfs_ctx *c) {
+    return gfs::batch_eligible(c->shape, c->cfg.trace_per_stream != 0, c->d_its_all != nullptr, batch_item_idle(c));
+}
 
 extern "C" {
-
-int gfs_batch_plan(const uint64_t *blocks_of_item, uint64_t n, uint64_t max_blocks, uint32_t *launch_of_item, uint32_t *n_launches) {
-    if (!n_launches || (n && (!blocks_of_item || !launch_of_item))) return fail(GFS_E_ARG, "null argument");
-    const uint64_t bad = gfs::batch_plan(blocks_of_item, n, max_blocks, launch_of_item, n_launches);
-    if (bad < n)
-        return fail(GFS_E_UNSUPPORTED, "batch item " + std::to_string(bad) + ": its " + std::to_string(blocks_of_item[bad]) +
-                                           " workgroups exceed the " + std::to_string(max_blocks) + " of one launch");
-    return GFS_OK;
-}
 
 void gfs_batch_destroy(gfs_batch *b) {
     if (!b) return;
@@ -1705,16 +1267,16 @@ int gfs_batch_create(gfs_ctx *const *ctxs, uint64_t n, const gfs_batch_config *c
         if (batch_item_idle(c)) continue;                                  // counted, not run
         if (!gfs::batch_fused_kernel(c->dims, true))
             return refuse(GFS_E_UNSUPPORTED, i, "no batch kernel is built for dims=" + std::to_string(c->dims) + " (1D sorts, layouts of 2 and 3 dimensions)");
-        if (c->bundle != 1 || c->phased || !c->plan.fused || !c->plan.pooled || c->cfg.trace_per_stream || !c->d_its_all)
-            return refuse(GFS_E_UNSUPPORTED, i, "its plan is not the pooled fused reference-stream kernel (bundle=" + std::to_string(c->bundle) +
-                                                    " phased=" + std::to_string(c->phased) + " fused=" + std::to_string(c->plan.fused != nullptr) +
+        if (!batch_eligible(c))
+            return refuse(GFS_E_UNSUPPORTED, i, "its plan is not the pooled fused reference-stream kernel (bundle=" + std::to_string(c->shape.bundle) +
+                                                    " phased=" + std::to_string(c->shape.phased) + " fused=" + std::to_string(c->shape.fused) +
                                                     " trace=" + std::to_string(c->cfg.trace_per_stream != 0) + ")");
         if (c->params.iter_max + 1 > 4096 || c->params.iter_max + 1 == 0)
             return refuse(GFS_E_UNSUPPORTED, i, "iter_max + 1 exceeds the 4096 iterations of one fused launch");
-        if (have_block && c->block != b->block)
-            return refuse(GFS_E_UNSUPPORTED, i, "block size " + std::to_string(c->block) + ", earlier items have " + std::to_string(b->block));
-        b->block = c->block; have_block = true;
-        (c->lds_tables ? with_lds : without_lds).push_back(i);
+        if (have_block && c->shape.block != b->block)
+            return refuse(GFS_E_UNSUPPORTED, i, "block size " + std::to_string(c->shape.block) + ", earlier items have " + std::to_string(b->block));
+        b->block = c->shape.block; have_block = true;
+        (c->shape.lds_tables ? with_lds : without_lds).push_back(i);
     }
     // ---- device from here on ----
     auto bail = [&](const char *what, hipError_t e) {
@@ -1730,11 +1292,11 @@ int gfs_batch_create(gfs_ctx *const *ctxs, uint64_t n, const gfs_batch_config *c
         size_t lds_max = 0;
         std::vector<uint64_t> blocks;
         for (uint64_t i : *group) {
-            lds_max = std::max(lds_max, ctxs[i]->lds_bytes);
-            blocks.push_back((ctxs[i]->n_streams + b->block - 1) / b->block);
+            lds_max = std::max(lds_max, ctxs[i]->shape.lds_bytes);
+            blocks.push_back((ctxs[i]->shape.n_streams + b->block - 1) / b->block);
         }
         // Every workgroup of a launch is resident at once: a graph whose workgroups start late would walk its early, large-eta
-        // iterations after the others have finished theirs (plan_launches has the measurement for the team kernels).
+        // iterations after the others have finished theirs (launch_policy.h shape_after_residency has the measurement for the team kernels).
         uint64_t max_blocks = cfg ? cfg->max_blocks_per_launch : 0;
         if (!max_blocks) {
             int per_cu = 0;
@@ -1758,12 +1320,12 @@ int gfs_batch_create(gfs_ctx *const *ctxs, uint64_t n, const gfs_batch_config *c
             BatchLaunch &l = b->launches[base + launch_of[k]];
             if (l.count == 0) { l.first = b->run.size(); l.lds_tables = lds_tables; l.block_offset = b->total_blocks; }
             l.count++; l.blocks += blocks[k];
-            if (lds_tables) l.lds_bytes = std::max(l.lds_bytes, ctxs[(*group)[k]]->lds_bytes);
+            if (lds_tables) l.lds_bytes = std::max(l.lds_bytes, ctxs[(*group)[k]]->shape.lds_bytes);
             b->run.push_back((*group)[k]);
             b->pool_offset.push_back(b->pool_words);
             b->item_blocks.push_back(blocks[k]);
             b->item_iters.push_back(ctxs[(*group)[k]]->params.iter_max + 1);
-            b->item_lds.push_back(lds_tables ? ctxs[(*group)[k]]->lds_bytes : 0);
+            b->item_lds.push_back(lds_tables ? ctxs[(*group)[k]]->shape.lds_bytes : 0);
             b->pool_words += gfs::pool_bytes(ctxs[(*group)[k]]->params.iter_max + 1) / sizeof(uint32_t);
             b->total_blocks += blocks[k];
         }
@@ -1790,12 +1352,11 @@ int gfs_batch_run(gfs_batch *b, void *hip_stream) {
     // the launches, the block table and the pools were sized at create: a context set up again since then no longer fits them
     for (size_t r = 0; r < b->run.size(); ++r) {
         const gfs_ctx *c = b->ctxs[b->run[r]];
-        const bool same_plan = c->dims == b->dims && c->block == b->block && c->bundle == 1 && !c->phased && c->plan.fused && c->plan.pooled &&
-                               !c->cfg.trace_per_stream && c->d_its_all && !batch_item_idle(c) &&
-                               (c->lds_tables ? c->lds_bytes : 0) == b->item_lds[r];
-        if (!same_plan || (c->n_streams + b->block - 1) / b->block != b->item_blocks[r] || c->params.iter_max + 1 != b->item_iters[r])
+        const bool same_plan = c->dims == b->dims && c->shape.block == b->block && batch_eligible(c) &&
+                               (c->shape.lds_tables ? c->shape.lds_bytes : 0) == b->item_lds[r];
+        if (!same_plan || (c->shape.n_streams + b->block - 1) / b->block != b->item_blocks[r] || c->params.iter_max + 1 != b->item_iters[r])
             return fail(GFS_E_STATE, "batch item " + std::to_string(b->run[r]) + ": set up again since the batch was created (" +
-                                         std::to_string(c->n_streams) + " streams, iter_max " + std::to_string(c->params.iter_max) + ")");
+                                         std::to_string(c->shape.n_streams) + " streams, iter_max " + std::to_string(c->params.iter_max) + ")");
     }
     auto t0 = std::chrono::steady_clock::now();
     HIPCHK(hipSetDevice(b->device));
@@ -1808,7 +1369,7 @@ int gfs_batch_run(gfs_batch *b, void *hip_stream) {
             gfs::BatchItem &it = b->h_items[r];
             it = gfs::BatchItem{};
             fill_kargs(c, it.a);
-            iter_consts(c, 0, it.a.it);
+            it.a.it = iter_consts(c, 0);
             it.its = c->d_its_all;
             it.pool = b->d_pool + b->pool_offset[r];
             it.n_iters = (uint32_t)(c->params.iter_max + 1);

@@ -310,13 +310,6 @@ gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbos
     return bs;
 }
 
-static uint64_t splitmix64(uint64_t &s) {
-    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 std::vector<double> default_layout_init(const FlatGraph &f, size_t D, uint64_t seed) {
     // the reference's own start (sgd.rs:829-853): dimension 0 = bp prefix, dimensions >= 1 = StandardNormal * sqrt(2N)
     // from one Xoshiro256+ seeded `seed` (gfs_init_layout restates rand_distr's ziggurat: parity unpinned)
@@ -348,48 +341,26 @@ Layout path_linear_sgd_layout(const BidirectedGraph &g, const LayoutSGDParams &p
 }
 
 // ---- calculate_layout_stress (sgd.rs:1196-1283) -----------------------------------------------------
-namespace {
-struct Xo {
-    uint64_t s[4];
-    explicit Xo(uint64_t seed) { uint64_t sm = seed; for (auto &v : s) v = splitmix64(sm); }
-    uint64_t next() {
-        uint64_t r = s[0] + s[3], t = s[1] << 17;
-        s[2] ^= s[0]; s[3] ^= s[1]; s[1] ^= s[2]; s[0] ^= s[3]; s[2] ^= t;
-        s[3] = (s[3] << 45) | (s[3] >> 19);
-        return r;
-    }
-    uint64_t uniform(uint64_t n) {                                   // rand 0.9 Uniform<usize>(0,n)
-        if (n <= 0xFFFFFFFFull) {
-            uint32_t range = (uint32_t)n, thresh = (uint32_t)(0u - range) % range;
-            for (;;) { uint64_t m = (uint64_t)(uint32_t)(next() >> 32) * range; if ((uint32_t)m >= thresh) return m >> 32; }
-        }
-        uint64_t thresh = (0ull - n) % n;
-        for (;;) { unsigned __int128 m = (unsigned __int128)next() * n; if ((uint64_t)m >= thresh) return (uint64_t)(m >> 64); }
-    }
-};
-}  // namespace
-
 double calculate_layout_stress(const BidirectedGraph &g, const Layout &layout, size_t sample_count) {
     FlatGraph f = g.flatten();
     const size_t S = f.step_node.size();
     if (S < 2) return 0.0;
-    std::vector<uint64_t> pos(S); std::vector<uint32_t> pth(S);
+    std::vector<uint64_t> pos(S);
     for (size_t p = 0; p + 1 < f.path_first_step.size(); ++p) {
         uint64_t position = 0;
         for (uint64_t s = f.path_first_step[p]; s < f.path_first_step[p + 1]; ++s) {
-            pos[s] = position; pth[s] = (uint32_t)p;
+            pos[s] = position;
             if (f.step_node[s] != GFS_NO_NODE) position += f.node_len[f.step_node[s]];
         }
     }
-    Xo rng(12345);
+    // the pairs: the library's restatement of the reference's draws (seed 12345; host only, no device needed)
+    std::vector<uint64_t> step_a(sample_count), step_b(sample_count);
+    uint64_t n_pairs = 0;
+    gfs_graph_view v = f.view();
+    check(gfs_stress_sample_pairs(&v, sample_count, 12345, step_a.data(), step_b.data(), &n_pairs));
     double sum = 0.0; uint64_t count = 0;
-    for (size_t k = 0; k < sample_count; ++k) {
-        uint64_t a = rng.uniform(S);
-        uint64_t p = pth[a], first = f.path_first_step[p], cnt = f.path_first_step[p + 1] - first;
-        if (cnt < 2) continue;
-        uint64_t ra = a - first, rb = rng.uniform(cnt);
-        if (ra == rb) continue;
-        uint64_t sa = first + ra, sb = first + rb;
+    for (uint64_t k = 0; k < n_pairs; ++k) {
+        const uint64_t sa = step_a[k], sb = step_b[k];
         double path_dist = std::fabs((double)pos[sa] - (double)pos[sb]);
         if (path_dist == 0.0) continue;
         uint32_t ia = f.step_node[sa], ib = f.step_node[sb];

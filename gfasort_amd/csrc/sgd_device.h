@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "sgd_limits.h"
 
 namespace gfs {
 
@@ -70,17 +71,7 @@ struct Rng {
     }
 };
 
-// ---- launch-uniform constants of one SGD batch (host-computed, bit-exact) ----------------
-struct IterConsts {
-    double   eta;          // etas[k]                                        sgd.rs:389,519
-    double   zeta2theta;   // 1.0 + fpp(0.5, theta_cur)  (also the 2nd fast-path bound) :471,143
-    double   omt_fb;       // (1 - theta_cur) split for fpp(2/n, 1-theta)               :133
-    double   alpha_fb;     // alpha = 1/(1-theta_cur) split for fpp(.., alpha)          :132,148
-    int32_t  omt_e;
-    int32_t  alpha_e;
-    int32_t  cooling;      // k > first_cooling_iteration                               :393-396
-    int32_t  _pad;
-};
+// (IterConsts, the launch-uniform constants of one SGD batch that the host computes: sgd_limits.h)
 
 // device mirror of PathIndex (sgd.rs:14-31), flattened:
 //   step_rec[s]  = { node slot | NO_NODE, path id (31 bits) | rev<<31, pos lo, pos hi (23 bits) | crowding a<<23 b<<29 }  (16 B)
@@ -130,7 +121,7 @@ __device__ __forceinline__ uint32_t rec_path(const uint4 &r) { return r.y & PATH
 
 // Crowded nodes.  The kernels run ~2.5e5 terms at once where the reference runs <= 64, and a term corrects its two
 // nodes from positions read before the other in-flight terms landed.  For an ordinary node that is at most one or two
-// concurrent corrections (the streams-per-node bound, capi.hip); but a node that carries a large share of all steps
+// concurrent corrections (the streams-per-node bound, launch_policy.h); but a node that carries a large share of all steps
 // (a hub), or that a path steps on many times in a row (a tandem repeat: a run of 64 consecutive steps then hits it
 // with many lanes of the SAME trip), receives dozens of full corrections of the same error at once and the positions
 // blow up (measured: NaN on graphs with 40-fold self-loops, profiles/r01/repeat_probe.log).  Every step record
@@ -273,12 +264,7 @@ __device__ __forceinline__ uint32_t leader_ok(uint32_t okw, uint32_t p) { return
 // both terms of a lane from one load of its a-side record and position, with one add for the a-side (TWIN trip,
 // sgd_kernels_1d.hip twin_trip): 3 blocks of records, position loads and atomic requests for 128 updates instead of 4.
 // The kernel is bound by the memory side's atomic units, then by HBM bytes; this takes a quarter off both.
-// A team wave works through an iteration in CHUNKS of this many updates (sgd_kernel_common.h, work pools); the rank cut-off
-// that makes a count exact applies at the end of every chunk.  2048 = 32 full trips.
-constexpr uint32_t TEAM_CHUNK = 2048;        // (the value of KArgs.chunk unless a probe says otherwise: capi.hip gfs_ctx_run_range)
-// ... and of this many in the layout kernels: their pool is ONE counter per iteration (sgd_kernels_nd_team.hip K2c), and half as many
-// claims are worth 3 % (C4: 49.5 -> 51.0 G updates/s; 8192: 50.8; profiles/r03/chunk_size_probe.log).  The sort is best at 2048.
-constexpr uint32_t ND_TEAM_CHUNK = 4096;
+// (A team wave works through an iteration in chunks of TEAM_CHUNK updates, ND_TEAM_CHUNK in the layout kernels: sgd_limits.h)
 
 // LONG RUNS.  A leader is expanded not over one trip but over K consecutive trips of its wave: trip `seg` takes the
 // steps seg*B .. seg*B+B-1 further along the path, all with the leader's jump, so a run is K*B consecutive steps.

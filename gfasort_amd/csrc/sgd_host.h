@@ -4,10 +4,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <string>
 #include <type_traits>
-
-int gfs_set_error(int code, const std::string &msg);      // capi.hip: sets gfs_last_error(), returns code
+#include "capi_error.h"                                   // gfs_set_error
+#include "sgd_limits.h"                                   // pool_bytes, nd_team_waves
 
 namespace gfs {
 
@@ -41,9 +40,6 @@ const void *fused_kernel_nd_team_wide(const KernelShape &s, bool pooled);   // s
 // Many contexts per launch, kernel(const BatchItem *items, const uint32_t *block_item) (sgd_batch.h): K1d's body (dims 0) or K2d's
 // (dims 2, 3) on the item that block_item[blockIdx.x] names.  Null for other dimensions.
 const void *batch_fused_kernel(int dims, bool lds_tables);                  // sgd_kernels_batch.hip: K1f, K2f
-
-size_t pool_bytes(uint64_t n_iters);                      // sgd_kernels_1d.hip
-int nd_team_waves(int dims);                              // sgd_kernels_nd_team.hip: waves per SIMD the layout team kernels are built for
 
 // HIP loads a translation unit's code object on first use: each of these touches one kernel of its unit (gfs_warmup)
 hipError_t warm_module_1d();

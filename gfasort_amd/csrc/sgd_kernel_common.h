@@ -17,6 +17,7 @@
 // loaded/stored coalesced (SoA) at entry/exit.
 #pragma once
 #include "sgd_device.h"
+#include "sgd_limits.h"
 
 namespace gfs {
 
@@ -48,8 +49,7 @@ __device__ __forceinline__ void stage_tables(const KArgs &a, unsigned char *smem
     }
 }
 
-constexpr uint32_t COUNTER_SLOTS = 1024;     // counters: [COUNTER_SLOTS][8] u64, [s][0] = updates, [s][1] = attempts
-
+// (COUNTER_SLOTS: sgd_limits.h)
 __device__ __forceinline__ void flush_counters(const KArgs &a, uint32_t done, uint32_t att) {
     // wave64 butterfly, one atomic per wave
     unsigned long long d = done, t = att;
@@ -222,15 +222,7 @@ __device__ __forceinline__ uint32_t merged_trip_base(uint32_t cnt, uint32_t ra0,
 // iteration still applies exactly min_term_updates updates with its own eta/theta.  C3: 97.8 G updates/s.
 // (A single wave claims every chunk itself, in order: the kernels with fixed quotas work through their quota in the same
 // chunks, so that one wave is bit for bit the oracle's mirror in both.)
-constexpr uint32_t POOL_SLOTS = 16, POOL_STRIDE = 16;              // counters per iteration; u32 per 64-B line
-// Counters in use: one per 16 waves, at most POOL_SLOTS.  Several counters exist so that 4 000 waves do not queue on one
-// address; a counter must still be SHARED by many waves — a wave with a counter of its own has a fixed quota again and drifts
-// away from the others in the schedule (a 40-lane last wave beside 15 full ones, each on its own counter, ran 60 % behind and
-// cost DRB1 a fifth of its final stress: 0.39 against 0.33, round 3).
-__host__ __device__ __forceinline__ uint32_t pool_slots(uint32_t n_waves) {
-    const uint32_t s = n_waves / 16u;
-    return s < 1u ? 1u : (s > POOL_SLOTS ? POOL_SLOTS : s);
-}
+// (POOL_SLOTS, POOL_STRIDE and pool_slots(), the counters in use: sgd_limits.h)
 
 // A wave's counter and that counter's share of an iteration's updates (< 2^31, host-checked): equal shares, the first
 // total % slots counters one more; or the whole iteration on counter 0 (pool_share_single: layouts, K2c).
@@ -284,8 +276,7 @@ __device__ __forceinline__ void pool_walk(KArgs &a, const IterConsts *its, const
 // updates do (DRB1: 35 059 updates in 0.1 ms, most of it launch ramp and tail).  Here every wave claims an iteration's
 // updates from the pool in chunks of REF_CHUNK_PER_LANE per live lane; a chunk is dealt to the lanes — each an ordinary
 // reference stream — in equal shares.  ONE stream claims every chunk itself, in order, and is bit for bit the
-// per-iteration kernel and the oracle's single stream (tested).
-constexpr uint32_t REF_CHUNK_PER_LANE = 16;
+// per-iteration kernel and the oracle's single stream (tested).  (REF_CHUNK_PER_LANE: sgd_limits.h)
 
 // run(share, max_attempts): the stream's loop for `share` successful updates (ref_run_1d / ref_run_nd)
 template <class Run>

@@ -173,7 +173,6 @@ const void *fused_kernel_1d(const KernelShape &s, bool pooled) {
         default: return nullptr;
     }
 }
-size_t pool_bytes(uint64_t n_iters) { return (size_t)n_iters * POOL_SLOTS * POOL_STRIDE * sizeof(uint32_t); }
 
 // K1 for reference streams, K1b<B> for bundles of 4..64 (its debug trace always reads with agent-scope loads)
 template <int B>

@@ -1,7 +1,7 @@
 // sgd_kernels_1d_phased.hip — K1e: the PHASED sampler of the 1D sort (GFS_F_PHASED), one persistent pooled launch over any
 // range of iterations.  An iteration is either a TEAM iteration (K1c's trip machine at B = 64, team_iteration) or a WINDOW
 // iteration (every lane is reference stream `tid`, K1d's ref_run_1d): the host marks the window's iterations in IterConsts._pad
-// (capi.hip iter_consts), and every wave reads the mark with the iteration's constants — a scalar load, a wave-uniform branch.
+// (launch_policy.h iter_consts), and every wave reads the mark with the iteration's constants — a scalar load, a wave-uniform branch.
 // Both samplers draw from the same per-lane RNG in registers, and each continues the state the other left; a team pass left
 // over when a window begins is kept and dropped by the team's own rule (a cooling flag other than the one it was sampled
 // under).  That is the oracle with gfo_state_set_bundle switched between 64 and 1 between iterations.

@@ -1,5 +1,5 @@
 // sgd_kernels_batch.hip — K1f / K2f: the fused reference-stream kernels (K1d, sgd_kernels_1d.hip; K2d, sgd_kernels_nd.hip) over
-// MANY graphs in one persistent launch.  A graph below 16 384 nodes runs at most one stream per 4 nodes (capi.hip
+// MANY graphs in one persistent launch.  A graph below 16 384 nodes runs at most one stream per 4 nodes (launch_policy.h
 // auto_stream_count): DRB1-3123 is 5 workgroups, and nothing done within the graph fills the other 250 CUs.  Here the grid is the
 // concatenation of the items' grids; a workgroup looks its item up, and from there on it is K1d / K2d on that item's buffers.
 #include "sgd_1d.h"

@@ -22,9 +22,6 @@ const void *fused_kernel_nd_team(const KernelShape &s, bool pooled) {
     return nullptr;
 }
 
-// waves per SIMD the layout team kernels are built for (the host sizes the stream count by it)
-int nd_team_waves(int dims) { return nd_waves_for(dims); }
-
 // loads this translation unit's code object (HIP loads modules on first use); see gfs_warmup
 hipError_t warm_module_nd_team() {
     hipFuncAttributes attr;

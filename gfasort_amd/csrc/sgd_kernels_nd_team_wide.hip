@@ -2,7 +2,7 @@
 // machine as D = 2, 3 (runs of GFS_F_CHAIN trips, one set of end flips per run, two partners per leader with twin trips, fused
 // short-jump trips with one add per end), instantiated in a translation unit of their own so that they compile beside D = 1..3.
 // Built for two waves per SIMD (nd_waves_for): 192-246 VGPRs for the fused kernels, 256 for the D = 8 trace kernel at B = 64,
-// nothing spilled (profiles/r04/nd_wide_resource_usage.txt).  The auto policy does not pick them (capi.hip choose_bundle):
+// nothing spilled (profiles/r04/nd_wide_resource_usage.txt).  The auto policy does not pick them (launch_policy.h choose_bundle):
 // they are reached with an explicit GFS_F_BUNDLE(8..64).
 #include "sgd_nd_team.h"
 

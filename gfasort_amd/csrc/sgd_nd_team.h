@@ -3,6 +3,7 @@
 // dispatcher) and sgd_kernels_nd_team_wide.hip (D = 4..8).
 #pragma once
 #include "sgd_kernel_common.h"
+#include "sgd_limits.h"
 #include "sgd_host.h"
 
 namespace gfs {
@@ -336,19 +337,8 @@ __device__ __forceinline__ bool twin_trip_nd(const KArgs &a, const TripND &cur, 
     return second;
 }
 
-// (3 waves per SIMD, <= 168 VGPRs: 165 at D = 2, nothing spilled; D = 3: two waves, 176, see nd_waves_for.  Round 2's kernel needed ~210 and ran
-// two waves — a twin trip holds the records of three steps and of the steps after them, the next trip's too, and three ends'
-// coordinates.  What brought it under 168: the trip machine's state in scalar registers (uni), steps as 32-bit ranks in their
-// path, no lane permutes for the adds (dimension planes), the sampler's constants re-read per pass.  Three waves hide the
-// round trip of a trip's loads and adds behind two other waves' arithmetic: without the adds the kernel runs at 64 G updates/s
-// where two waves gave 51 (profiles/r03/nd_waves3.log).  Hence also the bound on the workgroup size, checked by the host.)
-#ifndef GFS_ND_TEAM_WAVES
-#define GFS_ND_TEAM_WAVES 3
-#endif
-// (D = 3 holds half as many coordinates again: three waves' worth of registers spill 4-11 of them, and under the work pool two
-// waves are as fast — 34.2 against 34.3 G updates/s on C4, profiles/r03/nd_k_probe_fused.log — so D = 3 is built for two.  So is every
-// wider layout: two waves leave 256 VGPRs, enough for D = 8 without spilling, the trace kernel at B = 64 using all of them.)
-constexpr int nd_waves_for(int dims) { return dims >= 3 ? 2 : GFS_ND_TEAM_WAVES; }
+// (GFS_ND_TEAM_WAVES / nd_waves_for, the waves per SIMD these kernels are built for — three at D <= 2, two from D = 3 up — and
+// the registers that decide it: sgd_limits.h)
 // The wave's state across chunks, iterations and (through KArgs.lead) launches — as K1b's TeamState (sgd_kernels_1d.hip), plus the
 // run's end flips.
 struct NdTeamState {

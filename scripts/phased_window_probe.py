@@ -1,4 +1,4 @@
-"""Choosing GFS_F_PHASED's default window (capi.hip gfs_phase_window): candidate windows around the reference's switch to the
+"""Choosing GFS_F_PHASED's default window (host_tables.hip gfs_phase_window): candidate windows around the reference's switch to the
 cooling phase, f = first_cooling = floor(cooling_start * iter_max), run through the fused phased kernel (K1e), against reference
 streams (GFS_F_BUNDLE(1)) of the same seed.  Printed per run: kernel ms and the figures of tests/test_gpu_quality.py _compare
 (sampled stress 2M pairs, worst ratio of the relative error per octave of path distance and the ratio at distance 1, RMSE / MAE of

@@ -1,4 +1,4 @@
-"""Medium graphs (66k...300k nodes): the team kernel's streams-per-node bound (capi.hip auto_stream_count: three streams per 4
+"""Medium graphs (66k...300k nodes): the team kernel's streams-per-node bound (launch_policy.h auto_stream_count: three streams per 4
 nodes) leaves the chip partly empty there.  Default flags at 0.75 / 1.0 / 1.25 / 1.5 / 2.0 streams per node, two seeds each:
 rate, and the relative error per octave of path distance against reference streams (distance 1 and 2-3 over all pairs).
     python scripts/stream_cap_probe2.py"""

@@ -252,7 +252,7 @@ def test_coordinate_sums_are_conserved_at_full_width(dims, launch):
 
 # ---- f. the yardstick of test_gpu_layout_wide.py against the CPU, at full width ----------------------------------------------
 QUALITY_SEEDS = [9399220 + 1000 * k for k in range(8)]
-QUALITY_STREAMS = 1216                    # what the library picks for DRB1 (one stream per 4 nodes, capi.hip auto_stream_count)
+QUALITY_STREAMS = 1216                    # what the library picks for DRB1 (one stream per 4 nodes, launch_policy.h auto_stream_count)
 QUALITY_PAIRED_SD = {4: 0.02893, 8: 0.02900}      # oracle alone, relative to the mean stress (profiles/r06/quality_margin.log)
 
 

@@ -360,7 +360,7 @@ def test_bundled_terms_are_node_disjoint_within_a_bundle():
 
 
 def test_auto_bundle_policy():
-    """What the library picks by itself (capi.hip choose_bundle; measured basis: profiles/r03/policy_sweep.log)."""
+    """What the library picks by itself (launch_policy.h choose_bundle; measured basis: profiles/r03/policy_sweep.log)."""
     g_small = load("DRB1-3123.gfa")
     rc, x, st = hip.path_linear_sgd_raw(g_small, _ygs(g_small, 2))
     assert st.bundle == 1                                            # < 16384 nodes: reference streams

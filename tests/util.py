@@ -230,6 +230,6 @@ def reverse_short_paths_graph():
 
 
 def single_stream_kshift(g):
-    """The crowding onset of a one-stream run (capi.hip fill_kargs): floor(log2(n_steps / 2)) + 2."""
+    """The crowding onset of a one-stream run (launch_policy.h crowd_kshift): floor(log2(n_steps / 2)) + 2."""
     per = max(g.n_steps // 2, 1)
     return per.bit_length() - 1 + 2
