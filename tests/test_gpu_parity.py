@@ -540,6 +540,8 @@ def _mp_rank(rank, world, port, out):
 
 
 def test_two_ranks_on_one_gpu_hip_engine():
+    """Two processes, full-width kernels, gloo: an outcome test (replicas agree, update counts, quality).  What the merge
+    computes is pinned bit for bit by tests/test_gpu_multi_merge.py."""
     import socket
     import torch.multiprocessing as mp
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
@@ -982,6 +984,8 @@ def _rccl_rank(port, out):
 
 
 def test_one_rank_rccl_group_runs_the_merge_path():
+    """The merge kernels around a real RCCL all-reduce: an outcome test (update and launch counts, chain order).  The
+    exact check of the merge is tests/test_gpu_multi_merge.py."""
     import socket
     import torch.multiprocessing as mp
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
@@ -1114,7 +1118,8 @@ def _big_position_windows():
 @pytest.mark.parametrize("f64", [False, True])
 def test_exchange_payload_f32_and_f64_at_positions_of_1e8(f64):
     """The exchange buffer carries MOVES (x - x_prev), not positions: f32 rounds a move to 24 bits whatever the position
-    is.  With positions up to 1e8 bp both payloads sort the chain exactly and agree with each other to ~1e-6 of the span."""
+    is.  With positions up to 1e8 bp both payloads sort the chain exactly and agree with each other to ~1e-6 of the span.
+    An outcome test; both payload types are held to a restatement bit for bit in tests/test_gpu_multi_merge.py."""
     import socket
     import torch.multiprocessing as mp
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
@@ -1163,6 +1168,8 @@ def _mp_rank_nd(rank, world, port, out):
 
 
 def test_two_ranks_on_one_gpu_layout_2d():
+    """The layout step over two ranks: an outcome test (replicas agree, update count, stress).  The nD element order of the
+    exchange and the merge arithmetic are pinned bit for bit by tests/test_gpu_multi_merge.py."""
     import socket
     import torch.multiprocessing as mp
     from gfasort_amd import sgd as S
