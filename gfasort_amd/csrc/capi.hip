@@ -6,6 +6,7 @@
 #include "sgd_kernel_common.h"
 #include "sgd_batch.h"
 #include "batch_plan.h"
+#include "segment_sort.h"
 #include "launch_policy.h"
 #include "sgd_host.h"
 
@@ -1212,7 +1213,16 @@ struct gfs_batch {
     gfs::BatchItem *d_items = nullptr; uint32_t *d_block_item = nullptr; uint32_t *d_pool = nullptr;
     uint64_t launches_done = 0, blocks_done = 0;
     double kernel_ms = 0.0, total_ms = 0.0;
+    // K4b / K6b (batch_readout_kernels.hip): the item table, the packed outputs and the per-item sort's scratch, allocated on first use
+    uint64_t sort_cap = gfs::SEGMENT_SORT_CAP;       // items of more nodes take K6, one by one (gfs_batch_debug_sort_cap)
+    std::vector<gfs::ReadoutItem> h_readout;
+    gfs::ReadoutItem *d_readout = nullptr;
+    double *d_positions = nullptr; uint32_t *d_order = nullptr; uint64_t packed_cap = 0;
+    void *d_sort_tmp = nullptr; uint64_t sort_tmp_bytes = 0;
+    void *h_packed = nullptr; uint64_t h_packed_bytes = 0;   // pinned: the two copies land here at full rate, whatever the caller's pages are
+    hipEvent_t readout_e0 = nullptr, readout_e1 = nullptr;
 };
+static_assert(GFS_SEGMENT_SORT_CAP == gfs::SEGMENT_SORT_CAP, "the header's cap is the network's");
 
 static bool batch_item_idle(const gfs_ctx *c) { return !c->valid_paths || c->n_nodes == 0; }
 static bool batch_eligible(const gfs_ctx *c) {
@@ -1228,6 +1238,13 @@ void gfs_batch_destroy(gfs_batch *b) {
     if (b->d_items) (void)hipFree(b->d_items);
     if (b->d_block_item) (void)hipFree(b->d_block_item);
     if (b->d_pool) (void)hipFree(b->d_pool);
+    if (b->d_readout) (void)hipFree(b->d_readout);
+    if (b->d_positions) (void)hipFree(b->d_positions);
+    if (b->d_order) (void)hipFree(b->d_order);
+    if (b->d_sort_tmp) (void)hipFree(b->d_sort_tmp);
+    if (b->h_packed) (void)hipHostFree(b->h_packed);
+    if (b->readout_e0) (void)hipEventDestroy(b->readout_e0);
+    if (b->readout_e1) (void)hipEventDestroy(b->readout_e1);
     delete b;
 }
 
@@ -1419,6 +1436,162 @@ int gfs_batch_get_stats(gfs_batch *b, gfs_batch_stats *out) {
         if (rc) return rc;
         out->term_updates += st.term_updates; out->attempts += st.attempts;
     }
+    return GFS_OK;
+}
+
+// ---- K4b / K6b: every item's start positions, and every item's positions and rank order, in one launch ------------------------
+static uint64_t batch_total_nodes(const gfs_batch *b) {
+    uint64_t total = 0;
+    for (const gfs_ctx *c : b->ctxs) total += c->n_nodes;
+    return total;
+}
+// the checks gfs_ctx_init_positions and gfs_ctx_sort_order make, on every item; no device call
+static int batch_readout_check(const gfs_batch *b) {
+    if (b->dims != 0) return fail(GFS_E_UNSUPPORTED, "a batch of layouts has no start positions or rank order (dims=" + std::to_string(b->dims) + ")");
+    for (size_t i = 0; i < b->ctxs.size(); ++i) {
+        const gfs_ctx *c = b->ctxs[i];
+        if (!c->d_x || c->dims != 0) return fail(GFS_E_STATE, "batch item " + std::to_string(i) + ": needs a 1D context that has been set up");
+    }
+    return GFS_OK;
+}
+// The item table from the contexts as they are now (positions may have been bound anew), in the order `order` lists them;
+// offsets are those of gfs_batch_result_offsets.  Uploaded on st.
+static int batch_readout_table(gfs_batch *b, const std::vector<uint64_t> &order, hipStream_t st) {
+    if (!b->d_readout) HIPCHK(hipMalloc(&b->d_readout, b->ctxs.size() * sizeof(gfs::ReadoutItem)));
+    std::vector<uint64_t> offset(b->ctxs.size());
+    uint64_t total = 0;
+    for (size_t i = 0; i < b->ctxs.size(); ++i) { offset[i] = total; total += b->ctxs[i]->n_nodes; }
+    b->h_readout.resize(order.size());
+    for (size_t r = 0; r < order.size(); ++r) {
+        const gfs_ctx *c = b->ctxs[order[r]];
+        gfs::ReadoutItem &it = b->h_readout[r];
+        it.x = c->d_x; it.perm = c->d_perm; it.node_len = c->d_node_len;
+        it.offset = offset[order[r]];
+        it.n = (uint32_t)c->n_nodes;                                       // (a context has fewer than 2^31 nodes)
+        it.padded = c->n_nodes <= gfs::SEGMENT_SORT_CAP ? gfs::segment_padded(it.n) : 0;
+    }
+    if (!order.empty())
+        HIPCHK(hipMemcpyAsync(b->d_readout, b->h_readout.data(), order.size() * sizeof(gfs::ReadoutItem), hipMemcpyHostToDevice, st));
+    return GFS_OK;
+}
+
+int gfs_batch_result_offsets(const gfs_batch *b, uint64_t *offsets, uint64_t n) {
+    if (!b || !offsets) return fail(GFS_E_ARG, "null argument");
+    if (n != b->ctxs.size() + 1) return fail(GFS_E_ARG, "offsets: need items + 1 entries");
+    uint64_t total = 0;
+    for (size_t i = 0; i < b->ctxs.size(); ++i) { offsets[i] = total; total += b->ctxs[i]->n_nodes; }
+    offsets[b->ctxs.size()] = total;
+    return GFS_OK;
+}
+
+int gfs_batch_debug_sort_cap(gfs_batch *b, uint64_t cap) {
+    if (!b) return fail(GFS_E_ARG, "batch is null");
+    if (cap > gfs::SEGMENT_SORT_CAP) return fail(GFS_E_ARG, "sort cap above GFS_SEGMENT_SORT_CAP");
+    b->sort_cap = cap ? cap : gfs::SEGMENT_SORT_CAP;
+    return GFS_OK;
+}
+
+int gfs_batch_init_positions(gfs_batch *b, void *hip_stream) {
+    if (!b) return fail(GFS_E_ARG, "batch is null");
+    int rc = batch_readout_check(b);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipDeviceSynchronize());                                        // as gfs_ctx_init_positions: nothing of an item is in flight
+    hipStream_t st = (hipStream_t)hip_stream;
+    std::vector<uint64_t> all(b->ctxs.size());
+    std::iota(all.begin(), all.end(), 0ull);
+    rc = batch_readout_table(b, all, st);
+    if (rc) return rc;
+    hipError_t e = gfs::batch_init_positions_device(b->d_readout, (uint32_t)all.size(), st);
+    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch init_positions: ") + hipGetErrorString(e));
+    HIPCHK(hipStreamSynchronize(st));
+    return GFS_OK;
+}
+
+int gfs_batch_results(gfs_batch *b, double *positions, uint32_t *order, uint64_t total, double *kernel_ms, void *hip_stream) {
+    if (!b) return fail(GFS_E_ARG, "batch is null");
+    if (!positions && !order) return fail(GFS_E_ARG, "both output buffers are null");
+    if (total != batch_total_nodes(b)) return fail(GFS_E_ARG, "total is not the batch's node count (gfs_batch_result_offsets)");
+    int rc = batch_readout_check(b);
+    if (rc) return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipDeviceSynchronize());                                        // as gfs_ctx_sort_order
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (b->packed_cap < total) {
+        if (b->d_positions) HIPCHK(hipFree(b->d_positions));
+        if (b->d_order) HIPCHK(hipFree(b->d_order));
+        b->d_positions = nullptr; b->d_order = nullptr; b->packed_cap = 0;
+        HIPCHK(hipMalloc(&b->d_positions, total * sizeof(double)));
+        HIPCHK(hipMalloc(&b->d_order, total * sizeof(uint32_t)));
+        b->packed_cap = total;
+    }
+    if (!b->readout_e0) HIPCHK(hipEventCreate(&b->readout_e0));
+    if (!b->readout_e1) HIPCHK(hipEventCreate(&b->readout_e1));
+    // items within the cap by the length of their padded segment: one launch per length, its LDS and block sized by it; the others after them
+    std::vector<uint64_t> by_len(b->ctxs.size());
+    std::iota(by_len.begin(), by_len.end(), 0ull);
+    auto padded_of = [&](uint64_t i) -> uint64_t {
+        const uint64_t n = b->ctxs[i]->n_nodes;
+        return n <= b->sort_cap ? gfs::segment_padded((uint32_t)n) : ~0ull;
+    };
+    std::stable_sort(by_len.begin(), by_len.end(), [&](uint64_t a, uint64_t c) { return padded_of(a) < padded_of(c); });
+    rc = batch_readout_table(b, by_len, st);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(b->readout_e0, st));
+    size_t first = 0;
+    while (first < by_len.size() && padded_of(by_len[first]) != ~0ull) {
+        const uint64_t P = padded_of(by_len[first]);
+        size_t end = first;
+        while (end < by_len.size() && padded_of(by_len[end]) == P) ++end;
+        for (size_t at = first; at < end; at += 0x7FFFFFFFull) {           // (a grid's x dimension)
+            const uint32_t count = (uint32_t)std::min<size_t>(end - at, 0x7FFFFFFFull);
+            hipError_t e = gfs::sort_segments_device(b->d_readout + at, count, (uint32_t)P, positions ? b->d_positions : nullptr, b->d_order, st);
+            if (e != hipSuccess) return fail(GFS_E_HIP, std::string("segment sort launch: ") + hipGetErrorString(e));
+        }
+        first = end;
+    }
+    // above the cap: K6 (rocPRIM radix sort) once each, into the same packed arrays
+    for (size_t r = first; r < by_len.size(); ++r) {
+        const gfs_ctx *c = b->ctxs[by_len[r]];
+        const gfs::ReadoutItem &it = b->h_readout[r];
+        const uint64_t n = c->n_nodes, need = n * (2 * 8 + 2 * 4);
+        HIPCHK(hipStreamSynchronize(st));                                  // (K6 runs on the null stream)
+        if (b->sort_tmp_bytes < need) {
+            if (b->d_sort_tmp) HIPCHK(hipFree(b->d_sort_tmp));
+            b->d_sort_tmp = nullptr; b->sort_tmp_bytes = 0;
+            HIPCHK(hipMalloc(&b->d_sort_tmp, need));
+            b->sort_tmp_bytes = need;
+        }
+        uint32_t *d_sorted = nullptr;
+        hipError_t e = gfs::sort_order_device(c->d_x, c->d_perm, n, 1, b->d_sort_tmp, &d_sorted);
+        if (e != hipSuccess) return fail(GFS_E_HIP, "batch item " + std::to_string(by_len[r]) + ": sort_order_device: " + hipGetErrorString(e));
+        HIPCHK(hipMemcpyAsync(b->d_order + it.offset, d_sorted, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        if (positions) {
+            e = gfs::reorder_positions_device(c->d_x, b->d_positions + it.offset, c->d_perm, n, 0, 0, st);
+            if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch positions: ") + hipGetErrorString(e));
+        }
+        HIPCHK(hipStreamSynchronize(st));                                  // (the scratch is the next item's)
+    }
+    HIPCHK(hipEventRecord(b->readout_e1, st));
+    // The two copies go through pinned memory of the batch: a copy of megabytes straight into the caller's pageable buffer has
+    // the runtime pin those pages first, 20-30 ms where they are fresh (profiles/r10/batch_readout_probe_pageable.log).
+    const uint64_t staging = total * (sizeof(double) + sizeof(uint32_t));
+    if (b->h_packed_bytes < staging) {
+        if (b->h_packed) HIPCHK(hipHostFree(b->h_packed));
+        b->h_packed = nullptr; b->h_packed_bytes = 0;
+        HIPCHK(hipHostMalloc(&b->h_packed, staging, hipHostMallocDefault));
+        b->h_packed_bytes = staging;
+    }
+    double *h_positions = reinterpret_cast<double *>(b->h_packed);
+    uint32_t *h_order = reinterpret_cast<uint32_t *>(h_positions + total);
+    if (positions && total) HIPCHK(hipMemcpyAsync(h_positions, b->d_positions, total * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (order && total) HIPCHK(hipMemcpyAsync(h_order, b->d_order, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (positions && total) std::memcpy(positions, h_positions, total * sizeof(double));
+    if (order && total) std::memcpy(order, h_order, total * sizeof(uint32_t));
+    float t = 0.f;
+    if (kernel_ms && hipEventElapsedTime(&t, b->readout_e0, b->readout_e1) == hipSuccess) *kernel_ms = t;
     return GFS_OK;
 }
 

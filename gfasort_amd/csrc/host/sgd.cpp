@@ -245,23 +245,28 @@ gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbos
         ~Cleanup() { if (b) gfs_batch_destroy(b); for (auto &x : s) if (x.ctx) gfs_ctx_destroy(x.ctx); }
     } cleanup{slots};
     gfs_batch_stats bs{};
-    // run, read back, reorder the graph, free the context
-    auto finish = [&](size_t i, bool alone) {
+    // reorder the graph by its rank order, keep what was asked for, free the context
+    auto apply = [&](size_t i, std::vector<double> &&x, const auto *order, size_t n) {
         BatchSortItem &it = items[i];
-        gfs_ctx *c = slots[i].ctx;
-        if (alone) check(gfs_ctx_run(c, nullptr));
         const FlatGraph &f = slots[i].f;
-        std::vector<double> x(f.node_len.size());
+        check(gfs_ctx_stats(slots[i].ctx, &it.stats));
+        gfs_ctx_destroy(slots[i].ctx); slots[i].ctx = nullptr;
+        std::vector<Handle> ordering;
+        ordering.reserve(n);
+        for (size_t r = 0; r < n; ++r) ordering.push_back(Handle::forward(f.node_ids[order[r]]));   // idx -> handle, sgd.rs:649-662
+        it.graph->apply_ordering(ordering);
+        if (keep_positions) { it.positions = std::move(x); it.before = std::move(slots[i].f); }
+    };
+    // a graph that runs alone: start positions, run, read back through its own context
+    auto finish_alone = [&](size_t i) {
+        gfs_ctx *c = slots[i].ctx;
+        check(gfs_ctx_init_positions(c));
+        check(gfs_ctx_run(c, nullptr));
+        std::vector<double> x(slots[i].f.node_len.size());
         std::vector<uint64_t> order(x.size());
         check(gfs_ctx_download_positions(c, x.data(), x.size()));
         check(gfs_ctx_sort_order(c, order.data(), order.size()));
-        check(gfs_ctx_stats(c, &it.stats));
-        gfs_ctx_destroy(c); slots[i].ctx = nullptr;
-        std::vector<Handle> ordering;
-        ordering.reserve(order.size());
-        for (uint64_t idx : order) ordering.push_back(Handle::forward(f.node_ids[idx]));   // idx -> handle, sgd.rs:649-662
-        it.graph->apply_ordering(ordering);
-        if (keep_positions) { it.positions = std::move(x); it.before = std::move(slots[i].f); }
+        apply(i, std::move(x), order.data(), order.size());
     };
     std::vector<size_t> together;                                                     // indices into items: the batch's candidates
     for (size_t i = 0; i < items.size(); ++i) {
@@ -279,10 +284,9 @@ gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbos
             gfs_ctx_destroy(slots[i].ctx); slots[i].ctx = nullptr;
             continue;
         }
-        check(gfs_ctx_init_positions(slots[i].ctx));
         check(gfs_ctx_stats(slots[i].ctx, &it.stats));
         if (it.stats.bundle == 1) together.push_back(i);                              // stays resident until the batch has run
-        else finish(i, true);                                                         // a team-kernel graph: alone, now
+        else finish_alone(i);                                                         // a team-kernel graph: alone, now
     }
     // A graph the batch refuses (flags that rule the fused launch out, more workgroups than one launch holds) is named by the
     // error: it is taken out and runs alone, the others still run together.
@@ -301,12 +305,26 @@ gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbos
         together.erase(together.begin() + (std::ptrdiff_t)named);
     }
     if (cleanup.b) {
+        // start positions, the run and the read-out of all its graphs: one launch each, two copies (K4b, K1f, K6b)
+        check(gfs_batch_init_positions(cleanup.b, nullptr));
         check(gfs_batch_run(cleanup.b, nullptr));
         check(gfs_batch_get_stats(cleanup.b, &bs));
+        std::vector<uint64_t> offsets(together.size() + 1);
+        check(gfs_batch_result_offsets(cleanup.b, offsets.data(), offsets.size()));
+        std::vector<double> x(offsets.back());
+        std::vector<uint32_t> order(offsets.back());
+        double readout_ms = 0.0;
+        check(gfs_batch_results(cleanup.b, x.data(), order.data(), offsets.back(), &readout_ms, nullptr));
+        if (verbose >= 2) std::cerr << "[gfasort_hip] batch: read-out of " << together.size() << " graphs, " << readout_ms << " ms on the device\n";
         gfs_batch_destroy(cleanup.b); cleanup.b = nullptr;                            // (before its contexts go)
-        for (size_t i : together) { items[i].batched = true; finish(i, false); }
+        for (size_t k = 0; k < together.size(); ++k) {
+            const size_t i = together[k];
+            items[i].batched = true;
+            apply(i, std::vector<double>(x.begin() + (std::ptrdiff_t)offsets[k], x.begin() + (std::ptrdiff_t)offsets[k + 1]), order.data() + offsets[k],
+                  (size_t)(offsets[k + 1] - offsets[k]));
+        }
     }
-    for (size_t i : refused) finish(i, true);
+    for (size_t i : refused) finish_alone(i);
     return bs;
 }
 

@@ -5,6 +5,7 @@
 //       of node lengths over the steps, written straight into the 16-byte step records
 //   K6  path_sgd_sort's sort (src/sgd.rs:665-671): positions -> rank order
 #include "sgd_host.h"
+#include "sort_key.h"
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <stdint.h>
@@ -314,15 +315,7 @@ hipError_t init_positions_device(const uint32_t *d_node_len, const uint32_t *d_p
     return done(hipDeviceSynchronize());
 }
 
-// ---- K6 ------------------------------------------------------------------------------------------
-// Order-preserving u64 image of an f64: -0.0 is folded onto +0.0 (partial_cmp calls them equal, so the
-// tie must be broken by index, sgd.rs:666); NaNs (never produced by a finite run) sort after all numbers.
-__device__ __forceinline__ uint64_t orderable(double v) {
-    if (v != v) return 0xFFFFFFFFFFFFFFFFull;
-    if (v == 0.0) v = 0.0;
-    uint64_t b = (uint64_t)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
+// ---- K6 (the key of a position: sort_key.h orderable) --------------------------------------------
 // keys in DENSE-index order (the device vector is in layout order), so that the stable sort breaks ties by dense index
 __global__ void sort_keys_kernel(const double *x_layout, const uint32_t *perm, uint64_t *keys, uint32_t *vals, uint64_t n,
                                  uint64_t stride_doubles) {

@@ -62,6 +62,21 @@ hipError_t build_path_index_device(const uint32_t *d_step_node, const uint8_t *d
 hipError_t sort_order_device(const double *d_x_layout, const uint32_t *d_perm, uint64_t n, uint64_t stride_doubles,
                              void *d_tmp, uint32_t **d_order_out);
 
+// batch_readout_kernels.hip (K4b, K6b): one workgroup per item of a table on the device.  x, perm and node_len are the item's
+// context's; offset is where its segment starts in the packed outputs; padded = segment_padded(n) (segment_sort.h; K6b only).
+struct ReadoutItem {
+    double *x;
+    const uint32_t *perm, *node_len;
+    uint64_t offset;
+    uint32_t n, padded;
+};
+// K4b: every item's initial positions (what init_positions_device writes).  Asynchronous.
+hipError_t batch_init_positions_device(const ReadoutItem *d_items, uint32_t count, hipStream_t st);
+// K6b: count items of one padded length <= SEGMENT_SORT_CAP: d_positions (nullable) [offset + k] = x[perm[k]], d_order[offset + r] =
+// dense index of the node of rank r.  Asynchronous.
+hipError_t sort_segments_device(const ReadoutItem *d_items, uint32_t count, uint32_t padded, double *d_positions, uint32_t *d_order,
+                                hipStream_t st);
+
 // quality_kernels.hip (K7): read-outs of the resident positions.  They write their own output buffers only.
 // Workgroups of the step passes: a function of n_steps alone, so that a result does not depend on the device.
 unsigned quality_blocks(uint64_t n_steps);

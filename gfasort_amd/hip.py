@@ -134,7 +134,9 @@ EXPORTS = [
     "gfs_ctx_pair_errors", "gfs_stress_sample_pairs", "gfs_ctx_stress_of_pairs", "gfs_ctx_sort_quality", "gfs_pair_errors",
     "gfs_ctx_path_errors", "gfs_ctx_stretched_pairs", "gfs_ctx_node_errors", "gfs_diagnose",
     "gfs_batch_plan", "gfs_batch_create", "gfs_batch_run", "gfs_batch_get_stats", "gfs_batch_destroy",
+    "gfs_batch_result_offsets", "gfs_batch_init_positions", "gfs_batch_results", "gfs_batch_debug_sort_cap",
 ]
+SEGMENT_SORT_CAP = 8192                # GFS_SEGMENT_SORT_CAP
 
 _lib = None
 
@@ -225,6 +227,10 @@ def lib():
         L.gfs_batch_get_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.gfs_batch_destroy.argtypes = [C.c_void_p]
         L.gfs_batch_destroy.restype = None
+        L.gfs_batch_result_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.gfs_batch_init_positions.argtypes = [C.c_void_p, C.c_void_p]
+        L.gfs_batch_results.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.gfs_batch_debug_sort_cap.argtypes = [C.c_void_p, C.c_uint64]
         _lib = L
     return _lib
 
@@ -730,6 +736,32 @@ class Batch:
         st = BatchStats()
         check(lib().gfs_batch_get_stats(self._h, C.byref(st)))
         return st
+
+    def result_offsets(self):
+        """offsets[i] = first node of item i in the packed arrays of results(); offsets[items] = their length."""
+        off = np.zeros(len(self.contexts) + 1, dtype=np.uint64)
+        check(lib().gfs_batch_result_offsets(self._h, _ptr(off), C.c_uint64(off.shape[0])))
+        return off
+
+    def init_positions(self, stream=None):
+        """Context.init_positions() on every item, in one launch."""
+        check(lib().gfs_batch_init_positions(self._h, C.c_void_p(stream or 0)))
+
+    def results(self, positions=True, order=True, stream=None):
+        """Every item's download() and sort_order() in one launch per padded segment length and two copies: (list of float64
+        arrays, list of uint64 arrays, kernel_ms), one array per item in the order given; None for a list that was not asked for."""
+        off = self.result_offsets()
+        total = int(off[-1])
+        x = np.zeros(total, dtype=np.float64) if positions else None
+        o = np.zeros(total, dtype=np.uint32) if order else None
+        ms = C.c_double(0.0)
+        check(lib().gfs_batch_results(self._h, _ptr(x), _ptr(o), C.c_uint64(total), C.byref(ms), C.c_void_p(stream or 0)))
+        cut = lambda a: [a[int(off[i]):int(off[i + 1])] for i in range(len(self.contexts))]
+        return (cut(x) if positions else None, cut(o.astype(np.uint64)) if order else None, float(ms.value))
+
+    def debug_sort_cap(self, cap):
+        """Test hook: items of more than cap nodes take the per-item sort (0 restores SEGMENT_SORT_CAP)."""
+        check(lib().gfs_batch_debug_sort_cap(self._h, C.c_uint64(int(cap))))
 
 
 # ---- one-shot entry points ---------------------------------------------------------------------

@@ -71,7 +71,8 @@ def path_linear_sgd_layout(graph: FlatGraph, params: LayoutSGDParams, init: Opti
 
 def path_sgd_sort_batch(graphs, params, cfg=None, max_blocks_per_launch: int = 0, device: int = 0):
     """path_sgd_sort over MANY graphs: the ones whose plan is the fused reference-stream kernel (graphs of fewer than 16384
-    nodes under the default policy) run together as one hip.Batch — one persistent launch, or as few as fit the device —
+    nodes under the default policy) run together as one hip.Batch — one persistent launch, or as few as fit the device, with
+    their start positions set by one launch before it and their positions and orders read by one Batch.results() after it —
     and the others alone, one after the other.  A graph the batch refuses (hip.Batch names it) is taken out and runs alone;
     the rest still run together.  Only the batch's graphs are resident at once: a graph that runs alone for its bundle is run,
     read back and closed before the next one is set up.  params: one PathSGDParams for all, or one per graph; cfg likewise (or
@@ -97,10 +98,10 @@ def path_sgd_sort_batch(graphs, params, cfg=None, max_blocks_per_launch: int = 0
                 if rc != hip.OK:                               # nothing to do
                     out[i]["stats"] = ctx.stats()
                     continue
-                ctx.init_positions()
-                if ctx.stats().bundle == 1:
+                if ctx.stats().bundle == 1:                    # a candidate: initialised with the batch (or before its solo run)
                     held[i], ctx = ctx, None
                     continue
+                ctx.init_positions()
                 ctx.run()
                 out[i] = result(ctx, False)
             finally:
@@ -117,14 +118,19 @@ def path_sgd_sort_batch(graphs, params, cfg=None, max_blocks_per_launch: int = 0
                 del batched[int(named.group(1))]
         if batch is not None:
             try:
+                batch.init_positions()
                 batch.run()
                 batch_stats = batch.stats()
+                xs, orders, _ = batch.results()
             finally:
                 batch.close()
+            for k, i in enumerate(batched):
+                out[i] = dict(positions=xs[k], order=orders[k], stats=held[i].stats(), batched=True)
         for i, ctx in held.items():
             if i not in batched:
+                ctx.init_positions()
                 ctx.run()
-            out[i] = result(ctx, i in batched)
+                out[i] = result(ctx, False)
         return out, batch_stats
     finally:
         for ctx in held.values():

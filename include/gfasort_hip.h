@@ -381,7 +381,13 @@ int gfs_diagnose(const gfs_graph_view *g, uint64_t dims, const double *positions
  * iter_max + 1 <= 4096.  Otherwise GFS_E_UNSUPPORTED; GFS_E_ARG for null, n == 0 or the same context twice; GFS_E_STATE for a
  * context that is not set up; the text names the item; these checks come before any device call.  Items keep their own parameters,
  * schedules (iter_max may differ), quotas, seeds and stream counts.  A context with nothing to do is skipped and left alone.
- * Items with and without LDS tables go into separate launches; a launch's dynamic LDS is the largest among its items. */
+ * Items with and without LDS tables go into separate launches; a launch's dynamic LDS is the largest among its items.
+ * Either side of the run, a batch of 1D sorts does for all its items at once what gfs_ctx_init_positions, gfs_ctx_download_positions
+ * and gfs_ctx_sort_order do for one: gfs_batch_init_positions, one launch; gfs_batch_results, one launch per
+ * padded segment length and two copies, a workgroup sorting its item's (key, dense index) pairs in LDS.  Items of more than
+ * GFS_SEGMENT_SORT_CAP nodes take the per-context sort, once each, into the same arrays: no item is refused for its size.  Items
+ * with nothing to do are covered like the others.  The read-out changes no item's positions, RNG streams or counters. */
+#define GFS_SEGMENT_SORT_CAP 8192      /* nodes of the largest item sorted in LDS (96 KiB of a CU's 160) */
 typedef struct gfs_batch gfs_batch;
 typedef struct gfs_batch_config {
     uint64_t max_blocks_per_launch;   /* 0 = what the device holds at once (occupancy of the batch kernel at the launch's
@@ -406,6 +412,19 @@ int  gfs_batch_create(gfs_ctx *const *ctxs, uint64_t n, const gfs_batch_config *
 int  gfs_batch_run(gfs_batch *b, void *hip_stream);      /* every item's k = 0..=iter_max, then synchronises */
 int  gfs_batch_get_stats(gfs_batch *b, gfs_batch_stats *out);   /* synchronises */
 void gfs_batch_destroy(gfs_batch *b);
+/* host only: offsets[i] = sum of n_nodes of items 0..i-1, in the order given to gfs_batch_create (idle items included);
+ * offsets[items] = total.  n must be items + 1. */
+int  gfs_batch_result_offsets(const gfs_batch *b, uint64_t *offsets, uint64_t n);
+/* gfs_ctx_init_positions on every item, in one launch; then synchronises */
+int  gfs_batch_init_positions(gfs_batch *b, void *hip_stream);
+/* every item's positions (dense order, as gfs_ctx_download_positions) and rank order (as gfs_ctx_sort_order, as uint32_t)
+ * at offsets[i]; either pointer may be NULL; total must be offsets[items]; *kernel_ms (nullable): HIP events around the
+ * read-out launches; synchronises.  GFS_E_ARG for a null batch, both pointers NULL or a wrong total; GFS_E_UNSUPPORTED for a batch
+ * of layouts (both calls); an item on which gfs_ctx_sort_order would fail fails the call with that code, the text naming the item;
+ * all checked before any device call. */
+int  gfs_batch_results(gfs_batch *b, double *positions, uint32_t *order, uint64_t total, double *kernel_ms, void *hip_stream);
+/* test hook: items of more than cap nodes take the per-item sort (0 restores GFS_SEGMENT_SORT_CAP; larger values are GFS_E_ARG) */
+int  gfs_batch_debug_sort_cap(gfs_batch *b, uint64_t cap);
 
 /* ---- multi-device runs (no reference equivalent: the reference is one process, src/sgd.rs:413-593) ----
  * Paths are sharded over `world` ranks, one rank per GPU (one process per GPU, or one host thread per GPU); every rank
