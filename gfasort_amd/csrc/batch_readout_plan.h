@@ -1,0 +1,52 @@
+// batch_readout_plan.h — which workgroup of a batch's flat read-out launches works on which item (K4c / K6c, K7g:
+// batch_quality_kernels.hip).  Host only and free of HIP: the kernels take every index from the tables built here, and
+// tests/test_batch_layout_host.py compiles it into a program of its own under the address and undefined-behaviour sanitizers.
+#pragma once
+#include <stdint.h>
+
+namespace gfs {
+
+// ---- K7: workgroups of a step pass ----------------------------------------------------------------
+// A function of n_steps alone, never of the device (quality_kernels.hip: what makes a figure reproducible).
+constexpr unsigned Q_BLOCK = 256, Q_PAIRS_PER_THREAD = 8, Q_MAX_BLOCKS = 2048;
+inline unsigned quality_blocks_of(uint64_t n_steps) {
+    const uint64_t per_block = (uint64_t)Q_BLOCK * Q_PAIRS_PER_THREAD;
+    const uint64_t b = n_steps / per_block + (n_steps % per_block != 0);
+    return (unsigned)(b < 1 ? 1 : (b > Q_MAX_BLOCKS ? Q_MAX_BLOCKS : b));
+}
+
+// ---- K7g: item i owns quality_blocks_of(n_steps[i]) consecutive workgroups of every step distance's grid row ----------
+// first_block[0..n]: prefix sums (first_block[n] = the row's length).  Inside, workgroup b of item i is local block
+// b - first_block[i] of a grid of first_block[i + 1] - first_block[i]: the pair (block, grid) the item's own launch has.
+inline uint64_t quality_plan(const uint64_t *n_steps, uint64_t n, uint64_t *first_block) {
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; ++i) { first_block[i] = total; total += quality_blocks_of(n_steps[i]); }
+    first_block[n] = total;
+    return total;
+}
+
+// ---- K4c / K6c: item i has n_nodes[i] * 2 * D words of coordinates, packed in item order -------------------------------
+// A workgroup moves COORD_BLOCK consecutive words of ONE item: item i owns coord_blocks(words of i) consecutive workgroups
+// (none where it has no node), so that a workgroup reads its item once and the packed side is walked in order.
+constexpr unsigned COORD_BLOCK = 256;
+inline uint64_t coord_blocks(uint64_t words) { return words / COORD_BLOCK + (words % COORD_BLOCK != 0); }
+// word_offset[0..n], first_block[0..n]: prefix sums; returns the launch's workgroups (first_block[n]).
+inline uint64_t coord_plan(const uint64_t *n_nodes, uint64_t n, uint32_t D, uint64_t *word_offset, uint64_t *first_block) {
+    uint64_t words = 0, blocks = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        word_offset[i] = words; first_block[i] = blocks;
+        const uint64_t w = n_nodes[i] * 2 * (uint64_t)D;
+        words += w; blocks += coord_blocks(w);
+    }
+    word_offset[n] = words; first_block[n] = blocks;
+    return blocks;
+}
+
+// block -> item for either plan: block_item[b] = i for first_block[i] <= b < first_block[i + 1]; block_item has
+// first_block[n] entries.  (Read per workgroup as K1f reads its block table: no search on the device.)
+inline void block_item_table(const uint64_t *first_block, uint64_t n, uint32_t *block_item) {
+    for (uint64_t i = 0; i < n; ++i)
+        for (uint64_t b = first_block[i]; b < first_block[i + 1]; ++b) block_item[b] = (uint32_t)i;
+}
+
+}  // namespace gfs

@@ -6,6 +6,7 @@
 #include "sgd_kernel_common.h"
 #include "sgd_batch.h"
 #include "batch_plan.h"
+#include "batch_readout_plan.h"
 #include "segment_sort.h"
 #include "launch_policy.h"
 #include "sgd_host.h"
@@ -1221,7 +1222,27 @@ struct gfs_batch {
     void *d_sort_tmp = nullptr; uint64_t sort_tmp_bytes = 0;
     void *h_packed = nullptr; uint64_t h_packed_bytes = 0;   // pinned: the two copies land here at full rate, whatever the caller's pages are
     hipEvent_t readout_e0 = nullptr, readout_e1 = nullptr;
+    // K4c / K6c and K7g (batch_quality_kernels.hip): one device buffer each, [what the host sends | what the kernels write], grown on demand
+    void *d_coords = nullptr; uint64_t coords_bytes = 0;
+    void *d_quality = nullptr; uint64_t quality_bytes = 0;
 };
+// pinned staging of at least `bytes` (what it held is lost)
+static int batch_staging(gfs_batch *b, uint64_t bytes) {
+    if (b->h_packed_bytes >= bytes) return GFS_OK;
+    if (b->h_packed) HIPCHK(hipHostFree(b->h_packed));
+    b->h_packed = nullptr; b->h_packed_bytes = 0;
+    HIPCHK(hipHostMalloc(&b->h_packed, bytes, hipHostMallocDefault));
+    b->h_packed_bytes = bytes;
+    return GFS_OK;
+}
+static int batch_device_buffer(void **d, uint64_t *have, uint64_t bytes) {
+    if (*have >= bytes) return GFS_OK;
+    if (*d) HIPCHK(hipFree(*d));
+    *d = nullptr; *have = 0;
+    HIPCHK(hipMalloc(d, bytes));
+    *have = bytes;
+    return GFS_OK;
+}
 static_assert(GFS_SEGMENT_SORT_CAP == gfs::SEGMENT_SORT_CAP, "the header's cap is the network's");
 
 static bool batch_item_idle(const gfs_ctx *c) { return !c->valid_paths || c->n_nodes == 0; }
@@ -1243,6 +1264,8 @@ void gfs_batch_destroy(gfs_batch *b) {
     if (b->d_order) (void)hipFree(b->d_order);
     if (b->d_sort_tmp) (void)hipFree(b->d_sort_tmp);
     if (b->h_packed) (void)hipHostFree(b->h_packed);
+    if (b->d_coords) (void)hipFree(b->d_coords);
+    if (b->d_quality) (void)hipFree(b->d_quality);
     if (b->readout_e0) (void)hipEventDestroy(b->readout_e0);
     if (b->readout_e1) (void)hipEventDestroy(b->readout_e1);
     delete b;
@@ -1447,7 +1470,8 @@ static uint64_t batch_total_nodes(const gfs_batch *b) {
 }
 // the checks gfs_ctx_init_positions and gfs_ctx_sort_order make, on every item; no device call
 static int batch_readout_check(const gfs_batch *b) {
-    if (b->dims != 0) return fail(GFS_E_UNSUPPORTED, "a batch of layouts has no start positions or rank order (dims=" + std::to_string(b->dims) + ")");
+    if (b->dims != 0) return fail(GFS_E_UNSUPPORTED, "a batch of layouts has no start positions or rank order (dims=" + std::to_string(b->dims) +
+                                                          "): use gfs_batch_upload_coords and gfs_batch_coords");
     for (size_t i = 0; i < b->ctxs.size(); ++i) {
         const gfs_ctx *c = b->ctxs[i];
         if (!c->d_x || c->dims != 0) return fail(GFS_E_STATE, "batch item " + std::to_string(i) + ": needs a 1D context that has been set up");
@@ -1590,6 +1614,135 @@ int gfs_batch_results(gfs_batch *b, double *positions, uint32_t *order, uint64_t
     HIPCHK(hipStreamSynchronize(st));
     if (positions && total) std::memcpy(positions, h_positions, total * sizeof(double));
     if (order && total) std::memcpy(order, h_order, total * sizeof(uint32_t));
+    float t = 0.f;
+    if (kernel_ms && hipEventElapsedTime(&t, b->readout_e0, b->readout_e1) == hipSuccess) *kernel_ms = t;
+    return GFS_OK;
+}
+
+// ---- K4c / K6c: every item's layout coordinates, up or down, in one launch and one copy of coordinates -------------------------
+// The checks of both directions, on every item; no device call.  *total_out = the packed length in doubles.
+static int batch_coords_check(const gfs_batch *b, const double *coords, uint64_t total) {
+    if (!b) return fail(GFS_E_ARG, "batch is null");
+    if (!coords) return fail(GFS_E_ARG, "coords is null");
+    if (b->dims == 0)
+        return fail(GFS_E_UNSUPPORTED, "a batch of 1D sorts has no layout coordinates: use gfs_batch_init_positions and gfs_batch_results");
+    uint64_t want = 0;
+    for (size_t i = 0; i < b->ctxs.size(); ++i) {
+        const gfs_ctx *c = b->ctxs[i];
+        if (c->dims != b->dims || c->x_len != c->n_nodes * 2 * (uint64_t)b->dims || (c->x_len && !c->d_x))
+            return fail(GFS_E_STATE, "batch item " + std::to_string(i) + ": needs a context set up for layouts of " + std::to_string(b->dims) + " dimensions");
+        want += c->x_len;
+    }
+    if (total != want) return fail(GFS_E_ARG, "total is not the batch's node count * 2 * dimensions (gfs_batch_result_offsets)");
+    return GFS_OK;
+}
+// One call either way.  Device buffer and pinned staging: [packed coordinates | CoordItem table | block table]; up, the whole of it
+// goes in one copy; down, the two tables go up and the coordinates come back.
+static int batch_coords_move(gfs_batch *b, double *coords, uint64_t total, int to_device, double *kernel_ms, hipStream_t st) {
+    if (kernel_ms) *kernel_ms = 0.0;
+    const uint64_t n = b->ctxs.size();
+    std::vector<uint64_t> nodes(n), word_offset(n + 1), first_block(n + 1);
+    for (uint64_t i = 0; i < n; ++i) nodes[i] = b->ctxs[i]->n_nodes;
+    const uint64_t blocks = gfs::coord_plan(nodes.data(), n, (uint32_t)b->dims, word_offset.data(), first_block.data());
+    if (blocks > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, "the batch's coordinates exceed one launch");
+    if (total == 0) return GFS_OK;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipDeviceSynchronize());                                        // as gfs_ctx_download_positions: nothing of an item is in flight
+    const uint64_t tables_at = total * sizeof(double), blocks_at = tables_at + n * sizeof(gfs::CoordItem);
+    const uint64_t bytes = blocks_at + blocks * sizeof(uint32_t);
+    int rc = batch_staging(b, bytes);
+    if (!rc) rc = batch_device_buffer(&b->d_coords, &b->coords_bytes, bytes);
+    if (rc) return rc;
+    if (!b->readout_e0) HIPCHK(hipEventCreate(&b->readout_e0));
+    if (!b->readout_e1) HIPCHK(hipEventCreate(&b->readout_e1));
+    unsigned char *h = reinterpret_cast<unsigned char *>(b->h_packed), *d = reinterpret_cast<unsigned char *>(b->d_coords);
+    gfs::CoordItem *h_items = reinterpret_cast<gfs::CoordItem *>(h + tables_at);
+    for (uint64_t i = 0; i < n; ++i) {                                     // from the contexts as they are now (positions may have been bound anew)
+        const gfs_ctx *c = b->ctxs[i];
+        h_items[i] = gfs::CoordItem{c->d_x, c->d_perm, word_offset[i], (uint32_t)c->n_nodes, (uint32_t)first_block[i], (uint32_t)b->dims, 0u};
+    }
+    gfs::block_item_table(first_block.data(), n, reinterpret_cast<uint32_t *>(h + blocks_at));
+    if (to_device) {
+        std::memcpy(h, coords, total * sizeof(double));
+        HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
+    } else {
+        HIPCHK(hipMemcpyAsync(d + tables_at, h + tables_at, bytes - tables_at, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipEventRecord(b->readout_e0, st));
+    hipError_t e = gfs::batch_coords_device(reinterpret_cast<const gfs::CoordItem *>(d + tables_at), reinterpret_cast<const uint32_t *>(d + blocks_at),
+                                            blocks, reinterpret_cast<double *>(d), to_device, st);
+    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch coordinates launch: ") + hipGetErrorString(e));
+    HIPCHK(hipEventRecord(b->readout_e1, st));
+    if (!to_device) HIPCHK(hipMemcpyAsync(h, d, total * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (!to_device) std::memcpy(coords, h, total * sizeof(double));
+    float t = 0.f;
+    if (kernel_ms && hipEventElapsedTime(&t, b->readout_e0, b->readout_e1) == hipSuccess) *kernel_ms = t;
+    return GFS_OK;
+}
+
+int gfs_batch_upload_coords(gfs_batch *b, const double *coords, uint64_t total, void *hip_stream) {
+    int rc = batch_coords_check(b, coords, total);
+    if (rc) return rc;
+    return batch_coords_move(b, const_cast<double *>(coords), total, 1, nullptr, (hipStream_t)hip_stream);
+}
+
+int gfs_batch_coords(gfs_batch *b, double *coords, uint64_t total, double *kernel_ms, void *hip_stream) {
+    int rc = batch_coords_check(b, coords, total);
+    if (rc) return rc;
+    return batch_coords_move(b, coords, total, 0, kernel_ms, (hipStream_t)hip_stream);
+}
+
+// ---- K7g: gfs_ctx_pair_errors of every item, sorts and layouts alike, in one step launch and one reduce launch --------------------
+int gfs_batch_pair_errors(gfs_batch *b, const uint64_t *zs, uint64_t n_z, gfs_pair_error *out, double *kernel_ms, void *hip_stream) {
+    if (!b) return fail(GFS_E_ARG, "batch is null");
+    int rc = check_step_distances(zs, n_z, out);
+    if (rc) return rc;
+    const uint64_t n = b->ctxs.size();
+    for (uint64_t i = 0; i < n; ++i)
+        if (!b->ctxs[i]->d_x || b->ctxs[i]->dims != b->dims)
+            return fail(GFS_E_STATE, "batch item " + std::to_string(i) + ": the context has no positions (not set up)");
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (n_z == 0) return GFS_OK;
+    std::vector<uint64_t> steps(n), first_block(n + 1);
+    for (uint64_t i = 0; i < n; ++i) steps[i] = b->ctxs[i]->n_steps;
+    const uint64_t row_blocks = gfs::quality_plan(steps.data(), n, first_block.data());
+    if (row_blocks > 0x7FFFFFFFull || n > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, "the batch's step tables exceed one launch");
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    // device: [zs | QualityItem table | block table (whole words) | out words | partials]; the first three go up in one copy
+    const uint64_t items_at = n_z * 8, blocks_at = items_at + n * sizeof(gfs::QualityItem);
+    const uint64_t out_at = blocks_at + (row_blocks * sizeof(uint32_t) + 7) / 8 * 8, out_bytes = n * n_z * 5 * 8;
+    const uint64_t partials_at = out_at + out_bytes, bytes = partials_at + 5 * n_z * row_blocks * 8;
+    rc = batch_staging(b, out_at + out_bytes);                             // (staging: the same offsets, less the partials)
+    if (!rc) rc = batch_device_buffer(&b->d_quality, &b->quality_bytes, bytes);
+    if (rc) return rc;
+    if (!b->readout_e0) HIPCHK(hipEventCreate(&b->readout_e0));
+    if (!b->readout_e1) HIPCHK(hipEventCreate(&b->readout_e1));
+    unsigned char *h = reinterpret_cast<unsigned char *>(b->h_packed), *d = reinterpret_cast<unsigned char *>(b->d_quality);
+    std::memcpy(h, zs, n_z * 8);
+    gfs::QualityItem *h_items = reinterpret_cast<gfs::QualityItem *>(h + items_at);
+    for (uint64_t i = 0; i < n; ++i) {
+        const gfs_ctx *c = b->ctxs[i];
+        h_items[i] = gfs::QualityItem{c->d_step_rec, c->d_x, c->n_steps, c->n_nodes, (uint32_t)first_block[i], (uint32_t)(first_block[i + 1] - first_block[i])};
+    }
+    gfs::block_item_table(first_block.data(), n, reinterpret_cast<uint32_t *>(h + blocks_at));
+    HIPCHK(hipMemcpyAsync(d, h, blocks_at + row_blocks * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(b->readout_e0, st));
+    hipError_t e = gfs::batch_pair_errors_device(reinterpret_cast<const gfs::QualityItem *>(d + items_at), reinterpret_cast<const uint32_t *>(d + blocks_at),
+                                                 (uint32_t)n, row_blocks, (uint32_t)b->dims, reinterpret_cast<const uint64_t *>(d), (uint32_t)n_z,
+                                                 reinterpret_cast<uint64_t *>(d + partials_at), reinterpret_cast<uint64_t *>(d + out_at), st);
+    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch pair_errors launch: ") + hipGetErrorString(e));
+    HIPCHK(hipEventRecord(b->readout_e1, st));
+    HIPCHK(hipMemcpyAsync(h + out_at, d + out_at, out_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t *w = reinterpret_cast<const uint64_t *>(h + out_at);
+    for (uint64_t r = 0; r < n * n_z; ++r) {
+        gfs_pair_error &o = out[r];
+        o.step_distance = zs[r % n_z]; o.pairs = w[5 * r];
+        std::memcpy(&o.sum_rel_sq, &w[5 * r + 1], 8); std::memcpy(&o.max_rel_sq, &w[5 * r + 2], 8);
+        std::memcpy(&o.sum_abs, &w[5 * r + 3], 8); std::memcpy(&o.sum_sq, &w[5 * r + 4], 8);
+    }
     float t = 0.f;
     if (kernel_ms && hipEventElapsedTime(&t, b->readout_e0, b->readout_e1) == hipSuccess) *kernel_ms = t;
     return GFS_OK;

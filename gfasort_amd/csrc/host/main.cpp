@@ -20,7 +20,7 @@ using namespace gfasort;
 struct Args {
     std::string input, output, pipeline = "sYgs", layout_out;
     std::string layout_option;                     // the last of --dimensions / --layout-out / --layout-iter given: -p L only
-    std::string batch_list;                        // --batch: a file of in.gfa<TAB>out.gfa lines, all sorted in one invocation
+    std::string batch_list;                        // --batch: a file of in.gfa<TAB>out.gfa[<TAB>layout.tsv] lines, all run in one invocation
     size_t iter_max = 100, threads = 1, dimensions = 2, layout_iter = 30;
     unsigned verbose = 1;
     uint64_t streams = 0; uint32_t flags = 0;      // HIP launch shape (extra, not in the reference)
@@ -59,6 +59,10 @@ static void usage() {
         "                   (LIST: one in.gfa<TAB>out.gfa per line; every graph is sorted as a -i/-o run sorts it, the small ones —\n"
         "                    those that run reference streams — together in one persistent launch that fills the device, the\n"
         "                    others alone)\n"
+        "       gfasort_hip --batch LIST -p L [the options above, except -i, -o, --layout-out and those of -p Y]\n"
+        "                   (LIST: one in.gfa<TAB>out.gfa<TAB>layout.tsv per line; every graph is laid out as a -i/-o/--layout-out run\n"
+        "                    lays it out, the small ones of 2 or 3 dimensions together in one persistent launch, the others alone.\n"
+        "                    With --stress-profile either kind of batch measures its graphs while they are resident)\n"
         "Pipeline characters: Y = path-guided SGD sort, L = nD layout (HIP engine).\n"
         "g, s, S, u exist in the reference but are not part of this build.\n";
 }
@@ -97,8 +101,16 @@ static bool parse_args(int argc, char **argv, Args &a) {
     }
     if (!a.batch_list.empty()) {
         if (!a.input.empty() || !a.output.empty()) { std::cerr << "error: --batch takes its inputs and outputs from LIST: not with -i / -o\n"; return false; }
-        if (!a.layout_option.empty()) { std::cerr << "error: --batch sorts (-p Y): " << a.layout_option << " belongs to -p L\n"; return false; }
-        if (a.pipeline != "Y") { std::cerr << "error: --batch sorts many graphs in one launch: it needs -p Y exactly, not -p " << a.pipeline << "\n"; return false; }
+        if (a.pipeline != "Y" && a.pipeline != "L") {
+            std::cerr << "error: --batch runs one step over many graphs in one launch: it needs -p Y or -p L exactly, not -p " << a.pipeline << "\n";
+            return false;
+        }
+        if (a.pipeline == "Y" && !a.layout_option.empty()) { std::cerr << "error: --batch sorts (-p Y): " << a.layout_option << " belongs to -p L\n"; return false; }
+        if (a.pipeline == "L" && !a.layout_out.empty()) {
+            std::cerr << "error: --batch -p L takes its layout files from LIST (in.gfa<TAB>out.gfa<TAB>layout.tsv): not with --layout-out\n";
+            return false;
+        }
+        if (a.pipeline == "L" && a.phased) { std::cerr << "error: --batch lays out (-p L): --phased-sampler belongs to -p Y\n"; return false; }
         return true;
     }
     if (a.input.empty() || a.output.empty()) { std::cerr << "error: -i and -o are required\n"; return false; }
@@ -188,70 +200,141 @@ static void print_run_stats(const gfs_stats &st) {
               << st.total_ms << " ms\n";
 }
 
+// One column more than a sort's list: where the graph's layout goes.
+struct BatchFiles { std::string in, out, layout; };
+
+// The lines of LIST: in.gfa<TAB>out.gfa under -p Y, in.gfa<TAB>out.gfa<TAB>layout.tsv under -p L.  Needs no device.
+static bool read_batch_list(const Args &args, bool layouts, std::vector<BatchFiles> &files) {
+    std::ifstream list(args.batch_list);
+    if (!list) { std::cerr << "Error reading file: " << args.batch_list << ": " << std::strerror(errno) << "\n"; return false; }
+    std::string line;
+    size_t n = 0;
+    while (std::getline(list, line)) {
+        ++n;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        std::vector<std::string> cols;
+        size_t from = 0;
+        for (size_t tab; (tab = line.find('\t', from)) != std::string::npos; from = tab + 1) cols.push_back(line.substr(from, tab - from));
+        cols.push_back(line.substr(from));
+        bool ok = cols.size() == (layouts ? 3u : 2u);
+        for (const std::string &c : cols) ok = ok && !c.empty();
+        if (!ok) {
+            std::cerr << "Error: " << args.batch_list << " line " << n << ": expected "
+                      << (layouts ? "in.gfa<TAB>out.gfa<TAB>layout.tsv (--batch -p L; two columns are a -p Y list)" : "in.gfa<TAB>out.gfa") << "\n";
+            return false;
+        }
+        files.push_back(BatchFiles{cols[0], cols[1], layouts ? cols[2] : std::string()});
+    }
+    if (files.empty()) { std::cerr << "Error: " << args.batch_list << " lists no graph\n"; return false; }
+    return true;
+}
+
+static void print_batch_stats(const gfs_batch_stats &bs) {
+    std::cerr << "[gfasort_hip] batch: " << bs.items_run << " graphs in " << bs.launches << (bs.launches == 1 ? " launch" : " launches")
+              << " of " << bs.blocks << " workgroups; kernels " << bs.kernel_ms << " ms ("
+              << (bs.kernel_ms > 0 ? (double)bs.term_updates / bs.kernel_ms / 1e6 : 0.0) << " G updates/s), run " << bs.total_ms << " ms\n";
+}
+
+// --batch LIST -p L: every graph of the list gets its own LayoutSGDParams::from_graph, as a -i/-o run gives it; those of 2 or 3
+// dimensions that run reference streams are laid out in one batch, the others alone; every output is what the single run writes.
+static int run_layout_batch(const Args &args, const std::vector<BatchFiles> &files, std::vector<BidirectedGraph> &graphs) {
+    std::vector<BatchLayoutItem> items(files.size());
+    for (size_t i = 0; i < files.size(); ++i) {
+        items[i].graph = &graphs[i];
+        items[i].params = LayoutSGDParams::from_graph(graphs[i], args.dimensions, args.threads);
+        items[i].params.iter_max = args.layout_iter;
+        items[i].params.progress = args.verbose >= 2;
+    }
+    HipOptions opt; opt.cfg.n_streams = args.streams; opt.cfg.flags = args.flags | GFS_F_BUNDLE(args.bundle);
+    try {
+        const gfs_batch_stats bs = sgd_layout_batch(items, (uint8_t)args.verbose, opt, args.stress_profile);
+        for (size_t i = 0; i < items.size(); ++i) {
+            const BatchLayoutItem &it = items[i];
+            if (args.verbose >= 1) {
+                std::cerr << "[gfasort_hip] " << files[i].in << ": " << graphs[i].node_count() << " nodes, "
+                          << (it.batched ? "in the batch" : it.stats.iterations ? "alone" : "nothing to do") << "\n";
+                char buf[64]; snprintf(buf, sizeof buf, "%.6f", calculate_layout_stress(graphs[i], it.layout, 10000));
+                std::cerr << "[gfasort] layout stress: " << buf << "\n";
+                if (it.stats.iterations) print_run_stats(it.stats);
+            }
+            if (args.stress_profile && it.layout.num_nodes) {
+                if (it.batched) print_stress_profile(it.profile);                     // read while the batch was resident
+                else { FlatGraph f = graphs[i].flatten(); print_stress_profile(layout_pair_errors(f, it.layout.dimensions, it.layout.coords, step_distance_ladder(f))); }
+            }
+            if (args.diagnose && it.layout.num_nodes) print_diagnosis(graphs[i].flatten(), graphs[i].paths, it.layout.dimensions, it.layout.coords, args.diagnose_ratio);
+        }
+        if (args.verbose >= 1) print_batch_stats(bs);
+    } catch (const std::exception &e) {
+        std::cerr << "Error: " << e.what() << "\n";
+        return 1;
+    }
+    for (size_t i = 0; i < files.size(); ++i) {
+        if (args.verbose >= 1) std::cerr << "[gfasort] writing layout to " << files[i].layout << "\n";
+        std::ofstream f(files[i].layout, std::ios::binary);
+        if (!f) { std::cerr << "Error creating layout file: " << std::strerror(errno) << "\n"; return 1; }
+        items[i].layout.write_tsv(f);
+        f.close();
+        if (!f) { std::cerr << "Error writing layout file " << files[i].layout << ": " << std::strerror(errno) << "\n"; return 1; }
+    }
+    return 0;
+}
+
 // --batch LIST -p Y: every graph of the list gets its own YgsParams::from_graph, as a -i/-o run gives it; those that run reference
 // streams are sorted in one batch, the others alone; every output is what the single run writes.
-static int run_batch(const Args &args) {
-    std::thread warm([] { (void)gfs_warmup(0); });
-    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{warm};
-    std::vector<std::pair<std::string, std::string>> files;
-    {
-        std::ifstream list(args.batch_list);
-        if (!list) { std::cerr << "Error reading file: " << args.batch_list << ": " << std::strerror(errno) << "\n"; return 1; }
-        std::string line;
-        size_t n = 0;
-        while (std::getline(list, line)) {
-            ++n;
-            if (!line.empty() && line.back() == '\r') line.pop_back();
-            if (line.empty()) continue;
-            const size_t tab = line.find('\t');
-            if (tab == std::string::npos || tab == 0 || tab + 1 == line.size() || line.find('\t', tab + 1) != std::string::npos) {
-                std::cerr << "Error: " << args.batch_list << " line " << n << ": expected in.gfa<TAB>out.gfa\n";
-                return 1;
-            }
-            files.emplace_back(line.substr(0, tab), line.substr(tab + 1));
-        }
-    }
-    if (files.empty()) { std::cerr << "Error: " << args.batch_list << " lists no graph\n"; return 1; }
-    std::vector<BidirectedGraph> graphs(files.size());
+static int run_sort_batch(const Args &args, const std::vector<BatchFiles> &files, std::vector<BidirectedGraph> &graphs) {
     std::vector<BatchSortItem> items(files.size());
     for (size_t i = 0; i < files.size(); ++i) {
-        if (args.verbose >= 1) std::cerr << "[gfasort] reading " << files[i].first << "\n";
-        try { graphs[i] = parse_gfa(read_file(files[i].first)); }
-        catch (const std::exception &e) { std::cerr << "Error reading " << files[i].first << ": " << e.what() << "\n"; return 1; }
         items[i].graph = &graphs[i];
         items[i].params = YgsParams::from_graph(graphs[i], (uint8_t)args.verbose, args.threads).path_sgd;
         items[i].params.iter_max = args.iter_max;
     }
     HipOptions opt; opt.cfg.n_streams = args.streams; opt.cfg.flags = args.flags | GFS_F_BUNDLE(args.bundle);
     if (args.phased) opt.cfg.flags |= GFS_F_PHASED;
-    gfs_batch_stats bs{};
     try {
-        bs = sgd_sort_batch(items, (uint8_t)args.verbose, opt, args.stress_profile || args.diagnose);
+        const gfs_batch_stats bs = sgd_sort_batch(items, (uint8_t)args.verbose, opt, args.stress_profile || args.diagnose, args.stress_profile);
         for (size_t i = 0; i < items.size(); ++i) {
             const BatchSortItem &it = items[i];
             if (args.verbose >= 1) {
-                std::cerr << "[gfasort_hip] " << files[i].first << ": " << graphs[i].node_count() << " nodes, "
+                std::cerr << "[gfasort_hip] " << files[i].in << ": " << graphs[i].node_count() << " nodes, "
                           << (it.batched ? "in the batch" : it.stats.iterations ? "alone" : "nothing to do") << "\n";
                 if (it.stats.iterations) print_run_stats(it.stats);
             }
-            if (args.stress_profile && !it.positions.empty()) print_stress_profile(layout_pair_errors(it.before, 0, it.positions, step_distance_ladder(it.before)));
+            if (args.stress_profile && !it.positions.empty()) {
+                if (it.batched) print_stress_profile(it.profile);                     // read while the batch was resident
+                else print_stress_profile(layout_pair_errors(it.before, 0, it.positions, step_distance_ladder(it.before)));
+            }
             if (args.diagnose && !it.positions.empty()) print_diagnosis(it.before, graphs[i].paths, 0, it.positions, args.diagnose_ratio);
         }
-        if (args.verbose >= 1)
-            std::cerr << "[gfasort_hip] batch: " << bs.items_run << " graphs in " << bs.launches << (bs.launches == 1 ? " launch" : " launches")
-                      << " of " << bs.blocks << " workgroups; kernels " << bs.kernel_ms << " ms ("
-                      << (bs.kernel_ms > 0 ? (double)bs.term_updates / bs.kernel_ms / 1e6 : 0.0) << " G updates/s), run " << bs.total_ms << " ms\n";
+        if (args.verbose >= 1) print_batch_stats(bs);
     } catch (const std::exception &e) {
         std::cerr << "Error: " << e.what() << "\n";
         return 1;
     }
+    return 0;
+}
+
+static int run_batch(const Args &args) {
+    const bool layouts = args.pipeline == "L";
+    std::vector<BatchFiles> files;
+    if (!read_batch_list(args, layouts, files)) return 1;
+    std::thread warm([] { (void)gfs_warmup(0); });
+    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{warm};
+    std::vector<BidirectedGraph> graphs(files.size());
     for (size_t i = 0; i < files.size(); ++i) {
-        if (args.verbose >= 1) std::cerr << "[gfasort] writing " << files[i].second << "\n";
-        std::ofstream f(files[i].second, std::ios::binary);
+        if (args.verbose >= 1) std::cerr << "[gfasort] reading " << files[i].in << "\n";
+        try { graphs[i] = parse_gfa(read_file(files[i].in)); }
+        catch (const std::exception &e) { std::cerr << "Error reading " << files[i].in << ": " << e.what() << "\n"; return 1; }
+    }
+    const int rc = layouts ? run_layout_batch(args, files, graphs) : run_sort_batch(args, files, graphs);
+    if (rc) return rc;
+    for (size_t i = 0; i < files.size(); ++i) {
+        if (args.verbose >= 1) std::cerr << "[gfasort] writing " << files[i].out << "\n";
+        std::ofstream f(files[i].out, std::ios::binary);
         if (!f) { std::cerr << "Error writing output file: " << std::strerror(errno) << "\n"; return 1; }
         graphs[i].write_gfa(f);
         f.close();                                                                    // (a full disk shows here at the latest)
-        if (!f) { std::cerr << "Error writing output file " << files[i].second << ": " << std::strerror(errno) << "\n"; return 1; }
+        if (!f) { std::cerr << "Error writing output file " << files[i].out << ": " << std::strerror(errno) << "\n"; return 1; }
     }
     if (warm.joinable()) warm.join();
     std::cerr.flush(); std::cout.flush();

@@ -237,7 +237,24 @@ void sgd_sort_only(BidirectedGraph &g, const PathSGDParams &p, uint8_t verbose, 
     if (verbose >= 2) std::cerr << "[path_sgd] Complete\n";
 }
 
-gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbose, const HipOptions &opt, bool keep_positions) {
+// The pair errors of every item of a resident batch at its own step_distance_ladder, in ONE gfs_batch_pair_errors: the ladders are
+// prefixes of the longest one (the rungs do not depend on the graph, only where they stop), so the longest is measured for
+// all and every item keeps its own rungs.  fs[k]: the flattened graph of batch item k; out[k]: its rows.
+static void batch_profiles(gfs_batch *b, const std::vector<const FlatGraph *> &fs, const std::vector<std::vector<gfs_pair_error> *> &out) {
+    std::vector<std::vector<uint64_t>> ladders;
+    size_t longest = 0;
+    for (const FlatGraph *f : fs) {
+        ladders.push_back(step_distance_ladder(*f));
+        if (ladders.back().size() > ladders[longest].size()) longest = ladders.size() - 1;
+    }
+    const std::vector<uint64_t> &zs = ladders[longest];
+    std::vector<gfs_pair_error> rows(fs.size() * zs.size());
+    check(gfs_batch_pair_errors(b, zs.data(), zs.size(), rows.data(), nullptr, nullptr));
+    for (size_t k = 0; k < fs.size(); ++k)
+        out[k]->assign(rows.begin() + (std::ptrdiff_t)(k * zs.size()), rows.begin() + (std::ptrdiff_t)(k * zs.size() + ladders[k].size()));
+}
+
+gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbose, const HipOptions &opt, bool keep_positions, bool keep_profile) {
     struct Slot { gfs_ctx *ctx = nullptr; FlatGraph f; };
     std::vector<Slot> slots(items.size());
     struct Cleanup {
@@ -271,7 +288,7 @@ gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbos
     std::vector<size_t> together;                                                     // indices into items: the batch's candidates
     for (size_t i = 0; i < items.size(); ++i) {
         BatchSortItem &it = items[i];
-        it.stats = gfs_stats{}; it.batched = false; it.positions.clear();
+        it.stats = gfs_stats{}; it.batched = false; it.positions.clear(); it.profile.clear();
         if (!it.graph || it.graph->node_count() == 0) continue;                       // sgd.rs:242-244
         slots[i].f = it.graph->flatten();
         gfs_graph_view v = slots[i].f.view();
@@ -316,6 +333,12 @@ gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbos
         double readout_ms = 0.0;
         check(gfs_batch_results(cleanup.b, x.data(), order.data(), offsets.back(), &readout_ms, nullptr));
         if (verbose >= 2) std::cerr << "[gfasort_hip] batch: read-out of " << together.size() << " graphs, " << readout_ms << " ms on the device\n";
+        if (keep_profile) {
+            std::vector<const FlatGraph *> fs;
+            std::vector<std::vector<gfs_pair_error> *> rows;
+            for (size_t i : together) { fs.push_back(&slots[i].f); rows.push_back(&items[i].profile); }
+            batch_profiles(cleanup.b, fs, rows);
+        }
         gfs_batch_destroy(cleanup.b); cleanup.b = nullptr;                            // (before its contexts go)
         for (size_t k = 0; k < together.size(); ++k) {
             const size_t i = together[k];
@@ -356,6 +379,93 @@ Layout path_linear_sgd_layout(const BidirectedGraph &g, const LayoutSGDParams &p
     Layout l(p.dimensions, N);
     l.coords = std::move(coords);
     return l;
+}
+
+gfs_batch_stats sgd_layout_batch(std::vector<BatchLayoutItem> &items, uint8_t verbose, const HipOptions &opt, bool keep_profile) {
+    struct Slot { gfs_ctx *ctx = nullptr; FlatGraph f; };
+    std::vector<Slot> slots(items.size());
+    struct Cleanup {
+        std::vector<Slot> &s; gfs_batch *b = nullptr;
+        ~Cleanup() { if (b) gfs_batch_destroy(b); for (auto &x : s) if (x.ctx) gfs_ctx_destroy(x.ctx); }
+    } cleanup{slots};
+    gfs_batch_stats bs{};
+    // a graph that runs alone: the single call, after its context (if any) has left the device
+    auto finish_alone = [&](size_t i) {
+        if (slots[i].ctx) { gfs_ctx_destroy(slots[i].ctx); slots[i].ctx = nullptr; }
+        items[i].layout = path_linear_sgd_layout(*items[i].graph, items[i].params, opt, &items[i].stats);
+    };
+    std::vector<size_t> candidates;                                                   // indices into items, of either dimension
+    for (size_t i = 0; i < items.size(); ++i) {
+        BatchLayoutItem &it = items[i];
+        it.stats = gfs_stats{}; it.batched = false; it.profile.clear();
+        const size_t D = it.params.dimensions;
+        it.layout = Layout(D, 0);
+        if (!it.graph || it.graph->node_count() == 0) continue;                       // sgd.rs:780-782
+        if (D != 2 && D != 3) { finish_alone(i); continue; }                          // no batch kernel for the dimension
+        slots[i].f = it.graph->flatten();
+        gfs_graph_view v = slots[i].f.view();
+        gfs_layout_params cp = it.params.to_c();
+        check(gfs_ctx_create(&v, 0, &slots[i].ctx));
+        const int rc = gfs_ctx_setup_nd(slots[i].ctx, &cp, &opt.cfg, nullptr, nullptr);
+        check(rc);
+        if (rc != GFS_NOTHING_TO_DO) check(gfs_ctx_stats(slots[i].ctx, &it.stats));
+        if (rc == GFS_NOTHING_TO_DO || it.stats.bundle != 1) { it.stats = gfs_stats{}; finish_alone(i); continue; }   // (the single call says why)
+        candidates.push_back(i);                                                      // stays resident until its batch has run
+    }
+    for (size_t D : {(size_t)2, (size_t)3}) {
+        std::vector<size_t> together, refused;
+        for (size_t i : candidates) if (items[i].params.dimensions == D) together.push_back(i);
+        while (!together.empty() && !cleanup.b) {                                     // sgd_sort_batch's refusal loop
+            std::vector<gfs_ctx *> ctxs;
+            for (size_t i : together) ctxs.push_back(slots[i].ctx);
+            const int rc = gfs_batch_create(ctxs.data(), ctxs.size(), nullptr, &cleanup.b);
+            if (rc != GFS_E_UNSUPPORTED) { check(rc); break; }
+            const std::string why = gfs_last_error();
+            unsigned long long named = 0;
+            const size_t at = why.find("batch item ");
+            if (at == std::string::npos || std::sscanf(why.c_str() + at, "batch item %llu", &named) != 1 || named >= together.size()) check(rc);
+            if (verbose >= 1) std::cerr << "[gfasort_hip] batch: graph " << together[named] << " runs alone (" << why << ")\n";
+            refused.push_back(together[named]);
+            together.erase(together.begin() + (std::ptrdiff_t)named);
+        }
+        if (cleanup.b) {
+            // start coordinates, the run and the read-out of all its graphs: one call each (K4c, K2f, K6c)
+            std::vector<uint64_t> offsets(together.size() + 1);
+            check(gfs_batch_result_offsets(cleanup.b, offsets.data(), offsets.size()));
+            std::vector<double> coords(offsets.back() * 2 * D);
+            for (size_t k = 0; k < together.size(); ++k) {
+                const std::vector<double> c0 = default_layout_init(slots[together[k]].f, D, items[together[k]].params.seed);
+                std::copy(c0.begin(), c0.end(), coords.begin() + (std::ptrdiff_t)(offsets[k] * 2 * D));
+            }
+            check(gfs_batch_upload_coords(cleanup.b, coords.data(), coords.size(), nullptr));
+            check(gfs_batch_run(cleanup.b, nullptr));
+            gfs_batch_stats one{};
+            check(gfs_batch_get_stats(cleanup.b, &one));
+            bs.items += one.items; bs.items_run += one.items_run; bs.launches += one.launches; bs.blocks += one.blocks;
+            bs.term_updates += one.term_updates; bs.attempts += one.attempts; bs.kernel_ms += one.kernel_ms; bs.total_ms += one.total_ms;
+            double readout_ms = 0.0;
+            check(gfs_batch_coords(cleanup.b, coords.data(), coords.size(), &readout_ms, nullptr));
+            if (verbose >= 2) std::cerr << "[gfasort_hip] batch: coordinates of " << together.size() << " graphs, " << readout_ms << " ms on the device\n";
+            if (keep_profile) {
+                std::vector<const FlatGraph *> fs;
+                std::vector<std::vector<gfs_pair_error> *> rows;
+                for (size_t i : together) { fs.push_back(&slots[i].f); rows.push_back(&items[i].profile); }
+                batch_profiles(cleanup.b, fs, rows);
+            }
+            gfs_batch_destroy(cleanup.b); cleanup.b = nullptr;                        // (before its contexts go)
+            for (size_t k = 0; k < together.size(); ++k) {
+                const size_t i = together[k];
+                BatchLayoutItem &it = items[i];
+                it.batched = true;
+                check(gfs_ctx_stats(slots[i].ctx, &it.stats));
+                gfs_ctx_destroy(slots[i].ctx); slots[i].ctx = nullptr;
+                it.layout = Layout(D, slots[i].f.node_len.size());
+                std::copy(coords.begin() + (std::ptrdiff_t)(offsets[k] * 2 * D), coords.begin() + (std::ptrdiff_t)(offsets[k + 1] * 2 * D), it.layout.coords.begin());
+            }
+        }
+        for (size_t i : refused) finish_alone(i);
+    }
+    return bs;
 }
 
 // ---- calculate_layout_stress (sgd.rs:1196-1283) -----------------------------------------------------

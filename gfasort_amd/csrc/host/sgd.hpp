@@ -109,9 +109,29 @@ struct BatchSortItem {
     bool batched = false;
     FlatGraph before;                      // keep_positions: the graph as it was flattened before the sort ...
     std::vector<double> positions;         // ... and the final positions by its dense index; empty where there was nothing to do
+    std::vector<gfs_pair_error> profile;   // keep_profile, batched graphs: layout_pair_errors at step_distance_ladder, read while resident
 };
 // Returns the batch's figures (all zero where no graph was batched).  Throws std::runtime_error on a HIP / argument error.
-gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbose, const HipOptions &opt = {}, bool keep_positions = false);
+// keep_profile: the batched graphs' pair errors at their step_distance_ladder are read from the batch while it is resident
+// (gfs_batch_pair_errors: one call for all of them), the figures layout_pair_errors gives for the kept positions.
+gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbose, const HipOptions &opt = {}, bool keep_positions = false,
+                               bool keep_profile = false);
+// path_linear_sgd_layout over MANY graphs (no reference equivalent; gfasort_hip --batch -p L), the layout twin of sgd_sort_batch.
+// Every graph gets its own parameters and its own default_layout_init.  Graphs of 2 or 3 dimensions for which the policy picks
+// the pooled reference-stream kernel (stats.bundle == 1) run together, one gfs_batch per dimension: all start coordinates up
+// in one call, one persistent launch (or as few as fit the device), all final coordinates down in one call.  The others —
+// 4 to 8 dimensions, a team-kernel graph, a graph gfs_batch_create refuses (its error names the item) — run alone through
+// path_linear_sgd_layout.  Every Layout is what the single run returns.
+struct BatchLayoutItem {
+    const BidirectedGraph *graph = nullptr;
+    LayoutSGDParams params;
+    Layout layout;                         // what path_linear_sgd_layout returns for the graph
+    gfs_stats stats{};                     // the graph's own (a batched graph's kernel_ms is the batch's: 0 here)
+    bool batched = false;
+    std::vector<gfs_pair_error> profile;   // keep_profile, batched graphs: as BatchSortItem::profile, of the final coordinates
+};
+// Returns the batches' figures, summed where both dimensions had one (all zero where no graph was batched).
+gfs_batch_stats sgd_layout_batch(std::vector<BatchLayoutItem> &items, uint8_t verbose, const HipOptions &opt = {}, bool keep_profile = false);
 // sgd.rs:773.  Gaussian start of dims >= 1 is drawn here (Box-Muller on SplitMix64(seed); the
 // reference's rand_distr ziggurat stream is not reproduced).
 Layout path_linear_sgd_layout(const BidirectedGraph &g, const LayoutSGDParams &p, const HipOptions &opt = {},

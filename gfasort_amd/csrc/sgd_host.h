@@ -77,6 +77,31 @@ hipError_t batch_init_positions_device(const ReadoutItem *d_items, uint32_t coun
 hipError_t sort_segments_device(const ReadoutItem *d_items, uint32_t count, uint32_t padded, double *d_positions, uint32_t *d_order,
                                 hipStream_t st);
 
+// batch_quality_kernels.hip (K4c / K6c, K7g): flat launches over all items of a batch; workgroup b works on item block_item[b] and
+// is that item's local block b - first_block (batch_readout_plan.h builds first_block and block_item).
+// K4c / K6c: x, perm and n are the item's context's (dims = D >= 1: x is the end x dimension planes); offset is the item's first
+// word in the packed array, Layout.coords order.  first_block counts workgroups of COORD_BLOCK words.
+struct CoordItem {
+    double *x;
+    const uint32_t *perm;
+    uint64_t offset;
+    uint32_t n, first_block, dims, _pad;
+};
+// to_device = 1: packed -> the items' planes (what reorder_positions_device writes per item), else planes -> packed.  Asynchronous.
+hipError_t batch_coords_device(const CoordItem *d_items, const uint32_t *d_block_item, uint64_t blocks, double *d_packed, int to_device,
+                               hipStream_t st);
+// K7g: blocks = quality_blocks(n_steps), first_block = the sum of the blocks of the items before it.
+struct QualityItem {
+    const uint4 *step_rec;
+    const double *x;
+    uint64_t n_steps, n_nodes;
+    uint32_t first_block, blocks;
+};
+// All pairs (s, s + z) of every item for n_z step distances.  row_blocks: the sum of the items' blocks; d_partials: 5 * n_z *
+// row_blocks words; d_out: 5 words per (item, distance), [item][z], as pair_errors_device writes them for one.  Asynchronous.
+hipError_t batch_pair_errors_device(const QualityItem *d_items, const uint32_t *d_block_item, uint32_t n_items, uint64_t row_blocks,
+                                    uint32_t dims, const uint64_t *d_zs, uint32_t n_z, uint64_t *d_partials, uint64_t *d_out, hipStream_t st);
+
 // quality_kernels.hip (K7): read-outs of the resident positions.  They write their own output buffers only.
 // Workgroups of the step passes: a function of n_steps alone, so that a result does not depend on the device.
 unsigned quality_blocks(uint64_t n_steps);

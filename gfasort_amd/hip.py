@@ -135,6 +135,7 @@ EXPORTS = [
     "gfs_ctx_path_errors", "gfs_ctx_stretched_pairs", "gfs_ctx_node_errors", "gfs_diagnose",
     "gfs_batch_plan", "gfs_batch_create", "gfs_batch_run", "gfs_batch_get_stats", "gfs_batch_destroy",
     "gfs_batch_result_offsets", "gfs_batch_init_positions", "gfs_batch_results", "gfs_batch_debug_sort_cap",
+    "gfs_batch_upload_coords", "gfs_batch_coords", "gfs_batch_pair_errors",
 ]
 SEGMENT_SORT_CAP = 8192                # GFS_SEGMENT_SORT_CAP
 
@@ -231,6 +232,9 @@ def lib():
         L.gfs_batch_init_positions.argtypes = [C.c_void_p, C.c_void_p]
         L.gfs_batch_results.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.gfs_batch_debug_sort_cap.argtypes = [C.c_void_p, C.c_uint64]
+        L.gfs_batch_upload_coords.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.gfs_batch_coords.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.gfs_batch_pair_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -762,6 +766,42 @@ class Batch:
     def debug_sort_cap(self, cap):
         """Test hook: items of more than cap nodes take the per-item sort (0 restores SEGMENT_SORT_CAP)."""
         check(lib().gfs_batch_debug_sort_cap(self._h, C.c_uint64(int(cap))))
+
+    # ---- a batch of layouts: every item's coordinates as one packed array (K4c / K6c) ----
+    def coords_offsets(self):
+        """offsets[i] = first double of item i in the packed coordinates (result_offsets() * 2 * D); offsets[items] = their length."""
+        return self.result_offsets() * np.uint64(2 * self.contexts[0].dims)
+
+    def upload_coords(self, coords, stream=None):
+        """Context.upload() on every item in one copy and one launch.  coords: one float64 array per item (Layout.coords order,
+        n_nodes * 2 * D each), or the packed array of all of them."""
+        if isinstance(coords, (list, tuple)):
+            coords = np.concatenate([np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in coords]) if coords else np.zeros(0)
+        coords = np.ascontiguousarray(coords, dtype=np.float64).reshape(-1)
+        buf = coords if coords.shape[0] else np.zeros(1)                 # (a pointer even where there is nothing to move)
+        check(lib().gfs_batch_upload_coords(self._h, _ptr(buf), C.c_uint64(coords.shape[0]), C.c_void_p(stream or 0)))
+
+    def coords(self, stream=None):
+        """Every item's download() in one launch and one copy: (list of float64 views of one packed array, one per item in the
+        order given; kernel_ms)."""
+        if self.contexts[0].dims == 0:
+            total, off = 0, None
+        else:
+            off = self.coords_offsets()
+            total = int(off[-1])
+        x = np.zeros(max(total, 1), dtype=np.float64)
+        ms = C.c_double(0.0)
+        check(lib().gfs_batch_coords(self._h, _ptr(x), C.c_uint64(total), C.byref(ms), C.c_void_p(stream or 0)))
+        return [x[int(off[i]):int(off[i + 1])] for i in range(len(self.contexts))], float(ms.value)
+
+    def pair_errors(self, zs, stream=None, return_ms=False):
+        """Context.pair_errors(zs) of every item, sorts and layouts alike, in one step launch and one reduce launch: a
+        PAIR_ERROR_DTYPE array of shape (items, len(zs)), row i bit for bit what contexts[i].pair_errors(zs) returns."""
+        zs = np.ascontiguousarray(zs, dtype=np.uint64)
+        out = np.zeros((len(self.contexts), zs.shape[0]), dtype=PAIR_ERROR_DTYPE)
+        ms = C.c_double(0.0)
+        check(lib().gfs_batch_pair_errors(self._h, _ptr(zs), C.c_uint64(zs.shape[0]), _ptr(out), C.byref(ms), C.c_void_p(stream or 0)))
+        return (out, float(ms.value)) if return_ms else out
 
 
 # ---- one-shot entry points ---------------------------------------------------------------------

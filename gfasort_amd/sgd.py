@@ -135,3 +135,71 @@ def path_sgd_sort_batch(graphs, params, cfg=None, max_blocks_per_launch: int = 0
     finally:
         for ctx in held.values():
             ctx.close()
+
+
+def path_linear_sgd_layout_batch(graphs, params, inits=None, cfg=None, max_blocks_per_launch: int = 0, device: int = 0):
+    """path_linear_sgd_layout over MANY graphs, the twin of path_sgd_sort_batch: the graphs whose plan is the pooled
+    reference-stream kernel (stats.bundle == 1) and whose dimension a batch kernel is built for (2 and 3) run together, one
+    hip.Batch per dimension — all start coordinates up in one Batch.upload_coords(), one persistent launch (or as few as fit
+    the device), all final coordinates down in one Batch.coords() — and the others alone through path_linear_sgd_layout, as
+    does a graph the batch refuses (hip.Batch names it).  params: one LayoutSGDParams for all, or one per graph; cfg likewise
+    (or None); inits: None, or one start array (Layout order) or None per graph — None draws default_layout_init.  Returns one
+    dict per graph, in order: layout (the Layout path_linear_sgd_layout returns), stats (hip.Stats, None for an empty graph)
+    and batched; and a dict dimension -> hip.BatchStats of the batches that ran."""
+    graphs = list(graphs)
+    per_graph = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * len(graphs)
+    params, cfgs = per_graph(params), per_graph(cfg)
+    inits = [None] * len(graphs) if inits is None else list(inits)
+    if len(params) != len(graphs) or len(cfgs) != len(graphs) or len(inits) != len(graphs):
+        raise ValueError("params / cfg / inits: one for all graphs or one per graph")
+    out = [None] * len(graphs)
+
+    def alone(i):
+        lay, st = path_linear_sgd_layout(graphs[i], params[i], inits[i], cfgs[i], return_stats=True)
+        out[i] = dict(layout=lay, stats=st, batched=False)
+
+    held = {}                                                  # graph index -> its Context, for the batches' candidates
+    try:
+        for i, (g, p, c) in enumerate(zip(graphs, params, cfgs)):
+            if g.n_nodes == 0 or p.dimensions not in (2, 3):
+                alone(i)
+                continue
+            ctx = hip.Context(g, device=device)
+            try:
+                rc = ctx.setup_nd(p, c)
+                if rc == hip.OK and ctx.stats().bundle == 1:
+                    held[i], ctx = ctx, None
+            finally:
+                if ctx is not None:
+                    ctx.close()                                # nothing to do, or a team-kernel graph: the single call's business
+            if i not in held:
+                alone(i)
+        batch_stats = {}
+        for D in (2, 3):
+            batched, batch = sorted(i for i in held if params[i].dimensions == D), None
+            while batched and batch is None:
+                try:
+                    batch = hip.Batch([held[i] for i in batched], max_blocks_per_launch)
+                except hip.GfsError as e:
+                    named = re.search(r"batch item (\d+)", str(e))
+                    if e.code != -5 or not named:              # GFS_E_UNSUPPORTED names the item: that one runs alone
+                        raise
+                    refused = batched.pop(int(named.group(1)))
+                    held.pop(refused).close()
+                    alone(refused)
+            if batch is None:
+                continue
+            try:
+                start = [inits[i] if inits[i] is not None else default_layout_init(graphs[i], D, params[i].seed) for i in batched]
+                batch.upload_coords(start)
+                batch.run()
+                batch_stats[D] = batch.stats()
+                coords, _ = batch.coords()
+            finally:
+                batch.close()
+            for k, i in enumerate(batched):
+                out[i] = dict(layout=Layout(D, graphs[i].n_nodes, coords[k].copy()), stats=held[i].stats(), batched=True)
+        return out, batch_stats
+    finally:
+        for ctx in held.values():
+            ctx.close()

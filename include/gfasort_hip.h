@@ -386,7 +386,10 @@ int gfs_diagnose(const gfs_graph_view *g, uint64_t dims, const double *positions
  * and gfs_ctx_sort_order do for one: gfs_batch_init_positions, one launch; gfs_batch_results, one launch per
  * padded segment length and two copies, a workgroup sorting its item's (key, dense index) pairs in LDS.  Items of more than
  * GFS_SEGMENT_SORT_CAP nodes take the per-context sort, once each, into the same arrays: no item is refused for its size.  Items
- * with nothing to do are covered like the others.  The read-out changes no item's positions, RNG streams or counters. */
+ * with nothing to do are covered like the others.  The read-out changes no item's positions, RNG streams or counters.
+ * A batch of layouts is fed and read the same way (K4c / K6c): gfs_batch_upload_coords and gfs_batch_coords move every item's
+ * coordinates as one packed array, one launch and one copy each; gfs_batch_init_positions and gfs_batch_results stay the sorts'
+ * and refuse layouts.  Either kind reads every item's gfs_ctx_pair_errors in one call, gfs_batch_pair_errors (K7g). */
 #define GFS_SEGMENT_SORT_CAP 8192      /* nodes of the largest item sorted in LDS (96 KiB of a CU's 160) */
 typedef struct gfs_batch gfs_batch;
 typedef struct gfs_batch_config {
@@ -425,6 +428,24 @@ int  gfs_batch_init_positions(gfs_batch *b, void *hip_stream);
 int  gfs_batch_results(gfs_batch *b, double *positions, uint32_t *order, uint64_t total, double *kernel_ms, void *hip_stream);
 /* test hook: items of more than cap nodes take the per-item sort (0 restores GFS_SEGMENT_SORT_CAP; larger values are GFS_E_ARG) */
 int  gfs_batch_debug_sort_cap(gfs_batch *b, uint64_t cap);
+/* A batch of layouts (D = 2 or 3): every item's coordinates in one packed array, Layout.coords order (k*2 + end)*D + dim by dense index k,
+ * item i at offsets[i] * 2 * D (gfs_batch_result_offsets); total must be offsets[items] * 2 * D.  Up: one copy through the batch's pinned
+ * staging and one launch write every item's end x dimension planes by node slot, exactly what gfs_ctx_upload_positions writes; down: one
+ * launch and one copy give every item the bits of gfs_ctx_download_positions; *kernel_ms (nullable): HIP events around the launch.  Both
+ * synchronise.  GFS_E_ARG for a null pointer or a wrong total, GFS_E_UNSUPPORTED for a batch of 1D sorts (gfs_batch_init_positions and
+ * gfs_batch_results are theirs), GFS_E_STATE, naming the item, for a context no longer set up for the batch's dimensions; all checked
+ * before any device call.  Items with nothing to do are covered like the others; no RNG stream or counter is touched. */
+int  gfs_batch_upload_coords(gfs_batch *b, const double *coords, uint64_t total, void *hip_stream);
+int  gfs_batch_coords(gfs_batch *b, double *coords, uint64_t total, double *kernel_ms /*nullable*/, void *hip_stream);
+/* gfs_ctx_pair_errors of every item, for sorts and layouts alike: out[i * n_z + k] is item i at zs[k], field for field and bit for
+ * bit what the item's own call gives (a workgroup of the one step launch does the work of a workgroup of the item's own launch;
+ * an item's partial sums are added in the same order).  One step launch and one reduce launch over all items and distances,
+ * one copy back; scratch is the batch's.  Arguments as gfs_ctx_pair_errors (GFS_E_ARG for a null pointer with n_z > 0, a
+ * distance of 0, more than 65535 distances), GFS_E_STATE, naming the item, for a context without positions; checked before any
+ * device call.  *kernel_ms (nullable): HIP events around the two launches.  Runs on hip_stream and synchronises; writes nothing
+ * but out. */
+int  gfs_batch_pair_errors(gfs_batch *b, const uint64_t *zs, uint64_t n_z, gfs_pair_error *out /*[items][n_z]*/, double *kernel_ms /*nullable*/,
+                           void *hip_stream);
 
 /* ---- multi-device runs (no reference equivalent: the reference is one process, src/sgd.rs:413-593) ----
  * Paths are sharded over `world` ranks, one rank per GPU (one process per GPU, or one host thread per GPU); every rank
