@@ -288,7 +288,7 @@ inline int32_t crowd_kshift(uint64_t n_steps, uint64_t n_streams) {
 inline bool wide_index(uint64_t n_steps, uint32_t flags) { return n_steps > 0xFFFFFFFFull || (flags & GFS_F_DBG_WIDE_INDEX); }
 
 // "This context's plan is the pooled fused reference-stream kernel, with the schedule's constants resident, and it has work":
-// what a batch (capi.hip gfs_batch_create, gfs_batch_run) can take into its launch.
+// what a batch (capi_batch.hip gfs_batch_create, gfs_batch_run) can take into its launch.
 inline bool batch_eligible(const LaunchShape &s, bool trace, bool has_resident_schedule, bool idle) {
     return !idle && s.bundle == 1 && !s.phased && s.fused && s.pooled && !trace && has_resident_schedule;
 }

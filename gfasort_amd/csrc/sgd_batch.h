@@ -1,4 +1,4 @@
-// sgd_batch.h — the two tables a batch launch reads (sgd_kernels_batch.hip; written by capi.hip gfs_batch_run).
+// sgd_batch.h — the two tables a batch launch reads (sgd_kernels_batch.hip; written by capi_batch.hip gfs_batch_run).
 #pragma once
 #include "sgd_device.h"
 
