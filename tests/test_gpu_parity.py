@@ -310,22 +310,27 @@ def _mirror_partners(B, dims=0):
 
 
 
-@pytest.mark.parametrize("B", [4, 8, 16, 32, 64])
-def test_bundled_sampler_trace_matches_oracle_mirror(B):
+@pytest.mark.parametrize("B,wide", [pytest.param(b, False, id=str(b)) for b in (4, 8, 16, 32, 64)] + [pytest.param(64, True, id="64-wide")])
+def test_bundled_sampler_trace_matches_oracle_mirror(B, wide):
     """Implementation = specification: the bundled sampler's random-number consumption and emitted terms equal the
     oracle's MIRROR of it bit for bit (leader = reference stream, satellites = consecutive steps, long runs, two colours,
-    wave-level quota).  Not a statement about the reference."""
+    wave-level quota).  Not a statement about the reference.  wide: the u64 step sampler of graphs beyond 2^32 steps
+    (GFS_F_DBG_WIDE_INDEX, the oracle told to do the same) in the team kernel that such a graph runs."""
     g = load("DRB1-3123.gfa")
     p = _ygs(g, 6)
     T, K = 512, 48
     og, op = oracle_graph(g), oracle_params(p)
-    st_o = O.State(og, op, n_streams=T, trace_per_stream=K, bundle=B, node_slots=_node_slots(g), chain=_mirror_chain(B),
-                   partners=_mirror_partners(B))
-    x_ref = O.init_positions(og)
-    st_o.run(x_ref)
-    so = st_o.stats()
+    O.lib().gfo_set_force_wide_steps(1 if wide else 0)
+    try:
+        st_o = O.State(og, op, n_streams=T, trace_per_stream=K, bundle=B, node_slots=_node_slots(g), chain=_mirror_chain(B),
+                       partners=_mirror_partners(B))
+        x_ref = O.init_positions(og)
+        st_o.run(x_ref)
+        so = st_o.stats()
+    finally:
+        O.lib().gfo_set_force_wide_steps(0)
     ctx = hip.Context(g)
-    assert ctx.setup_1d(p, hip.make_config(n_streams=T, trace_per_stream=K, flags=hip.F_BUNDLE(B))) == 0
+    assert ctx.setup_1d(p, hip.make_config(n_streams=T, trace_per_stream=K, flags=hip.F_BUNDLE(B) | (hip.F_DBG_WIDE_INDEX if wide else 0))) == 0
     ctx.upload(hip.init_positions(g))
     ctx.run()
     tr, counts = ctx.trace()
@@ -429,8 +434,10 @@ def test_bundled_quality_matches_reference_streams_on_bubble_graph(B):
     assert ratio.max() <= (1.15 if B == 16 else 1.08), np.round(ratio, 3).tolist()
 
 
-@pytest.mark.parametrize("B,dims", [(8, 2), (64, 2), (16, 3)])
-def test_bundled_nd_sampler_trace_matches_oracle_mirror(B, dims):
+@pytest.mark.parametrize("B,dims,wide", [pytest.param(b, d, False, id=f"{b}-{d}") for b, d in ((8, 2), (64, 2), (16, 3))] +
+                         [pytest.param(64, 2, True, id="64-2-wide")])
+def test_bundled_nd_sampler_trace_matches_oracle_mirror(B, dims, wide):
+    """wide: as in test_bundled_sampler_trace_matches_oracle_mirror, for the layout team kernel."""
     g = load("DRB1-3123.gfa")
     p = P.LayoutSGDParams.from_graph(g, dims, 1)
     p.iter_max = 4
@@ -439,12 +446,16 @@ def test_bundled_nd_sampler_trace_matches_oracle_mirror(B, dims):
     og, op = oracle_graph(g), oracle_params(p)
     c0 = gaussian_init(g, dims, 11)
     c_ref = c0.copy()
-    st_o = O.State(og, op, dims=dims, n_streams=T, trace_per_stream=K, bundle=B, node_slots=_node_slots(g), chain=_mirror_chain(B, dims),
-                   partners=_mirror_partners(B, dims))
-    st_o.run(c_ref)
-    so = st_o.stats()
+    O.lib().gfo_set_force_wide_steps(1 if wide else 0)
+    try:
+        st_o = O.State(og, op, dims=dims, n_streams=T, trace_per_stream=K, bundle=B, node_slots=_node_slots(g), chain=_mirror_chain(B, dims),
+                       partners=_mirror_partners(B, dims))
+        st_o.run(c_ref)
+        so = st_o.stats()
+    finally:
+        O.lib().gfo_set_force_wide_steps(0)
     ctx = hip.Context(g)
-    assert ctx.setup_nd(p, hip.make_config(n_streams=T, trace_per_stream=K, flags=hip.F_BUNDLE(B))) == 0
+    assert ctx.setup_nd(p, hip.make_config(n_streams=T, trace_per_stream=K, flags=hip.F_BUNDLE(B) | (hip.F_DBG_WIDE_INDEX if wide else 0))) == 0
     ctx.upload(c0)
     ctx.run()
     tr, counts = ctx.trace()
