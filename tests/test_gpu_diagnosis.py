@@ -22,7 +22,7 @@ import pytest
 from util import G, P, DATA, load, graph_from_paths, self_loop_graph, absent_node_graph, reverse_short_paths_graph
 from gfasort_amd import build as B
 from gfasort_amd import hip, quality as Q
-from quality_restatement import np_pairs_at, np_pair_values, noisy_start
+from quality_restatement import expected, noisy_start, shuffled_start
 
 pytestmark = pytest.mark.gpu
 
@@ -77,15 +77,6 @@ def context(g, dims, positions=None, node_perm=None):
     return ctx
 
 
-def shuffled_start(g, dims, seed):
-    """The reference's start positions handed to the nodes in a seeded random order."""
-    perm = np.random.default_rng(seed).permutation(g.n_nodes)
-    start = noisy_start(g, dims, 0, scale=0.0)
-    if dims == 0:
-        return np.ascontiguousarray(start[perm])
-    return np.ascontiguousarray(start.reshape(g.n_nodes, 2 * dims)[perm].reshape(-1))
-
-
 def step_distances(g):
     longest = int(np.diff(g.path_first_step.astype(np.int64)).max())
     return [1, 2, 65, longest, g.n_steps + 5]
@@ -96,54 +87,11 @@ def position_kinds(g, dims):
     return [("noisy", noisy, 1.5), ("noisy", noisy, 10.0), ("shuffled", shuffled_start(g, dims, 23 + dims), 10.0)]
 
 
-_expected = {}
-
-
-def expected(name, dims, kind, coords, z, ratio):
-    """The restatement, grouped: dict(paths, nodes, list, counted) — computed once per case and shared."""
-    key = (name, dims, kind, z, ratio)
-    if key in _expected:
-        return _expected[key]
-    g = graph(name)
-    sa, sb = np_pairs_at(g, z)
-    err, rel, ok = np_pair_values(g, coords, dims, sa, sb)
-    sa, sb = sa[ok], sb[ok]
-    pos, _ = g.step_positions()
-    d_path = np.abs(pos[sa].astype(np.float64) - pos[sb].astype(np.float64))
-    d_layout = err + d_path
-    stretched = d_layout / d_path > ratio
-    first = g.path_first_step.astype(np.int64)
-    path_of = np.repeat(np.arange(g.n_paths), np.diff(first))
-    pa = path_of[sa]
-    paths = np.zeros(g.n_paths, dtype=hip.PATH_ERROR_DTYPE)
-    paths["steps"] = np.diff(first)
-    paths["reverse_steps"] = np.bincount(path_of[g.step_is_rev.astype(bool)], minlength=g.n_paths)
-    paths["pairs"] = np.bincount(pa, minlength=g.n_paths)
-    paths["stretched"] = np.bincount(pa[stretched], minlength=g.n_paths)
-    np.maximum.at(paths["max_rel_sq"], pa, rel)
-    for k, v in (("sum_rel_sq", rel), ("sum_abs", np.abs(err)), ("sum_sq", err * err)):
-        paths[k] = np.bincount(pa, weights=v, minlength=g.n_paths)
-    sn = g.step_node.astype(np.int64)
-    na, nb = sn[sa], sn[sb]
-    other = nb != na                                                    # a pair from a node to itself counts once
-    nodes = np.zeros(g.n_nodes, dtype=hip.NODE_ERROR_DTYPE)
-    nodes["pairs"] = np.bincount(na, minlength=g.n_nodes) + np.bincount(nb[other], minlength=g.n_nodes)
-    nodes["stretched"] = np.bincount(na[stretched], minlength=g.n_nodes) + np.bincount(nb[other & stretched], minlength=g.n_nodes)
-    np.maximum.at(nodes["max_rel_sq"], na, rel)
-    np.maximum.at(nodes["max_rel_sq"], nb, rel)
-    lst = np.zeros(int(stretched.sum()), dtype=hip.STRETCHED_PAIR_DTYPE)
-    lst["step_a"], lst["step_b"], lst["path"] = sa[stretched], sb[stretched], pa[stretched]
-    lst["d_path"], lst["d_layout"] = d_path[stretched], d_layout[stretched]
-    assert np.all(np.diff(lst["step_a"].astype(np.int64)) > 0)
-    _expected[key] = dict(paths=paths, nodes=nodes, list=lst, counted=int(sa.shape[0]))
-    return _expected[key]
-
-
 def cases(name, dims):
     g = graph(name)
     for kind, coords, ratio in position_kinds(g, dims):
         for z in step_distances(g):
-            yield kind, coords, ratio, z, expected(name, dims, kind, coords, z, ratio)
+            yield kind, coords, ratio, z, expected(g, name, dims, kind, coords, z, ratio)
 
 
 def by_kind(g, dims):
