@@ -85,22 +85,17 @@ int gfs_warmup(int device) {
 // ---------------------------------------------------------------------------------------------
 // resident context
 // ---------------------------------------------------------------------------------------------
-// the fixed allocations of a context are plain pointers (the kernels' arguments are made of them): freed and nulled here
-template <typename T> static void free_device(T *&p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
+// what a setup allocates, let go before the next one (the index of gfs_ctx_create and the read-outs' scratch stay)
 static void free_sgd_state(gfs_ctx *c) {
-    free_device(c->d_zetas);
-    if (c->x_owned) free_device(c->d_x);                                  // (a bound pointer is the caller's: gfs_ctx_bind_positions)
-    c->d_x = nullptr; c->x_owned = false;
-    free_device(c->d_rng);
-    free_device(c->d_lead);
-    free_device(c->d_counters);
-    free_device(c->d_trace);
-    free_device(c->d_trace_cnt);
+    c->d_zetas.reset();
+    c->d_x.reset();                                                       // (a bound pointer is the caller's: only dropped)
+    c->d_rng.reset();
+    c->d_lead.reset();
+    c->d_counters.reset();
+    c->d_trace.reset();
+    c->d_trace_cnt.reset();
     c->d_its.reset();
-    free_device(c->d_its_all);
+    c->d_its_all.reset();
     c->d_pool.reset();
     c->configured = false;
 }
@@ -139,7 +134,7 @@ static int upload_zeta_table(gfs_ctx *c, const gfs_sgd_params *p, const double *
         std::copy(part.begin(), part.begin() + std::min<size_t>(part.size(), ztab.size()), ztab.begin());
         zetas = ztab.data();
     }
-    HIPCHK(hipMalloc(&c->d_zetas, zlen_full * 8));
+    HIPCHK(c->d_zetas.grow(zlen_full * 8));
     HIPCHK(hipMemcpy(c->d_zetas, zetas, zlen_full * 8, hipMemcpyHostToDevice));
     return GFS_OK;
 }
@@ -233,9 +228,8 @@ static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs
     // update) still owns a full-length position replica: a multi-GPU rank whose shard holds no such path must be able to
     // upload, bind, merge and download like its peers — its contribution to every merge is a zero delta of the same size.
     c->x_len = dims ? c->n_nodes * 2 * (uint64_t)dims : c->n_nodes;
-    HIPCHK(hipMalloc(&c->d_x, c->x_len * 8));
+    HIPCHK(c->d_x.grow(c->x_len * 8));
     HIPCHK(hipMemset(c->d_x, 0, c->x_len * 8));
-    c->x_owned = true;
     if (!c->valid_paths) { c->configured = true; return GFS_NOTHING_TO_DO; }
 
     // launch shape (launch_policy.h): decided before anything of the run's state is allocated
@@ -253,22 +247,22 @@ static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs
     rc = upload_zeta_table(c, p, zetas);
     if (rc) return rc;
 
-    HIPCHK(hipMalloc(&c->d_rng, 4 * n_streams * 8));
+    HIPCHK(c->d_rng.grow(4 * n_streams * 8));
     if (c->shape.bundle > 1) {                                           // team kernels, sort and layout
-        HIPCHK(hipMalloc(&c->d_lead, 8 * n_streams * sizeof(uint32_t)));
+        HIPCHK(c->d_lead.grow(8 * n_streams * sizeof(uint32_t)));
         HIPCHK(hipMemset(c->d_lead, 0, 8 * n_streams * sizeof(uint32_t)));      // trips left = 0: no pass yet
     }
-    HIPCHK(hipMalloc(&c->d_counters, kCounterBytes));
+    HIPCHK(c->d_counters.grow(kCounterBytes));
     if (c->cfg.trace_per_stream) {
-        HIPCHK(hipMalloc(&c->d_trace, n_streams * c->cfg.trace_per_stream * sizeof(gfs_term)));
+        HIPCHK(c->d_trace.grow(n_streams * c->cfg.trace_per_stream * sizeof(gfs_term)));
         HIPCHK(hipMemset(c->d_trace, 0, n_streams * c->cfg.trace_per_stream * sizeof(gfs_term)));
-        HIPCHK(hipMalloc(&c->d_trace_cnt, n_streams * sizeof(uint32_t)));
+        HIPCHK(c->d_trace_cnt.grow(n_streams * sizeof(uint32_t)));
     }
     rc = seed_streams(c);
     if (rc) return rc;
     if ((c->shape.team || c->shape.bundle == 1) && c->params.iter_max < (1u << 20)) {
         // the whole schedule's per-iteration constants, for fused launches over consecutive iterations
-        HIPCHK(hipMalloc(&c->d_its_all, (c->params.iter_max + 1) * sizeof(gfs::IterConsts)));
+        HIPCHK(c->d_its_all.grow((c->params.iter_max + 1) * sizeof(gfs::IterConsts)));
         rc = upload_schedule(c);
         if (rc) return rc;
     }
@@ -359,31 +353,31 @@ int gfs_ctx_create_with_layout(const gfs_graph_view *g, int device, const uint32
         return e == hipSuccess;
     };
     const uint64_t S = g->n_steps, N = g->n_nodes, P = g->n_paths;
-    gfs::Buffer d_tmp, d_first, d_rev, d_step_node;                        // (scope frees them last to first)
+    gfs::Array<uint64_t> d_tmp, d_first; gfs::Array<uint8_t> d_rev; gfs::Array<uint32_t> d_step_node;   // (scope frees them last to first)
     // (one record of padding, zeroed: the layout team kernels read the record AFTER a step for its node's length and use it
     // only where that step is not its path's last — so the graph's very last step needs no clamp, sgd_kernels_nd_team.hip)
-    if (!ok("hipMalloc step_rec", hipMalloc(&c->d_step_rec, (S + 1) * sizeof(uint4)))) return rc;
+    if ((rc = c->d_step_rec.reserve((S + 1) * sizeof(uint4), "hipMalloc step_rec"))) return rc;
     if (!ok("hipMemset step_rec", hipMemset(c->d_step_rec + S, 0, sizeof(uint4)))) return rc;
-    if (!ok("hipMalloc path_rec", hipMalloc(&c->d_path_rec, prec.size() * sizeof(uint4)))) return rc;
-    if (!ok("hipMalloc path_len", hipMalloc(&c->d_path_len, std::max<uint64_t>(P, 1) * 8))) return rc;
-    if (!ok("hipMalloc perm", hipMalloc(&c->d_perm, std::max<uint64_t>(N, 1) * 4))) return rc;
-    if (!ok("hipMalloc node_len", hipMalloc(&c->d_node_len, std::max<uint64_t>(N, 1) * 4))) return rc;
+    if ((rc = c->d_path_rec.reserve(prec.size() * sizeof(uint4), "hipMalloc path_rec"))) return rc;
+    if ((rc = c->d_path_len.reserve(std::max<uint64_t>(P, 1) * 8, "hipMalloc path_len"))) return rc;
+    if ((rc = c->d_perm.reserve(std::max<uint64_t>(N, 1) * 4, "hipMalloc perm"))) return rc;
+    if ((rc = c->d_node_len.reserve(std::max<uint64_t>(N, 1) * 4, "hipMalloc node_len"))) return rc;
     if (N && !ok("hipMemcpy node_len", hipMemcpy(c->d_node_len, g->node_len, N * 4, hipMemcpyHostToDevice))) return rc;
     if (!ok("hipMemcpy path_rec", hipMemcpy(c->d_path_rec, prec.data(), prec.size() * sizeof(uint4), hipMemcpyHostToDevice))) return rc;
     if (S) {
         if ((rc = d_step_node.reserve(S * 4, "hipMalloc step_node"))) return rc;
-        if (!ok("hipMemcpy step_node", hipMemcpy(d_step_node.p, g->step_node, S * 4, hipMemcpyHostToDevice))) return rc;
+        if (!ok("hipMemcpy step_node", hipMemcpy(d_step_node, g->step_node, S * 4, hipMemcpyHostToDevice))) return rc;
         if ((rc = d_first.reserve((P + 1) * 8, "hipMalloc path_first"))) return rc;
-        if (!ok("hipMemcpy path_first", hipMemcpy(d_first.p, g->path_first_step, (P + 1) * 8, hipMemcpyHostToDevice))) return rc;
+        if (!ok("hipMemcpy path_first", hipMemcpy(d_first, g->path_first_step, (P + 1) * 8, hipMemcpyHostToDevice))) return rc;
     }
     laps.lap("step upload");
     {
         // range check of step_node, and (unless the caller brought a layout) the first-visit order
         int bad = 0;
-        gfs::Buffer d_scratch_perm;
+        gfs::Array<uint32_t> d_scratch_perm;
         if (node_perm && N && (rc = d_scratch_perm.reserve(N * 4, "hipMalloc scratch"))) return rc;
-        const hipError_t e = gfs::first_visit_layout_device(d_step_node.as<uint32_t>(), S, N, d_first.as<uint64_t>(), (uint32_t)P,
-                                                            node_perm && N ? d_scratch_perm.as<uint32_t>() : c->d_perm, &bad);
+        const hipError_t e = gfs::first_visit_layout_device(d_step_node, S, N, d_first, (uint32_t)P,
+                                                            node_perm && N ? d_scratch_perm : c->d_perm, &bad);
         d_scratch_perm.reset();
         if (!ok("first_visit_layout", e)) return rc;
         if (bad) return fail(GFS_E_ARG, "step_node out of range");
@@ -395,10 +389,9 @@ int gfs_ctx_create_with_layout(const gfs_graph_view *g, int device, const uint32
         if ((rc = d_rev.reserve(S, "hipMalloc step_is_rev"))) return rc;
         if ((rc = d_tmp.reserve((S + 1) * 8, "hipMalloc scan"))) return rc;
         laps.lap("alloc tmp");
-        if (!ok("hipMemcpy step_is_rev", hipMemcpy(d_rev.p, g->step_is_rev, S, hipMemcpyHostToDevice))) return rc;
+        if (!ok("hipMemcpy step_is_rev", hipMemcpy(d_rev, g->step_is_rev, S, hipMemcpyHostToDevice))) return rc;
         laps.lap("upload");
-        if (!ok("build_path_index", gfs::build_path_index_device(d_step_node.as<uint32_t>(), d_rev.as<uint8_t>(), c->d_node_len, c->d_perm,
-                                                                 d_first.as<uint64_t>(), (uint32_t)P, S, N, d_tmp.as<uint64_t>(),
+        if (!ok("build_path_index", gfs::build_path_index_device(d_step_node, d_rev, c->d_node_len, c->d_perm, d_first, (uint32_t)P, S, N, d_tmp,
                                                                  c->d_step_rec, c->d_path_len))) return rc;
     }
     laps.lap("K3");
@@ -411,14 +404,7 @@ int gfs_ctx_create_with_layout(const gfs_graph_view *g, int device, const uint32
 void gfs_ctx_destroy(gfs_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    free_sgd_state(c);
-    for (auto &ev : c->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-    free_device(c->d_step_rec);
-    free_device(c->d_path_rec);
-    free_device(c->d_path_len);
-    free_device(c->d_perm);
-    free_device(c->d_node_len);
-    delete c;                                                              // (d_quality goes here: the device is set)
+    delete c;                                                              // (its buffers and events go here: the device is set)
 }
 
 int gfs_ctx_setup_1d(gfs_ctx *c, const gfs_sgd_params *p, const gfs_launch_config *cfg,
@@ -481,8 +467,7 @@ int gfs_ctx_bind_positions(gfs_ctx *c, void *device_ptr) {
     if (!c || !device_ptr) return fail(GFS_E_ARG, "null argument");
     if (!c->configured || !c->x_len) return fail(GFS_E_STATE, "context not set up");
     HIPCHK(hipSetDevice(c->device));
-    if (c->d_x && c->x_owned) HIPCHK(hipFree(c->d_x));
-    c->d_x = (double *)device_ptr; c->x_owned = false;
+    HIPCHK(c->d_x.borrow(device_ptr));                                     // (frees the context's own vector)
     return GFS_OK;
 }
 int gfs_ctx_reset_streams(gfs_ctx *c) {
@@ -530,20 +515,19 @@ void gfs::fill_kargs(const gfs_ctx *c, gfs::KArgs &a) {
 
 extern "C" {
 
-static int next_event_pair(gfs_ctx *c, std::pair<hipEvent_t, hipEvent_t> *&ev) {
+static int next_event_pair(gfs_ctx *c, gfs::EventPair *&ev) {
     if (c->events_used == c->events.size()) {
         if (c->events.size() >= 4096) {
             // long-lived context: recycle the pool instead of growing it (one sync per 4096 launches)
-            HIPCHK(hipEventSynchronize(c->events.back().second));
+            HIPCHK(hipEventSynchronize(c->events.back().e1));
             for (auto &p : c->events) {
                 float t = 0.f;
-                if (hipEventElapsedTime(&t, p.first, p.second) == hipSuccess) c->kernel_ms_harvested += t;
+                if (p.elapsed(&t)) c->kernel_ms_harvested += t;
             }
             c->events_used = 0;
         } else {
-            hipEvent_t e0, e1;
-            HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-            c->events.emplace_back(e0, e1);
+            c->events.emplace_back();
+            if (int rc = c->events.back().ready()) { c->events.pop_back(); return rc; }
         }
     }
     ev = &c->events[c->events_used++];
@@ -562,13 +546,13 @@ int gfs_ctx_run_iteration(gfs_ctx *c, uint64_t k, void *hip_stream) {
     a.it = gfs::iter_consts(c, k);
     const bool window = gfs::in_window(c->shape, k);                                 // GFS_F_PHASED: the window's iterations are K1's
     if (window) a.bundle = 1;
-    std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
+    gfs::EventPair *ev = nullptr;
     int rc = next_event_pair(c, ev);
     if (rc) return rc;
-    HIPCHK(hipEventRecord(ev->first, st));
+    HIPCHK(ev->start(st));
     hipError_t e = launch(c, window ? c->plan.window_iteration : c->plan.iteration, a, nullptr, 0, nullptr, st);
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    HIPCHK(hipEventRecord(ev->second, st));
+    HIPCHK(ev->stop(st));
     c->iterations++;
     c->launches++;
     return GFS_OK;
@@ -635,13 +619,13 @@ int gfs_ctx_run_range(gfs_ctx *c, const uint64_t *ks, uint64_t n, void *hip_stre
         pool = c->d_pool.as<uint32_t>();
         HIPCHK(hipMemsetAsync(pool, 0, gfs::pool_bytes(n), st));
     }
-    std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
+    gfs::EventPair *ev = nullptr;
     int rc = next_event_pair(c, ev);
     if (rc) return rc;
-    HIPCHK(hipEventRecord(ev->first, st));                // (the event pair brackets the kernel alone)
+    HIPCHK(ev->start(st));                // (the event pair brackets the kernel alone)
     hipError_t e = launch(c, pl.fused, a, d_slice, (uint32_t)n, pool, st);
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("fused kernel launch: ") + hipGetErrorString(e));
-    HIPCHK(hipEventRecord(ev->second, st));
+    HIPCHK(ev->stop(st));
     c->iterations += n;
     c->launches++;
     return GFS_OK;
@@ -684,7 +668,7 @@ int gfs_ctx_stats(gfs_ctx *c, gfs_stats *out) {
     double ms = c->kernel_ms_harvested;
     for (size_t k = 0; k < c->events_used; ++k) {
         float t = 0.f;
-        if (hipEventElapsedTime(&t, c->events[k].first, c->events[k].second) == hipSuccess) ms += t;
+        if (c->events[k].elapsed(&t)) ms += t;
     }
     out->kernel_ms = ms; out->total_ms = c->total_ms; out->launches = c->launches;
     return GFS_OK;
@@ -795,24 +779,13 @@ gfs_pair_error gfs::unpack_pair_error(uint64_t z, const uint64_t *w) {
 
 extern "C" {
 
-// the duration of an entry's device work on stderr under GFS_TIMING (one HIP event pair, destroyed however the entry returns)
-struct QualityTimer {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipStream_t st;
-    explicit QualityTimer(hipStream_t s) : st(s) {
-        if (!std::getenv("GFS_TIMING")) return;
-        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, st) != hipSuccess) done();
-    }
-    void stop() { if (e0 && hipEventRecord(e1, st) != hipSuccess) done(); }
-    bool elapsed(float *ms) const { return e0 && hipEventElapsedTime(ms, e0, e1) == hipSuccess; }   // after the stream was synchronised
-    void report(const char *what, uint64_t z, uint64_t n_steps) const {
-        float ms = 0.f;
-        if (elapsed(&ms))
-            std::fprintf(stderr, "[%s] z = %llu, %llu steps: kernels %.4f ms\n", what, (unsigned long long)z, (unsigned long long)n_steps, ms);
-    }
-    void done() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); e0 = e1 = nullptr; }
-    ~QualityTimer() { done(); }
-};
+// the duration of an entry's device work on stderr under GFS_TIMING: only then does the entry's event pair come into being
+static void start_if_timing(gfs::EventPair &timer, hipStream_t st) { if (std::getenv("GFS_TIMING")) (void)timer.start(st); }
+static void report_timing(const gfs::EventPair &timer, const char *what, uint64_t z, uint64_t n_steps) {   // after the stream was synchronised
+    float ms = 0.f;
+    if (timer.elapsed(&ms))
+        std::fprintf(stderr, "[%s] z = %llu, %llu steps: kernels %.4f ms\n", what, (unsigned long long)z, (unsigned long long)n_steps, ms);
+}
 
 int gfs_ctx_pair_errors(gfs_ctx *c, const uint64_t *zs, uint64_t n_z, gfs_pair_error *out, void *hip_stream) {
     if (!c) return fail(GFS_E_ARG, "ctx is null");
@@ -828,11 +801,12 @@ int gfs_ctx_pair_errors(gfs_ctx *c, const uint64_t *zs, uint64_t n_z, gfs_pair_e
     if (rc) return rc;
     uint64_t *d_zs = c->d_quality.as<uint64_t>(), *d_out = d_zs + n_z, *d_partials = d_out + 5 * n_z;
     HIPCHK(hipMemcpyAsync(d_zs, zs, n_z * 8, hipMemcpyHostToDevice, st));
-    QualityTimer timer(st);
+    gfs::EventPair timer;
+    start_if_timing(timer, st);
     hipError_t e = gfs::pair_errors_device(c->d_step_rec, c->n_steps, c->d_x, c->n_nodes, (uint32_t)c->dims, d_zs, (uint32_t)n_z,
                                            d_partials, d_out, st);
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("pair_errors_device: ") + hipGetErrorString(e));
-    timer.stop();
+    (void)timer.stop(st);
     std::vector<uint64_t> w(5 * n_z);
     HIPCHK(hipMemcpyAsync(w.data(), d_out, w.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -922,14 +896,15 @@ int gfs_ctx_path_errors(gfs_ctx *c, uint64_t z, double ratio, gfs_path_error *ou
     rc = c->d_quality.reserve(8 * (8 * n_paths + 10 * tiles));             // [out | head partials | tail partials]
     if (rc) return rc;
     uint64_t *d_out = c->d_quality.as<uint64_t>(), *d_head = d_out + 8 * n_paths, *d_tail = d_head + 5 * tiles;
-    QualityTimer timer(st);
+    gfs::EventPair timer;
+    start_if_timing(timer, st);
     hipError_t e = gfs::path_errors_device(c->d_step_rec, c->n_steps, c->d_path_rec, n_paths, c->d_x, c->n_nodes, (uint32_t)c->dims, z, ratio,
                                            d_head, d_tail, d_out, st);
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("path_errors_device: ") + hipGetErrorString(e));
-    timer.stop();
+    (void)timer.stop(st);
     HIPCHK(hipMemcpyAsync(out, d_out, n_paths * sizeof(gfs_path_error), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    timer.report("gfs_ctx_path_errors", z, c->n_steps);
+    report_timing(timer, "gfs_ctx_path_errors", z, c->n_steps);
     return GFS_OK;
 }
 
@@ -947,15 +922,16 @@ int gfs_ctx_stretched_pairs(gfs_ctx *c, uint64_t z, double ratio, gfs_stretched_
     rc = c->d_quality.reserve(8 * (2 * (tiles + 1) + 5 * room));           // [tile counts | offsets | list]
     if (rc) return rc;
     uint64_t *d_counts = c->d_quality.as<uint64_t>(), *d_offsets = d_counts + tiles + 1, *d_list = d_offsets + tiles + 1;
-    QualityTimer timer(st);
+    gfs::EventPair timer;
+    start_if_timing(timer, st);
     hipError_t e = gfs::stretched_pairs_device(c->d_step_rec, c->n_steps, c->d_x, c->n_nodes, (uint32_t)c->dims, z, ratio, d_counts, d_offsets,
                                                room ? d_list : nullptr, room, total, st);
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("stretched_pairs_device: ") + hipGetErrorString(e));
-    timer.stop();
+    (void)timer.stop(st);
     const uint64_t n = std::min(room, *total);
     if (n) HIPCHK(hipMemcpyAsync(out, d_list, n * sizeof(gfs_stretched_pair), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    timer.report("gfs_ctx_stretched_pairs", z, c->n_steps);
+    report_timing(timer, "gfs_ctx_stretched_pairs", z, c->n_steps);
     return GFS_OK;
 }
 
@@ -972,13 +948,14 @@ int gfs_ctx_node_errors(gfs_ctx *c, uint64_t z, double ratio, gfs_node_error *ou
     rc = c->d_quality.reserve(8 * 6 * n_nodes);                            // [per slot: pairs | stretched | max] [out]
     if (rc) return rc;
     uint64_t *d_slots = c->d_quality.as<uint64_t>(), *d_out = d_slots + 3 * n_nodes;
-    QualityTimer timer(st);
+    gfs::EventPair timer;
+    start_if_timing(timer, st);
     hipError_t e = gfs::node_errors_device(c->d_step_rec, c->n_steps, c->d_x, c->d_perm, n_nodes, (uint32_t)c->dims, z, ratio, d_slots, d_out, st);
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("node_errors_device: ") + hipGetErrorString(e));
-    timer.stop();
+    (void)timer.stop(st);
     HIPCHK(hipMemcpyAsync(out, d_out, n_nodes * sizeof(gfs_node_error), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    timer.report("gfs_ctx_node_errors", z, c->n_steps);
+    report_timing(timer, "gfs_ctx_node_errors", z, c->n_steps);
     return GFS_OK;
 }
 
@@ -1039,10 +1016,8 @@ static int positions_only_ctx(const gfs_graph_view *g, uint64_t dims, const doub
     if (rc) return rc;
     c->dims = (int)dims;
     c->x_len = dims ? c->n_nodes * 2 * dims : c->n_nodes;
-    hipError_t e = hipMalloc(&c->d_x, c->x_len * 8);
-    if (e != hipSuccess) { gfs_ctx_destroy(c); return fail(GFS_E_HIP, std::string("hipMalloc positions: ") + hipGetErrorString(e)); }
-    c->x_owned = true;
-    rc = gfs_ctx_upload_positions(c, positions, c->x_len);
+    rc = c->d_x.reserve(c->x_len * 8, "hipMalloc positions");
+    if (!rc) rc = gfs_ctx_upload_positions(c, positions, c->x_len);
     if (rc) { gfs_ctx_destroy(c); return rc; }
     *out = c;
     return GFS_OK;

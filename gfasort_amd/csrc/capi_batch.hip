@@ -18,22 +18,7 @@ struct BatchLaunch {
     size_t lds_bytes = 0;              // the largest among its items
     uint64_t first = 0, count = 0;     // its items: run[first .. first + count)
     uint64_t blocks = 0, block_offset = 0;   // workgroups; where its part of the block table starts
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-};
-// The event pair of a batch's read-outs, created on first use: start and stop on the stream, *kernel_ms after the synchronise.
-struct GFS_LOCAL ReadoutTimer {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t start(hipStream_t st) {
-        hipError_t e = e0 ? hipSuccess : hipEventCreate(&e0);
-        if (e == hipSuccess && !e1) e = hipEventCreate(&e1);
-        return e == hipSuccess ? hipEventRecord(e0, st) : e;
-    }
-    hipError_t stop(hipStream_t st) { return hipEventRecord(e1, st); }
-    void read(double *kernel_ms) const {
-        float t = 0.f;
-        if (kernel_ms && hipEventElapsedTime(&t, e0, e1) == hipSuccess) *kernel_ms = t;
-    }
-    ~ReadoutTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    gfs::EventPair ev;                 // created with the batch
 };
 struct gfs_batch {
     int device = 0, dims = 0;
@@ -54,12 +39,16 @@ struct gfs_batch {
     std::vector<gfs::ReadoutItem> h_readout;
     gfs::Buffer d_readout, d_positions, d_order, d_sort_tmp;
     gfs::Buffer h_packed{true};        // pinned staging of every read-out: copies land here at full rate, whatever the caller's pages are
-    ReadoutTimer readout_timer;
+    gfs::EventPair readout_timer;      // created on first use: start and stop on the stream, read after the synchronise
     // K4c / K6c and K7g (batch_quality_kernels.hip): one device buffer each, [what the host sends | what the kernels write], grown on demand
     gfs::Buffer d_coords, d_quality;
 };
 static_assert(GFS_SEGMENT_SORT_CAP == gfs::SEGMENT_SORT_CAP, "the header's cap is the network's");
 
+static void read_kernel_ms(const gfs::EventPair &timer, double *kernel_ms) {
+    float t = 0.f;
+    if (kernel_ms && timer.elapsed(&t)) *kernel_ms = t;
+}
 static bool batch_item_idle(const gfs_ctx *c) { return !c->valid_paths || c->n_nodes == 0; }
 static bool batch_eligible(const gfs_ctx *c) {
     return gfs::batch_eligible(c->shape, c->cfg.trace_per_stream != 0, c->d_its_all != nullptr, batch_item_idle(c));
@@ -70,8 +59,7 @@ extern "C" {
 void gfs_batch_destroy(gfs_batch *b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
-    for (auto &l : b->launches) { if (l.e0) (void)hipEventDestroy(l.e0); if (l.e1) (void)hipEventDestroy(l.e1); }
-    delete b;                                                              // (its buffers and the read-out events go here: the device is set)
+    delete b;                                                              // (its buffers and events go here: the device is set)
 }
 
 int gfs_batch_create(gfs_ctx *const *ctxs, uint64_t n, const gfs_batch_config *cfg, gfs_batch **out) {
@@ -180,9 +168,8 @@ int gfs_batch_create(gfs_ctx *const *ctxs, uint64_t n, const gfs_batch_config *c
         if (!rc) rc = b->d_block_item.reserve(b->total_blocks * sizeof(uint32_t), "hipMalloc block table");
         if (!rc) rc = b->d_pool.reserve(b->pool_words * sizeof(uint32_t), "hipMalloc pools");
         if (rc) { gfs_batch_destroy(b); return rc; }
-        for (auto &l : b->launches) {
-            if ((e = hipEventCreate(&l.e0)) != hipSuccess || (e = hipEventCreate(&l.e1)) != hipSuccess) return bail("hipEventCreate", e);
-        }
+        for (auto &l : b->launches)
+            if ((rc = l.ev.ready())) { gfs_batch_destroy(b); return rc; }
     }
     *out = b;
     return GFS_OK;
@@ -231,15 +218,15 @@ int gfs_batch_run(gfs_batch *b, void *hip_stream) {
         const gfs::BatchItem *items = b->d_items.as<gfs::BatchItem>();
         const uint32_t *block_item = b->d_block_item.as<uint32_t>() + l.block_offset;
         void *args[] = {&items, &block_item};
-        HIPCHK(hipEventRecord(l.e0, st));                  // (the event pair brackets the kernel alone)
+        HIPCHK(l.ev.start(st));                          // (the event pair brackets the kernel alone)
         hipError_t e = hipLaunchKernel(gfs::batch_fused_kernel(b->dims, l.lds_tables), dim3((unsigned)l.blocks), dim3(b->block), args, l.lds_bytes, st);
         if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch kernel launch: ") + hipGetErrorString(e));
-        HIPCHK(hipEventRecord(l.e1, st));
+        HIPCHK(l.ev.stop(st));
     }
     HIPCHK(hipStreamSynchronize(st));
     for (BatchLaunch &l : b->launches) {
         float t = 0.f;
-        if (hipEventElapsedTime(&t, l.e0, l.e1) == hipSuccess) b->kernel_ms += t;
+        if (l.ev.elapsed(&t)) b->kernel_ms += t;
         b->launches_done++; b->blocks_done += l.blocks;
     }
     for (uint64_t r : b->run) {                            // each context as if it had been run alone (its kernel_ms apart)
@@ -402,7 +389,7 @@ int gfs_batch_results(gfs_batch *b, double *positions, uint32_t *order, uint64_t
     HIPCHK(hipStreamSynchronize(st));
     if (positions && total) std::memcpy(positions, h_positions, total * sizeof(double));
     if (order && total) std::memcpy(order, h_order, total * sizeof(uint32_t));
-    b->readout_timer.read(kernel_ms);
+    read_kernel_ms(b->readout_timer, kernel_ms);
     return GFS_OK;
 }
 
@@ -461,7 +448,7 @@ static int batch_coords_move(gfs_batch *b, double *coords, uint64_t total, int t
     if (!to_device) HIPCHK(hipMemcpyAsync(h, d, total * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (!to_device) std::memcpy(coords, h, total * sizeof(double));
-    b->readout_timer.read(kernel_ms);
+    read_kernel_ms(b->readout_timer, kernel_ms);
     return GFS_OK;
 }
 
@@ -520,7 +507,7 @@ int gfs_batch_pair_errors(gfs_batch *b, const uint64_t *zs, uint64_t n_z, gfs_pa
     HIPCHK(hipStreamSynchronize(st));
     const uint64_t *w = reinterpret_cast<const uint64_t *>(h + out_at);
     for (uint64_t r = 0; r < n * n_z; ++r) out[r] = gfs::unpack_pair_error(zs[r % n_z], &w[5 * r]);
-    b->readout_timer.read(kernel_ms);
+    read_kernel_ms(b->readout_timer, kernel_ms);
     return GFS_OK;
 }
 

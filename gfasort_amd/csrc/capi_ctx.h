@@ -1,53 +1,17 @@
 // capi_ctx.h — what the two units of the C ABI share and nobody else includes: the resident context (capi.hip) as the batch
-// entries (capi_batch.hip) read it, error reporting, the owning buffer type of both, and the few functions of capi.hip that a
-// batch calls.  Nothing here is exported from the shared object.
+// entries (capi_batch.hip) read it, error reporting, and the few functions of capi.hip that a batch calls (the owners of its
+// memory and events: device_memory.h).  Nothing here is exported from the shared object.
 #pragma once
 #include "../../include/gfasort_hip.h"
+#include "device_memory.h"
 #include "sgd_kernel_common.h"
 #include "launch_policy.h"
 #include "sgd_host.h"
 
 #include <string>
-#include <utility>
 #include <vector>
 
-#define GFS_LOCAL __attribute__((visibility("hidden")))       // not exported from the shared object
-
 static inline int fail(int code, const std::string &msg) { return gfs_set_error(code, msg); }   // (the error slot: host_tables.hip)
-#define HIPCHK(expr)                                                                           \
-    do {                                                                                       \
-        hipError_t _e = (expr);                                                                \
-        if (_e != hipSuccess)                                                                  \
-            return fail(GFS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));         \
-    } while (0)
-
-namespace gfs {
-// One allocation, device memory or (pinned) page-locked host memory, freed when its owner goes.  The caller has set the device.
-struct GFS_LOCAL Buffer {
-    void *p = nullptr;
-    uint64_t bytes = 0;
-    bool pinned = false;
-    explicit Buffer(bool pinned_ = false) : pinned(pinned_) {}
-    Buffer(Buffer &&o) noexcept : p(o.p), bytes(o.bytes), pinned(o.pinned) { o.p = nullptr; o.bytes = 0; }   // (move-only)
-    ~Buffer() { reset(); }
-    template <typename T> T *as() const { return static_cast<T *>(p); }
-    hipError_t release() {
-        const hipError_t e = !p ? hipSuccess : pinned ? hipHostFree(p) : hipFree(p);
-        p = nullptr; bytes = 0;
-        return e;
-    }
-    void reset() { (void)release(); }
-    // At least `need` bytes.  Only grows, and what the buffer held is lost: it frees (a synchronisation point) before it allocates.
-    int reserve(uint64_t need, const char *what = nullptr) {
-        if (bytes >= need) return GFS_OK;
-        hipError_t e = release();
-        if (e == hipSuccess) e = pinned ? hipHostMalloc(&p, need, hipHostMallocDefault) : hipMalloc(&p, need);
-        if (e != hipSuccess) { p = nullptr; return fail(GFS_E_HIP, std::string(what ? what : pinned ? "hipHostMalloc" : "hipMalloc") + ": " + hipGetErrorString(e)); }
-        bytes = need;
-        return GFS_OK;
-    }
-};
-}  // namespace gfs
 
 static constexpr size_t kCounterBytes = gfs::COUNTER_SLOTS * 8 * sizeof(unsigned long long);   // lines of 64 B
 
@@ -68,32 +32,32 @@ struct gfs_ctx {
     std::vector<uint32_t> path_counts;
     std::vector<uint32_t> perm;        // dense node index (ABI order) -> internal index (device layout of positions)
     // device mirror of PathIndex
-    uint4 *d_step_rec = nullptr;
-    uint4 *d_path_rec = nullptr;
-    uint64_t *d_path_len = nullptr;
-    uint32_t *d_perm = nullptr;         // node layout on the device (dense index -> slot)
-    uint32_t *d_node_len = nullptr;     // node lengths by dense index (K4: initial positions)
+    gfs::Array<uint4> d_step_rec;
+    gfs::Array<uint4> d_path_rec;
+    gfs::Array<uint64_t> d_path_len;
+    gfs::Array<uint32_t> d_perm;        // node layout on the device (dense index -> slot)
+    gfs::Array<uint32_t> d_node_len;    // node lengths by dense index (K4: initial positions)
     // SGD state
     int dims = 0;                      // 0 = 1D
     bool configured = false;
     gfs_sgd_params params{};
     gfs_launch_config cfg{};
     std::vector<double> etas;
-    double *d_zetas = nullptr;
-    double *d_x = nullptr; bool x_owned = false; uint64_t x_len = 0;
-    uint64_t *d_rng = nullptr;
-    uint32_t *d_lead = nullptr;      // team kernels: the waves' partly expanded passes, [8][n_streams]
-    unsigned long long *d_counters = nullptr;
-    gfs_term *d_trace = nullptr; uint32_t *d_trace_cnt = nullptr;
+    gfs::Array<double> d_zetas;
+    gfs::Array<double> d_x; uint64_t x_len = 0;               // (borrowed once a caller has bound its own: gfs_ctx_bind_positions)
+    gfs::Array<uint64_t> d_rng;
+    gfs::Array<uint32_t> d_lead;     // team kernels: the waves' partly expanded passes, [8][n_streams]
+    gfs::Array<unsigned long long> d_counters;
+    gfs::Array<gfs_term> d_trace; gfs::Array<uint32_t> d_trace_cnt;
     gfs::Buffer d_its;                                        // schedule slice of a fused launch (arbitrary lists), grown on demand
-    gfs::IterConsts *d_its_all = nullptr;                     // constants of iterations 0..=iter_max, resident
+    gfs::Array<gfs::IterConsts> d_its_all;                    // constants of iterations 0..=iter_max, resident
     gfs::Buffer d_pool;                // fused launch: per-iteration work pool counters (sgd_kernels_1d.hip), grown on demand
     gfs::LaunchShape shape;            // streams, bundle, run length, phase window, LDS tables, what a range launches (launch_policy.h)
     LaunchPlan plan;
     int32_t kshift_override = -1;      // test hook gfs_ctx_debug_kshift: >= 0 replaces the crowding onset of fill_kargs
     gfs::Buffer d_quality;             // K7 read-outs: scratch of 8-byte words, grown on demand and kept between calls and setups
     // timing
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    std::vector<gfs::EventPair> events;
     size_t events_used = 0;
     double kernel_ms_harvested = 0.0;  // durations of event pairs already recycled
     uint64_t iterations = 0;

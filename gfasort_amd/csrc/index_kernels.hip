@@ -5,6 +5,7 @@
 //       of node lengths over the steps, written straight into the 16-byte step records
 //   K6  path_sgd_sort's sort (src/sgd.rs:665-671): positions -> rank order
 #include "sgd_host.h"
+#include "device_memory.h"
 #include "sort_key.h"
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -89,13 +90,13 @@ hipError_t build_path_index_device(const uint32_t *d_step_node, const uint8_t *d
     hipError_t e = rocprim::exclusive_scan(nullptr, tmp_bytes, lens, d_scan, (uint64_t)0, (size_t)(n_steps + 1),
                                            rocprim::plus<uint64_t>(), 0);
     if (e != hipSuccess) return e;
-    void *d_scan_tmp = nullptr;
-    if ((e = hipMalloc(&d_scan_tmp, tmp_bytes ? tmp_bytes : 8)) != hipSuccess) return e;
-    e = rocprim::exclusive_scan(d_scan_tmp, tmp_bytes, lens, d_scan, (uint64_t)0, (size_t)(n_steps + 1),
+    Array<uint32_t> d_rep, d_cnt;                                         // (freed after the synchronise, last to first)
+    Buffer d_scan_tmp;
+    if ((e = d_scan_tmp.grow(tmp_bytes ? tmp_bytes : 8)) != hipSuccess) return e;
+    e = rocprim::exclusive_scan(d_scan_tmp.p, tmp_bytes, lens, d_scan, (uint64_t)0, (size_t)(n_steps + 1),
                                 rocprim::plus<uint64_t>(), 0);
-    uint32_t *d_cnt = nullptr, *d_rep = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&d_cnt, (n_nodes ? n_nodes : 1) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&d_rep, (n_nodes ? n_nodes : 1) * sizeof(uint32_t));
+    if (e == hipSuccess) e = d_cnt.grow((n_nodes ? n_nodes : 1) * sizeof(uint32_t));
+    if (e == hipSuccess) e = d_rep.grow((n_nodes ? n_nodes : 1) * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(d_cnt, 0, (n_nodes ? n_nodes : 1) * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(d_rep, 0, (n_nodes ? n_nodes : 1) * sizeof(uint32_t));
     if (e == hipSuccess) {
@@ -105,8 +106,7 @@ hipError_t build_path_index_device(const uint32_t *d_step_node, const uint8_t *d
         hipLaunchKernelGGL(path_len_kernel, dim3((n_paths + 255) / 256), dim3(256), 0, 0, d_scan, d_path_first, d_path_len, n_paths);
         e = hipGetLastError();
     }
-    hipError_t e2 = hipDeviceSynchronize();
-    (void)hipFree(d_scan_tmp); (void)hipFree(d_cnt); (void)hipFree(d_rep);
+    const hipError_t e2 = hipDeviceSynchronize();
     return e != hipSuccess ? e : e2;
 }
 
@@ -203,37 +203,36 @@ hipError_t first_visit_layout_device(const uint32_t *d_step_node, uint64_t n_ste
                                      uint32_t n_paths, uint32_t *d_perm, int *bad_out) {
     *bad_out = 0;
     if (n_nodes == 0) return hipSuccess;
-    unsigned long long *d_first = nullptr, *d_first_sorted = nullptr;
-    uint32_t *d_ids = nullptr, *d_ids_sorted = nullptr, *d_a = nullptr, *d_b = nullptr;
-    int *d_bad = nullptr;
-    void *d_tmp = nullptr;
+    // the owners (scope frees them last to first, after the synchronise that ends the pass); the pointers below swap roles
+    Buffer d_tmp;
+    Array<int> bad;
+    Array<uint32_t> b, a, ids_sorted, ids;
+    Array<unsigned long long> first_sorted, first;
     hipError_t e = hipSuccess;
-    auto done = [&](hipError_t err) {
-        (void)hipFree(d_first); (void)hipFree(d_first_sorted); (void)hipFree(d_ids); (void)hipFree(d_ids_sorted);
-        (void)hipFree(d_a); (void)hipFree(d_b); (void)hipFree(d_bad); (void)hipFree(d_tmp);
-        return err;
-    };
-    if ((e = hipMalloc(&d_first, n_nodes * 8)) != hipSuccess) return done(e);
-    if ((e = hipMalloc(&d_first_sorted, n_nodes * 8)) != hipSuccess) return done(e);
-    if ((e = hipMalloc(&d_ids, n_nodes * 4)) != hipSuccess) return done(e);
-    if ((e = hipMalloc(&d_ids_sorted, n_nodes * 4)) != hipSuccess) return done(e);
-    if ((e = hipMalloc(&d_a, n_nodes * 4)) != hipSuccess) return done(e);
-    if ((e = hipMalloc(&d_b, n_nodes * 4)) != hipSuccess) return done(e);
-    if ((e = hipMalloc(&d_bad, 2 * sizeof(int))) != hipSuccess) return done(e);
-    if ((e = hipMemset(d_first, 0xFF, n_nodes * 8)) != hipSuccess) return done(e);
-    if ((e = hipMemset(d_bad, 0, 2 * sizeof(int))) != hipSuccess) return done(e);
+    if ((e = first.grow(n_nodes * 8)) != hipSuccess) return e;
+    if ((e = first_sorted.grow(n_nodes * 8)) != hipSuccess) return e;
+    if ((e = ids.grow(n_nodes * 4)) != hipSuccess) return e;
+    if ((e = ids_sorted.grow(n_nodes * 4)) != hipSuccess) return e;
+    if ((e = a.grow(n_nodes * 4)) != hipSuccess) return e;
+    if ((e = b.grow(n_nodes * 4)) != hipSuccess) return e;
+    if ((e = bad.grow(2 * sizeof(int))) != hipSuccess) return e;
+    unsigned long long *d_first = first, *d_first_sorted = first_sorted;
+    uint32_t *d_ids = ids, *d_ids_sorted = ids_sorted, *d_a = a, *d_b = b;
+    int *d_bad = bad;
+    if ((e = hipMemset(d_first, 0xFF, n_nodes * 8)) != hipSuccess) return e;
+    if ((e = hipMemset(d_bad, 0, 2 * sizeof(int))) != hipSuccess) return e;
     if (n_steps) hipLaunchKernelGGL(first_visit_kernel, dim3(4096), dim3(256), 0, 0, d_step_node, n_steps, n_nodes, d_first, d_bad);
-    if ((e = hipMemcpy(bad_out, d_bad, sizeof(int), hipMemcpyDeviceToHost)) != hipSuccess) return done(e);
-    if (*bad_out) return done(hipSuccess);                                 // (the kernels below index by step_node)
+    if ((e = hipMemcpy(bad_out, d_bad, sizeof(int), hipMemcpyDeviceToHost)) != hipSuccess) return e;
+    if (*bad_out) return hipSuccess;                                       // (the kernels below index by step_node)
     hipLaunchKernelGGL(iota_kernel, dim3(1024), dim3(256), 0, 0, d_ids, n_nodes);
     size_t tmp_bytes = 0;
     e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, (uint64_t *)d_first, (uint64_t *)d_first_sorted, d_ids, d_ids_sorted,
                                   (size_t)n_nodes, 0, 64, 0);
-    if (e != hipSuccess) return done(e);
-    if ((e = hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 8)) != hipSuccess) return done(e);
-    e = rocprim::radix_sort_pairs(d_tmp, tmp_bytes, (uint64_t *)d_first, (uint64_t *)d_first_sorted, d_ids, d_ids_sorted,
+    if (e != hipSuccess) return e;
+    if ((e = d_tmp.grow(tmp_bytes ? tmp_bytes : 8)) != hipSuccess) return e;
+    e = rocprim::radix_sort_pairs(d_tmp.p, tmp_bytes, (uint64_t *)d_first, (uint64_t *)d_first_sorted, d_ids, d_ids_sorted,
                                   (size_t)n_nodes, 0, 64, 0);                 // stable: unvisited nodes stay in index order
-    if (e != hipSuccess) return done(e);
+    if (e != hipSuccess) return e;
     if (n_steps && d_path_first) {
         // branches: run heads by pointer jumping along the runs, anchors, roots by pointer jumping along the anchors
         int *d_changed = d_bad + 1;
@@ -250,20 +249,20 @@ hipError_t first_visit_layout_device(const uint32_t *d_step_node, uint64_t n_ste
             return hipSuccess;
         };
         hipLaunchKernelGGL(run_up_kernel, dim3(2048), dim3(256), 0, 0, d_step_node, d_first, d_path_first, n_paths, n_nodes, d_a);
-        if ((e = jump_to_fixpoint(d_a, d_b)) != hipSuccess) return done(e);                          // d_a = run head of every node
+        if ((e = jump_to_fixpoint(d_a, d_b)) != hipSuccess) return e;                                // d_a = run head of every node
         hipLaunchKernelGGL(anchor_kernel, dim3(2048), dim3(256), 0, 0, d_step_node, d_first, d_path_first, n_paths, d_a, n_nodes, d_b);
         std::swap(d_a, d_b);
-        if ((e = jump_to_fixpoint(d_a, d_b)) != hipSuccess) return done(e);                          // d_a = root of every node
+        if ((e = jump_to_fixpoint(d_a, d_b)) != hipSuccess) return e;                                // d_a = root of every node
         hipLaunchKernelGGL(branch_key_kernel, dim3(2048), dim3(256), 0, 0, d_first, d_a, d_ids_sorted, n_nodes, d_first_sorted);
         // stable sort by key of the ids already in first-visit order: (key, first visit)
-        e = rocprim::radix_sort_pairs(d_tmp, tmp_bytes, (uint64_t *)d_first_sorted, (uint64_t *)d_first, d_ids_sorted, d_ids,
+        e = rocprim::radix_sort_pairs(d_tmp.p, tmp_bytes, (uint64_t *)d_first_sorted, (uint64_t *)d_first, d_ids_sorted, d_ids,
                                       (size_t)n_nodes, 0, 64, 0);
-        if (e != hipSuccess) return done(e);
+        if (e != hipSuccess) return e;
         std::swap(d_ids, d_ids_sorted);
     }
     hipLaunchKernelGGL(scatter_rank_kernel, dim3(1024), dim3(256), 0, 0, d_ids_sorted, d_perm, n_nodes);
-    if ((e = hipGetLastError()) != hipSuccess) return done(e);
-    return done(hipDeviceSynchronize());
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    return hipDeviceSynchronize();
 }
 
 // ---- ABI order <-> device order of positions / coordinates ------------------------------------------------
@@ -298,21 +297,22 @@ __global__ void scatter_prefix_kernel(const uint64_t *prefix, const uint32_t *pe
 // x[perm[k]] = sum of node_len[0..k).  Synchronous.
 hipError_t init_positions_device(const uint32_t *d_node_len, const uint32_t *d_perm, double *d_x, uint64_t n) {
     if (n == 0) return hipSuccess;
-    uint64_t *d_len = nullptr, *d_scan = nullptr; void *d_tmp = nullptr;
+    Buffer tmp;                                                            // (scope frees them last to first, after the synchronise)
+    Array<uint64_t> scan, len;
     hipError_t e;
-    auto done = [&](hipError_t err) { (void)hipFree(d_len); (void)hipFree(d_scan); (void)hipFree(d_tmp); return err; };
-    if ((e = hipMalloc(&d_len, n * 8)) != hipSuccess) return done(e);
-    if ((e = hipMalloc(&d_scan, n * 8)) != hipSuccess) return done(e);
+    if ((e = len.grow(n * 8)) != hipSuccess) return e;
+    if ((e = scan.grow(n * 8)) != hipSuccess) return e;
+    uint64_t *d_len = len, *d_scan = scan;
     hipLaunchKernelGGL(widen_len_kernel, dim3(1024), dim3(256), 0, 0, d_node_len, d_len, n);
     size_t tmp_bytes = 0;
     e = rocprim::exclusive_scan(nullptr, tmp_bytes, d_len, d_scan, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), 0);
-    if (e != hipSuccess) return done(e);
-    if ((e = hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 8)) != hipSuccess) return done(e);
-    e = rocprim::exclusive_scan(d_tmp, tmp_bytes, d_len, d_scan, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), 0);
-    if (e != hipSuccess) return done(e);
+    if (e != hipSuccess) return e;
+    if ((e = tmp.grow(tmp_bytes ? tmp_bytes : 8)) != hipSuccess) return e;
+    e = rocprim::exclusive_scan(tmp.p, tmp_bytes, d_len, d_scan, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), 0);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(scatter_prefix_kernel, dim3(1024), dim3(256), 0, 0, d_scan, d_perm, d_x, n);
-    if ((e = hipGetLastError()) != hipSuccess) return done(e);
-    return done(hipDeviceSynchronize());
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    return hipDeviceSynchronize();
 }
 
 // ---- K6 (the key of a position: sort_key.h orderable) --------------------------------------------
@@ -335,11 +335,10 @@ hipError_t sort_order_device(const double *d_x_layout, const uint32_t *d_perm, u
     size_t tmp_bytes = 0;
     hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, v_in, v_out, (size_t)n, 0, 64, 0);
     if (e != hipSuccess) return e;
-    void *d_sort_tmp = nullptr;
-    if ((e = hipMalloc(&d_sort_tmp, tmp_bytes ? tmp_bytes : 8)) != hipSuccess) return e;
-    e = rocprim::radix_sort_pairs(d_sort_tmp, tmp_bytes, k_in, k_out, v_in, v_out, (size_t)n, 0, 64, 0);   // stable
-    hipError_t e2 = hipDeviceSynchronize();
-    (void)hipFree(d_sort_tmp);
+    Buffer d_sort_tmp;                                                     // (freed after the synchronise)
+    if ((e = d_sort_tmp.grow(tmp_bytes ? tmp_bytes : 8)) != hipSuccess) return e;
+    e = rocprim::radix_sort_pairs(d_sort_tmp.p, tmp_bytes, k_in, k_out, v_in, v_out, (size_t)n, 0, 64, 0);   // stable
+    const hipError_t e2 = hipDeviceSynchronize();
     *d_order_out = v_out;
     return e != hipSuccess ? e : e2;
 }

@@ -19,6 +19,7 @@
 // device and is what the CPU tests and the Python driver for test engines use too.
 #include "../../include/gfasort_hip.h"
 #include "sgd_host.h"
+#include "device_memory.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -28,13 +29,6 @@
 #include <numeric>
 #include <string>
 #include <vector>
-
-#define MHIPCHK(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t _e = (expr);                                                                \
-        if (_e != hipSuccess)                                                                  \
-            return gfs_set_error(GFS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
 
 namespace gfs {
 
@@ -309,11 +303,11 @@ struct gfs_rank {
     uint64_t shared_slots = 0;           // slots more than one rank can move
     uint64_t total = 0;                  // exchanged elements (shared slots x planes x dims), 0 when world == 1
     std::vector<gfs::ESeg> esegs, owned;
-    gfs::ESeg *d_esegs = nullptr, *d_owned = nullptr;
-    double *d_xprev = nullptr;
-    void *d_buf = nullptr; bool buf_owned = false;
-    double *d_full = nullptr;            // finish: full-length scratch when the caller binds none
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    gfs::Array<gfs::ESeg> d_esegs, d_owned;
+    gfs::Array<double> d_xprev;
+    gfs::Buffer d_buf;                   // the rank's own, or the caller's (borrowed: gfs_rank_bind_exchange_buffer)
+    gfs::Array<double> d_full;           // finish: full-length scratch when the caller binds none
+    gfs::EventPair ev_prepare, ev_apply; // the last window's two merge kernels
     double merge_ms = 0.0; uint64_t windows = 0; bool ev_pending = false;
     std::vector<double> etas;            // the schedule (merge rule 0)
     double eta_sum = 1.0;                // learning rate below which a window's moves are small enough to be summed (merge rule 0)
@@ -328,13 +322,7 @@ void gfs_rank_destroy(gfs_rank *r) {
     if (!r) return;
     (void)hipSetDevice(r->cfg.device);
     if (r->ctx) gfs_ctx_destroy(r->ctx);
-    if (r->d_esegs) (void)hipFree(r->d_esegs);
-    if (r->d_owned) (void)hipFree(r->d_owned);
-    if (r->d_xprev) (void)hipFree(r->d_xprev);
-    if (r->d_buf && r->buf_owned) (void)hipFree(r->d_buf);
-    if (r->d_full) (void)hipFree(r->d_full);
-    for (auto &e : r->ev) if (e) (void)hipEventDestroy(e);
-    delete r;
+    delete r;                                                              // (its buffers and events go here: the device is set)
 }
 
 int gfs_rank_create(const gfs_graph_view *g, const gfs_sgd_params *p, uint64_t dims, const gfs_rank_config *cfg, gfs_rank **out) {
@@ -423,18 +411,18 @@ int gfs_rank_create(const gfs_graph_view *g, const gfs_sgd_params *p, uint64_t d
             for (uint32_t k = 0; k < n_own; ++k)
                 if (own_rank[k] == cfg->rank) r->owned.push_back({ pl * N + own_lo[k], pl * N + own_hi[k], 0 });
         if (hipSetDevice(cfg->device) != hipSuccess) return bail(gfs_set_error(GFS_E_HIP, "hipSetDevice failed"));
-        auto up = [&](const std::vector<gfs::ESeg> &v, gfs::ESeg **d) -> int {
+        auto up = [&](const std::vector<gfs::ESeg> &v, gfs::Array<gfs::ESeg> &d) -> int {
             if (v.empty()) return GFS_OK;
-            MHIPCHK(hipMalloc(d, v.size() * sizeof(gfs::ESeg)));
-            MHIPCHK(hipMemcpy(*d, v.data(), v.size() * sizeof(gfs::ESeg), hipMemcpyHostToDevice));
+            if (int rc2 = d.reserve(v.size() * sizeof(gfs::ESeg), "hipMalloc exchange segments")) return rc2;
+            HIPCHK(hipMemcpy(d, v.data(), v.size() * sizeof(gfs::ESeg), hipMemcpyHostToDevice));
             return GFS_OK;
         };
-        if ((rc = up(r->esegs, &r->d_esegs)) || (rc = up(r->owned, &r->d_owned))) return bail(rc);
+        if ((rc = up(r->esegs, r->d_esegs)) || (rc = up(r->owned, r->d_owned))) return bail(rc);
         if (r->total) {
-            if (hipMalloc(&r->d_xprev, r->total * 8) != hipSuccess) return bail(gfs_set_error(GFS_E_NOMEM, "hipMalloc x_prev"));
+            if (r->d_xprev.grow(r->total * 8) != hipSuccess) return bail(gfs_set_error(GFS_E_NOMEM, "hipMalloc x_prev"));
             if (hipMemset(r->d_xprev, 0, r->total * 8) != hipSuccess) return bail(gfs_set_error(GFS_E_HIP, "hipMemset x_prev"));
         }
-        for (auto &e : r->ev) if (hipEventCreate(&e) != hipSuccess) return bail(gfs_set_error(GFS_E_HIP, "hipEventCreate"));
+        if ((rc = r->ev_prepare.ready()) || (rc = r->ev_apply.ready())) return bail(rc);
     }
     *out = r;
     return r->idle && !multi ? GFS_NOTHING_TO_DO : GFS_OK;
@@ -457,8 +445,8 @@ int gfs_rank_get_info(const gfs_rank *r, gfs_rank_info *out) {
     if (r->ev_pending) {
         // the last window's merge kernels (events recorded on the caller's stream)
         float a = 0.f, b = 0.f;
-        if (hipEventSynchronize(r->ev[3]) == hipSuccess && hipEventElapsedTime(&a, r->ev[0], r->ev[1]) == hipSuccess &&
-            hipEventElapsedTime(&b, r->ev[2], r->ev[3]) == hipSuccess) out->last_merge_kernels_ms = a + b;
+        if (hipEventSynchronize(r->ev_apply.e1) == hipSuccess && r->ev_prepare.elapsed(&a) && r->ev_apply.elapsed(&b))
+            out->last_merge_kernels_ms = a + b;
     }
     return GFS_OK;
 }
@@ -466,29 +454,27 @@ int gfs_rank_get_info(const gfs_rank *r, gfs_rank_info *out) {
 uint64_t gfs_rank_exchange_count(const gfs_rank *r) { return r ? 2 * r->total : 0; }
 
 static int ensure_buf(gfs_rank *r) {
-    if (r->d_buf || r->total == 0) return GFS_OK;
-    MHIPCHK(hipSetDevice(r->cfg.device));
-    MHIPCHK(hipMalloc(&r->d_buf, 2 * r->total * payload_size(r)));
-    r->buf_owned = true;
-    return GFS_OK;
+    if (r->d_buf.p || r->total == 0) return GFS_OK;
+    HIPCHK(hipSetDevice(r->cfg.device));
+    return r->d_buf.reserve(2 * r->total * payload_size(r), "hipMalloc exchange buffer");
 }
 void *gfs_rank_exchange_buffer(gfs_rank *r) {
     if (!r || ensure_buf(r)) return nullptr;
-    return r->d_buf;
+    return r->d_buf.p;
 }
 int gfs_rank_bind_exchange_buffer(gfs_rank *r, void *device_ptr) {
     if (!r || !device_ptr) return gfs_set_error(GFS_E_ARG, "null argument");
-    if (r->d_buf && r->buf_owned) { MHIPCHK(hipSetDevice(r->cfg.device)); MHIPCHK(hipFree(r->d_buf)); }
-    r->d_buf = device_ptr; r->buf_owned = false;
+    if (r->d_buf.p && !r->d_buf.borrowed) HIPCHK(hipSetDevice(r->cfg.device));
+    HIPCHK(r->d_buf.borrow(device_ptr));                                   // (frees the rank's own)
     return GFS_OK;
 }
 
 static int snapshot(gfs_rank *r, hipStream_t st) {
     if (!r->total) return GFS_OK;
-    MHIPCHK(hipSetDevice(r->cfg.device));
+    HIPCHK(hipSetDevice(r->cfg.device));
     hipLaunchKernelGGL(gfs::exchange_snapshot_kernel, dim3(1024), dim3(256), 0, st, (const double *)gfs_ctx_positions_device(r->ctx),
                        r->d_xprev, r->d_esegs, (uint32_t)r->esegs.size(), r->total);
-    MHIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return GFS_OK;
 }
 
@@ -499,7 +485,7 @@ int gfs_rank_set_positions(gfs_rank *r, const double *host, uint64_t n) {
     if (rc) return rc;
     rc = snapshot(r, nullptr);
     if (rc) return rc;
-    MHIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipDeviceSynchronize());
     return GFS_OK;
 }
 // the caller replaced the positions behind the library's back (gfs_ctx_bind_positions + its own copy): re-snapshot
@@ -526,15 +512,15 @@ int gfs_rank_window_begin(gfs_rank *r, const uint64_t *ks, uint64_t n, void *hip
     if (!r->total) return GFS_OK;
     int rc = ensure_buf(r);
     if (rc) return rc;
-    MHIPCHK(hipSetDevice(r->cfg.device));
+    HIPCHK(hipSetDevice(r->cfg.device));
     const double *x = (const double *)gfs_ctx_positions_device(r->ctx);
-    MHIPCHK(hipEventRecord(r->ev[0], st));
+    HIPCHK(r->ev_prepare.start(st));
     if (r->cfg.payload) hipLaunchKernelGGL((gfs::exchange_prepare_kernel<double>), dim3(1024), dim3(256), 0, st, x, r->d_xprev,
-                                           (double *)r->d_buf, r->d_esegs, (uint32_t)r->esegs.size(), r->total);
-    else hipLaunchKernelGGL((gfs::exchange_prepare_kernel<float>), dim3(1024), dim3(256), 0, st, x, r->d_xprev, (float *)r->d_buf,
+                                           (double *)r->d_buf.p, r->d_esegs, (uint32_t)r->esegs.size(), r->total);
+    else hipLaunchKernelGGL((gfs::exchange_prepare_kernel<float>), dim3(1024), dim3(256), 0, st, x, r->d_xprev, (float *)r->d_buf.p,
                             r->d_esegs, (uint32_t)r->esegs.size(), r->total);
-    MHIPCHK(hipGetLastError());
-    MHIPCHK(hipEventRecord(r->ev[1], st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(r->ev_prepare.stop(st));
     return GFS_OK;
 }
 int gfs_rank_window_end(gfs_rank *r, void *hip_stream) {
@@ -542,7 +528,7 @@ int gfs_rank_window_end(gfs_rank *r, void *hip_stream) {
     r->windows++;
     if (!r->total) return GFS_OK;
     hipStream_t st = (hipStream_t)hip_stream;
-    MHIPCHK(hipSetDevice(r->cfg.device));
+    HIPCHK(hipSetDevice(r->cfg.device));
     double *x = (double *)gfs_ctx_positions_device(r->ctx);
     const double div = (r->cfg.merge_rule == 0 || r->cfg.merge_rule == 3) ? 0.0 : (r->cfg.merge_rule == 1 ? 1.0 : (double)r->cfg.world);   // 0 annealed, 3 plain touch
     // Rule 0 (annealed, the default).  c ranks each ran their share of the window on their own replica.  While the learning rate is large a
@@ -555,13 +541,13 @@ int gfs_rank_window_end(gfs_rank *r, void *hip_stream) {
     double cscale = 1.0;
     if (r->cfg.merge_rule == 0 && r->win_last_k < r->etas.size())
         cscale = std::min(1.0, (double)r->win_len * r->etas[r->win_last_k] / r->eta_sum);
-    MHIPCHK(hipEventRecord(r->ev[2], st));
+    HIPCHK(r->ev_apply.start(st));
     if (r->cfg.payload) hipLaunchKernelGGL((gfs::exchange_apply_kernel<double>), dim3(1024), dim3(256), 0, st, x, r->d_xprev,
-                                           (const double *)r->d_buf, r->d_esegs, (uint32_t)r->esegs.size(), r->total, div, cscale);
-    else hipLaunchKernelGGL((gfs::exchange_apply_kernel<float>), dim3(1024), dim3(256), 0, st, x, r->d_xprev, (const float *)r->d_buf,
+                                           (const double *)r->d_buf.p, r->d_esegs, (uint32_t)r->esegs.size(), r->total, div, cscale);
+    else hipLaunchKernelGGL((gfs::exchange_apply_kernel<float>), dim3(1024), dim3(256), 0, st, x, r->d_xprev, (const float *)r->d_buf.p,
                             r->d_esegs, (uint32_t)r->esegs.size(), r->total, div, cscale);
-    MHIPCHK(hipGetLastError());
-    MHIPCHK(hipEventRecord(r->ev[3], st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(r->ev_apply.stop(st));
     r->ev_pending = true;
     return GFS_OK;
 }
@@ -571,14 +557,14 @@ int gfs_rank_window_end(gfs_rank *r, void *hip_stream) {
 int gfs_rank_finish_begin(gfs_rank *r, double *full_device, void *hip_stream) {
     if (!r) return gfs_set_error(GFS_E_ARG, "rank is null");
     if (r->cfg.world < 2 || !r->x_len) return GFS_OK;
-    MHIPCHK(hipSetDevice(r->cfg.device));
+    HIPCHK(hipSetDevice(r->cfg.device));
     if (!full_device) {
-        if (!r->d_full) MHIPCHK(hipMalloc(&r->d_full, r->x_len * 8));
+        if (!r->d_full) HIPCHK(r->d_full.grow(r->x_len * 8));
         full_device = r->d_full;
     }
     hipLaunchKernelGGL(gfs::finish_mask_kernel, dim3(2048), dim3(256), 0, (hipStream_t)hip_stream,
                        (const double *)gfs_ctx_positions_device(r->ctx), full_device, r->d_owned, (uint32_t)r->owned.size(), r->x_len);
-    MHIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return GFS_OK;
 }
 double *gfs_rank_finish_buffer(gfs_rank *r) { return r ? r->d_full : nullptr; }
@@ -587,8 +573,8 @@ int gfs_rank_finish_end(gfs_rank *r, const double *full_device, void *hip_stream
     if (r->cfg.world < 2 || !r->x_len) return GFS_OK;
     if (!full_device) full_device = r->d_full;
     if (!full_device) return gfs_set_error(GFS_E_STATE, "gfs_rank_finish_begin has not run");
-    MHIPCHK(hipSetDevice(r->cfg.device));
-    MHIPCHK(hipMemcpyAsync(gfs_ctx_positions_device(r->ctx), full_device, r->x_len * 8, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
+    HIPCHK(hipSetDevice(r->cfg.device));
+    HIPCHK(hipMemcpyAsync(gfs_ctx_positions_device(r->ctx), full_device, r->x_len * 8, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
     return snapshot(r, (hipStream_t)hip_stream);
 }
 
@@ -606,7 +592,7 @@ int gfs_rank_run(gfs_rank *r, gfs_allreduce_fn allreduce, void *user, void *hip_
         int rc = gfs_rank_window_begin(r, ks.data(), ks.size(), hip_stream);
         if (rc < 0) return rc;
         if (r->cfg.world > 1) {
-            if (r->total && (rc = allreduce(user, r->d_buf, 2 * r->total, (int)r->cfg.payload, hip_stream)) != 0)
+            if (r->total && (rc = allreduce(user, r->d_buf.p, 2 * r->total, (int)r->cfg.payload, hip_stream)) != 0)
                 return gfs_set_error(GFS_E_STATE, "the caller's all-reduce failed");
             if ((rc = gfs_rank_window_end(r, hip_stream)) < 0) return rc;
         }
@@ -618,8 +604,8 @@ int gfs_rank_run(gfs_rank *r, gfs_allreduce_fn allreduce, void *user, void *hip_
             return gfs_set_error(GFS_E_STATE, "the caller's all-reduce failed");
         if ((rc = gfs_rank_finish_end(r, nullptr, hip_stream)) < 0) return rc;
     }
-    MHIPCHK(hipSetDevice(r->cfg.device));
-    MHIPCHK(hipStreamSynchronize((hipStream_t)hip_stream));
+    HIPCHK(hipSetDevice(r->cfg.device));
+    HIPCHK(hipStreamSynchronize((hipStream_t)hip_stream));
     return GFS_OK;
 }
 

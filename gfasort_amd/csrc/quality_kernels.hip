@@ -14,6 +14,7 @@
 // workgroup stores its partials, and ONE thread per step distance sums them in workgroup order (reduce_partials_kernel).
 // No floating-point atomics anywhere.
 #include "sgd_host.h"
+#include "device_memory.h"
 #include "quality_device.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -152,12 +153,12 @@ hipError_t sort_quality_device(const uint4 *d_step_rec, uint64_t n_steps, const 
     size_t tmp_bytes = 0;
     hipError_t e = rocprim::exclusive_scan(nullptr, tmp_bytes, lens, d_prefix, (uint64_t)0, (size_t)(n_nodes + 1), rocprim::plus<uint64_t>(), st);
     if (e != hipSuccess) return e;
-    void *d_tmp = nullptr;
-    if ((e = hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 8)) != hipSuccess) return e;
-    e = rocprim::exclusive_scan(d_tmp, tmp_bytes, lens, d_prefix, (uint64_t)0, (size_t)(n_nodes + 1), rocprim::plus<uint64_t>(), st);
+    Buffer d_tmp;
+    if ((e = d_tmp.grow(tmp_bytes ? tmp_bytes : 8)) != hipSuccess) return e;
+    e = rocprim::exclusive_scan(d_tmp.p, tmp_bytes, lens, d_prefix, (uint64_t)0, (size_t)(n_nodes + 1), rocprim::plus<uint64_t>(), st);
     if (e == hipSuccess) e = hipMemcpyAsync(total_len_out, d_prefix + n_nodes, 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(d_tmp);
+    d_tmp.reset();                                                         // (here, before the launches below: not at the end of scope)
     if (e != hipSuccess || *total_len_out >= (1ull << 53)) return e;
     const unsigned blocks = quality_blocks(n_steps);
     hipLaunchKernelGGL(scatter_sorted_pos_kernel, dim3(1024), dim3(256), 0, st, d_prefix, d_order, d_perm, d_spos, n_nodes);
@@ -377,9 +378,9 @@ hipError_t stretched_pairs_device(const uint4 *d_step_rec, uint64_t n_steps, con
     size_t tmp_bytes = 0;
     e = rocprim::exclusive_scan(nullptr, tmp_bytes, d_counts, d_offsets, (uint64_t)0, (size_t)(tiles + 1), rocprim::plus<uint64_t>(), st);
     if (e != hipSuccess) return e;
-    void *d_tmp = nullptr;
-    if ((e = hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 8)) != hipSuccess) return e;
-    e = rocprim::exclusive_scan(d_tmp, tmp_bytes, d_counts, d_offsets, (uint64_t)0, (size_t)(tiles + 1), rocprim::plus<uint64_t>(), st);
+    Buffer d_tmp;                                                          // (freed after the synchronise)
+    if ((e = d_tmp.grow(tmp_bytes ? tmp_bytes : 8)) != hipSuccess) return e;
+    e = rocprim::exclusive_scan(d_tmp.p, tmp_bytes, d_counts, d_offsets, (uint64_t)0, (size_t)(tiles + 1), rocprim::plus<uint64_t>(), st);
     if (e == hipSuccess) e = hipMemcpyAsync(total_out, d_offsets + tiles, 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && cap && d_list) {
         hipLaunchKernelGGL(stretched_tiles_kernel, dim3(blocks), dim3(Q_BLOCK), 0, st, d_step_rec, n_steps, d_x, n_nodes, dims, z, ratio, tiles,
@@ -387,7 +388,6 @@ hipError_t stretched_pairs_device(const uint4 *d_step_rec, uint64_t n_steps, con
         e = hipGetLastError();
     }
     const hipError_t e2 = hipStreamSynchronize(st);
-    (void)hipFree(d_tmp);
     return e != hipSuccess ? e : e2;
 }
 
