@@ -236,106 +236,99 @@ static void print_batch_stats(const gfs_batch_stats &bs) {
               << (bs.kernel_ms > 0 ? (double)bs.term_updates / bs.kernel_ms / 1e6 : 0.0) << " G updates/s), run " << bs.total_ms << " ms\n";
 }
 
-// --batch LIST -p L: every graph of the list gets its own LayoutSGDParams::from_graph, as a -i/-o run gives it; those of 2 or 3
-// dimensions that run reference streams are laid out in one batch, the others alone; every output is what the single run writes.
-static int run_layout_batch(const Args &args, const std::vector<BatchFiles> &files, std::vector<BidirectedGraph> &graphs) {
-    std::vector<BatchLayoutItem> items(files.size());
-    for (size_t i = 0; i < files.size(); ++i) {
-        items[i].graph = &graphs[i];
-        items[i].params = LayoutSGDParams::from_graph(graphs[i], args.dimensions, args.threads);
-        items[i].params.iter_max = args.layout_iter;
-        items[i].params.progress = args.verbose >= 2;
-    }
-    HipOptions opt; opt.cfg.n_streams = args.streams; opt.cfg.flags = args.flags | GFS_F_BUNDLE(args.bundle);
-    try {
-        const gfs_batch_stats bs = sgd_layout_batch(items, (uint8_t)args.verbose, opt, args.stress_profile);
-        for (size_t i = 0; i < items.size(); ++i) {
-            const BatchLayoutItem &it = items[i];
-            if (args.verbose >= 1) {
-                std::cerr << "[gfasort_hip] " << files[i].in << ": " << graphs[i].node_count() << " nodes, "
-                          << (it.batched ? "in the batch" : it.stats.iterations ? "alone" : "nothing to do") << "\n";
-                char buf[64]; snprintf(buf, sizeof buf, "%.6f", calculate_layout_stress(graphs[i], it.layout, 10000));
-                std::cerr << "[gfasort] layout stress: " << buf << "\n";
-                if (it.stats.iterations) print_run_stats(it.stats);
-            }
-            if (args.stress_profile && it.layout.num_nodes) {
-                if (it.batched) print_stress_profile(it.profile);                     // read while the batch was resident
-                else { FlatGraph f = graphs[i].flatten(); print_stress_profile(layout_pair_errors(f, it.layout.dimensions, it.layout.coords, step_distance_ladder(f))); }
-            }
-            if (args.diagnose && it.layout.num_nodes) print_diagnosis(graphs[i].flatten(), graphs[i].paths, it.layout.dimensions, it.layout.coords, args.diagnose_ratio);
-        }
-        if (args.verbose >= 1) print_batch_stats(bs);
-    } catch (const std::exception &e) {
-        std::cerr << "Error: " << e.what() << "\n";
-        return 1;
-    }
-    for (size_t i = 0; i < files.size(); ++i) {
-        if (args.verbose >= 1) std::cerr << "[gfasort] writing layout to " << files[i].layout << "\n";
-        std::ofstream f(files[i].layout, std::ios::binary);
-        if (!f) { std::cerr << "Error creating layout file: " << std::strerror(errno) << "\n"; return 1; }
-        items[i].layout.write_tsv(f);
-        f.close();
-        if (!f) { std::cerr << "Error writing layout file " << files[i].layout << ": " << std::strerror(errno) << "\n"; return 1; }
-    }
-    return 0;
+// --stress-profile and --diagnose of the positions a step ended with: x by dense index of f (dims = 0, a sort; f is the graph as
+// it was before the sort reordered it) or Layout.coords.  resident: the profile, where a batch read it while the graph was resident.
+static void print_measures(const Args &args, const FlatGraph &f, const std::vector<BiPath> &paths, size_t dims, const std::vector<double> &x,
+                           const std::vector<gfs_pair_error> *resident = nullptr) {
+    if (args.stress_profile) print_stress_profile(resident ? *resident : layout_pair_errors(f, dims, x, step_distance_ladder(f)));
+    if (args.diagnose) print_diagnosis(f, paths, dims, x, args.diagnose_ratio);
 }
 
-// --batch LIST -p Y: every graph of the list gets its own YgsParams::from_graph, as a -i/-o run gives it; those that run reference
-// streams are sorted in one batch, the others alone; every output is what the single run writes.
-static int run_sort_batch(const Args &args, const std::vector<BatchFiles> &files, std::vector<BidirectedGraph> &graphs) {
-    std::vector<BatchSortItem> items(files.size());
-    for (size_t i = 0; i < files.size(); ++i) {
-        items[i].graph = &graphs[i];
-        items[i].params = YgsParams::from_graph(graphs[i], (uint8_t)args.verbose, args.threads).path_sgd;
-        items[i].params.iter_max = args.iter_max;
-    }
-    HipOptions opt; opt.cfg.n_streams = args.streams; opt.cfg.flags = args.flags | GFS_F_BUNDLE(args.bundle);
-    if (args.phased) opt.cfg.flags |= GFS_F_PHASED;
-    try {
-        const gfs_batch_stats bs = sgd_sort_batch(items, (uint8_t)args.verbose, opt, args.stress_profile || args.diagnose, args.stress_profile);
-        for (size_t i = 0; i < items.size(); ++i) {
-            const BatchSortItem &it = items[i];
-            if (args.verbose >= 1) {
-                std::cerr << "[gfasort_hip] " << files[i].in << ": " << graphs[i].node_count() << " nodes, "
-                          << (it.batched ? "in the batch" : it.stats.iterations ? "alone" : "nothing to do") << "\n";
-                if (it.stats.iterations) print_run_stats(it.stats);
-            }
-            if (args.stress_profile && !it.positions.empty()) {
-                if (it.batched) print_stress_profile(it.profile);                     // read while the batch was resident
-                else print_stress_profile(layout_pair_errors(it.before, 0, it.positions, step_distance_ladder(it.before)));
-            }
-            if (args.diagnose && !it.positions.empty()) print_diagnosis(it.before, graphs[i].paths, 0, it.positions, args.diagnose_ratio);
-        }
-        if (args.verbose >= 1) print_batch_stats(bs);
-    } catch (const std::exception &e) {
-        std::cerr << "Error: " << e.what() << "\n";
-        return 1;
-    }
-    return 0;
+static void print_layout_stress(const BidirectedGraph &g, const Layout &layout) {
+    char buf[64]; snprintf(buf, sizeof buf, "%.6f", calculate_layout_stress(g, layout, 10000));
+    std::cerr << "[gfasort] layout stress: " << buf << "\n";
 }
 
+// Every output file is written here: body(stream), closed, and an error of either said on stderr with the site's own words.
+template <class Body>
+static bool write_file(const std::string &path, const char *cannot_open, const char *cannot_write, Body body) {
+    std::ofstream f(path, std::ios::binary);
+    if (!f) { std::cerr << cannot_open << ": " << std::strerror(errno) << "\n"; return false; }
+    body(f);
+    f.close();                                                                        // (a full disk shows here at the latest)
+    if (!f) { std::cerr << cannot_write << " " << path << ": " << std::strerror(errno) << "\n"; return false; }
+    return true;
+}
+
+static bool write_gfa_file(const Args &args, const std::string &path, const BidirectedGraph &g) {
+    if (args.verbose >= 1) std::cerr << "[gfasort] writing " << path << "\n";
+    return write_file(path, "Error writing output file", "Error writing output file", [&](std::ostream &f) { g.write_gfa(f); });
+}
+
+static bool write_layout_file(const Args &args, const std::string &path, const Layout &layout) {
+    if (args.verbose >= 1) std::cerr << "[gfasort] writing layout to " << path << "\n";
+    return write_file(path, "Error creating layout file", "Error writing layout file", [&](std::ostream &f) { layout.write_tsv(f); });
+}
+
+// joins the warm-up thread on every way out that returns
+struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } };
+
+// --batch LIST: every graph of the list gets its own YgsParams::from_graph (-p Y) or LayoutSGDParams::from_graph (-p L), as a
+// -i/-o run gives it; those that run reference streams (-p L: in 2 or 3 dimensions) go through the step in one batch, the others
+// alone; every output is what the single run writes.
 static int run_batch(const Args &args) {
     const bool layouts = args.pipeline == "L";
     std::vector<BatchFiles> files;
     if (!read_batch_list(args, layouts, files)) return 1;
     std::thread warm([] { (void)gfs_warmup(0); });
-    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{warm};
+    Joiner joiner{warm};
     std::vector<BidirectedGraph> graphs(files.size());
     for (size_t i = 0; i < files.size(); ++i) {
         if (args.verbose >= 1) std::cerr << "[gfasort] reading " << files[i].in << "\n";
         try { graphs[i] = parse_gfa(read_file(files[i].in)); }
         catch (const std::exception &e) { std::cerr << "Error reading " << files[i].in << ": " << e.what() << "\n"; return 1; }
     }
-    const int rc = layouts ? run_layout_batch(args, files, graphs) : run_sort_batch(args, files, graphs);
-    if (rc) return rc;
-    for (size_t i = 0; i < files.size(); ++i) {
-        if (args.verbose >= 1) std::cerr << "[gfasort] writing " << files[i].out << "\n";
-        std::ofstream f(files[i].out, std::ios::binary);
-        if (!f) { std::cerr << "Error writing output file: " << std::strerror(errno) << "\n"; return 1; }
-        graphs[i].write_gfa(f);
-        f.close();                                                                    // (a full disk shows here at the latest)
-        if (!f) { std::cerr << "Error writing output file " << files[i].out << ": " << std::strerror(errno) << "\n"; return 1; }
+    std::vector<BatchSortItem> sorts(layouts ? 0 : files.size());
+    std::vector<BatchLayoutItem> lays(layouts ? files.size() : 0);
+    for (size_t i = 0; i < sorts.size(); ++i) {
+        sorts[i].graph = &graphs[i];
+        sorts[i].params = YgsParams::from_graph(graphs[i], (uint8_t)args.verbose, args.threads).path_sgd;
+        sorts[i].params.iter_max = args.iter_max;
     }
+    for (size_t i = 0; i < lays.size(); ++i) {
+        lays[i].graph = &graphs[i];
+        lays[i].params = LayoutSGDParams::from_graph(graphs[i], args.dimensions, args.threads);
+        lays[i].params.iter_max = args.layout_iter;
+        lays[i].params.progress = args.verbose >= 2;
+    }
+    HipOptions opt; opt.cfg.n_streams = args.streams; opt.cfg.flags = args.flags | GFS_F_BUNDLE(args.bundle);
+    if (args.phased) opt.cfg.flags |= GFS_F_PHASED;                                   // (-p Y only: parse_args)
+    const bool measure = args.stress_profile || args.diagnose;
+    try {
+        const gfs_batch_stats bs = layouts ? sgd_layout_batch(lays, (uint8_t)args.verbose, opt, args.stress_profile)
+                                           : sgd_sort_batch(sorts, (uint8_t)args.verbose, opt, measure, args.stress_profile);
+        for (size_t i = 0; i < files.size(); ++i) {
+            const bool batched = layouts ? lays[i].batched : sorts[i].batched;
+            const gfs_stats &st = layouts ? lays[i].stats : sorts[i].stats;
+            const std::vector<double> &x = layouts ? lays[i].layout.coords : sorts[i].positions;   // empty: nothing was placed
+            if (args.verbose >= 1) {
+                std::cerr << "[gfasort_hip] " << files[i].in << ": " << graphs[i].node_count() << " nodes, "
+                          << (batched ? "in the batch" : st.iterations ? "alone" : "nothing to do") << "\n";
+                if (layouts) print_layout_stress(graphs[i], lays[i].layout);
+                if (st.iterations) print_run_stats(st);
+            }
+            if (!measure || x.empty()) continue;
+            const std::vector<gfs_pair_error> *resident = !batched ? nullptr : layouts ? &lays[i].profile : &sorts[i].profile;
+            if (layouts) print_measures(args, graphs[i].flatten(), graphs[i].paths, lays[i].layout.dimensions, x, resident);
+            else print_measures(args, sorts[i].before, graphs[i].paths, 0, x, resident);
+        }
+        if (args.verbose >= 1) print_batch_stats(bs);
+    } catch (const std::exception &e) {
+        std::cerr << "Error: " << e.what() << "\n";
+        return 1;
+    }
+    for (size_t i = 0; i < lays.size(); ++i) if (!write_layout_file(args, files[i].layout, lays[i].layout)) return 1;
+    for (size_t i = 0; i < files.size(); ++i) if (!write_gfa_file(args, files[i].out, graphs[i])) return 1;
     if (warm.joinable()) warm.join();
     std::cerr.flush(); std::cout.flush();
     std::_Exit(0);
@@ -351,7 +344,7 @@ int main(int argc, char **argv) {
     double t_read = 0, t_parse = 0, t_steps = 0, t_write = 0;
     // bring the HIP context up while the GFA is read and parsed (errors surface later, in the SGD call)
     std::thread warm([] { (void)gfs_warmup(0); });
-    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{warm};
+    Joiner joiner{warm};
     if (args.verbose >= 1) std::cerr << "[gfasort] reading " << args.input << "\n";
     std::string content;
     try { content = read_file(args.input); }
@@ -377,6 +370,7 @@ int main(int argc, char **argv) {
 
     bool have_layout = false;
     Layout layout;
+    const bool measure = args.stress_profile || args.diagnose;
     // the warm-up thread is NOT joined here: flattening and parameter scans need no GPU, and the first HIP
     // call of the SGD step simply waits inside the runtime for whatever initialisation is still going on
     auto t_s0 = std::chrono::steady_clock::now();
@@ -394,11 +388,9 @@ int main(int argc, char **argv) {
                 // (the profile speaks the dense indices of the graph as it is before the sort reorders it)
                 FlatGraph before;
                 std::vector<double> x;
-                const bool measure = args.stress_profile || args.diagnose;
                 if (measure) before = graph.flatten();
                 sgd_sort_only(graph, sgd_params, (uint8_t)args.verbose, opt_y, &st, measure ? &x : nullptr);   // gfasort.rs:250-252
-                if (args.stress_profile && !x.empty()) print_stress_profile(layout_pair_errors(before, 0, x, step_distance_ladder(before)));
-                if (args.diagnose && !x.empty()) print_diagnosis(before, graph.paths, 0, x, args.diagnose_ratio);
+                if (!x.empty()) print_measures(args, before, graph.paths, 0, x);
                 if (args.phased && args.verbose >= 2) {
                     uint64_t kb = 0, ke = sgd_params.iter_max + 1;         // reference streams picked: the whole schedule is theirs
                     if (st.bundle == 64) { gfs_sgd_params cp = sgd_params.to_c(); gfs_phase_window(&cp, &kb, &ke); }
@@ -408,16 +400,8 @@ int main(int argc, char **argv) {
             } else {
                 layout = path_linear_sgd_layout(graph, layout_params, opt, &st);            // :265-267
                 have_layout = true;
-                if (args.verbose >= 1) {
-                    double stress = calculate_layout_stress(graph, layout, 10000);
-                    char buf[64]; snprintf(buf, sizeof buf, "%.6f", stress);
-                    std::cerr << "[gfasort] layout stress: " << buf << "\n";
-                }
-                if (args.stress_profile && layout.num_nodes) {
-                    FlatGraph f = graph.flatten();
-                    print_stress_profile(layout_pair_errors(f, layout.dimensions, layout.coords, step_distance_ladder(f)));
-                }
-                if (args.diagnose && layout.num_nodes) print_diagnosis(graph.flatten(), graph.paths, layout.dimensions, layout.coords, args.diagnose_ratio);
+                if (args.verbose >= 1) print_layout_stress(graph, layout);
+                if (measure && !layout.coords.empty()) print_measures(args, graph.flatten(), graph.paths, layout.dimensions, layout.coords);
             }
             if (args.verbose >= 1 && st.iterations) print_run_stats(st);
         }
@@ -430,20 +414,12 @@ int main(int argc, char **argv) {
     auto t_w0 = std::chrono::steady_clock::now();
     if (have_layout) {
         if (!args.layout_out.empty()) {
-            if (args.verbose >= 1) std::cerr << "[gfasort] writing layout to " << args.layout_out << "\n";
-            std::ofstream f(args.layout_out, std::ios::binary);
-            if (!f) { std::cerr << "Error creating layout file: " << std::strerror(errno) << "\n"; return 1; }
-            layout.write_tsv(f);
+            if (!write_layout_file(args, args.layout_out, layout)) return 1;
         } else if (args.verbose >= 1) {
             std::cerr << "[gfasort] warning: layout computed but --layout-out not specified\n";
         }
     }
-    if (args.verbose >= 1) std::cerr << "[gfasort] writing " << args.output << "\n";
-    {
-        std::ofstream f(args.output, std::ios::binary);
-        if (!f) { std::cerr << "Error writing output file: " << std::strerror(errno) << "\n"; return 1; }
-        graph.write_gfa(f);
-    }
+    if (!write_gfa_file(args, args.output, graph)) return 1;
     t_write = since(t_w0);
     if (args.verbose >= 1) {
         double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();

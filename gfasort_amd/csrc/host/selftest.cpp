@@ -6,6 +6,7 @@
 #include <fstream>
 #include <iostream>
 #include <sstream>
+#include <stdexcept>
 
 #include "sgd.hpp"
 
@@ -118,6 +119,21 @@ int main(int argc, char **argv) {
         Layout l = path_linear_sgd_layout(g, LayoutSGDParams());
         REQUIRE(l.num_nodes == 0 && l.dimensions == 2);
         std::cout << "ok empty\n";
+    }
+    {   // which graph a batch refused, read from the library's text: its position, or the library's error as it stands
+        const std::string one = "batch item 2: its plan is not the pooled fused reference-stream kernel";
+        const std::string many = "batch item 117: 4 workgroups, one launch holds 1";
+        REQUIRE(refused_batch_item(GFS_E_UNSUPPORTED, one, 3) == 2);
+        REQUIRE(refused_batch_item(GFS_E_UNSUPPORTED, many, 118) == 117);
+        auto rethrown = [](int rc, const std::string &why, size_t n) {
+            try { (void)refused_batch_item(rc, why, n); } catch (const std::runtime_error &e) { return e.what() == "gfasort_hip: " + why; }
+            return false;
+        };
+        REQUIRE(rethrown(GFS_E_UNSUPPORTED, "a batch of layouts has no start positions or rank order", 3));   // names no item
+        REQUIRE(rethrown(GFS_E_UNSUPPORTED, "batch item : no number", 3));
+        REQUIRE(rethrown(GFS_E_UNSUPPORTED, one, 2) && rethrown(GFS_E_UNSUPPORTED, many, 117));                // one past the list
+        REQUIRE(rethrown(GFS_E_STATE, one, 3));                                                                // another code
+        std::cout << "ok refused item\n";
     }
     {   // the reader's path-step tokenizer: trims, skips empty tokens, cuts long lists into pieces (any thread count)
         std::string small = "S\t1\tA\nS\t2\tC\nS\t3\tG\nP\tp\t1+,, 2- ,3+ ,\t*\nP\tempty\t\t*\nP\tq\t3x,+2+\t*\n";

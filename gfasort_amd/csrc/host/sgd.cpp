@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstring>
 #include <iostream>
+#include <memory>
 #include <ostream>
 #include <stdexcept>
 
@@ -237,37 +238,94 @@ void sgd_sort_only(BidirectedGraph &g, const PathSGDParams &p, uint8_t verbose, 
     if (verbose >= 2) std::cerr << "[path_sgd] Complete\n";
 }
 
-// The pair errors of every item of a resident batch at its own step_distance_ladder, in ONE gfs_batch_pair_errors: the ladders are
-// prefixes of the longest one (the rungs do not depend on the graph, only where they stop), so the longest is measured for
-// all and every item keeps its own rungs.  fs[k]: the flattened graph of batch item k; out[k]: its rows.
-static void batch_profiles(gfs_batch *b, const std::vector<const FlatGraph *> &fs, const std::vector<std::vector<gfs_pair_error> *> &out) {
+// ---- batches: what sgd_sort_batch and sgd_layout_batch share ------------------------------------------------------------------
+size_t refused_batch_item(int rc, const std::string &why, size_t n) {
+    static const char phrase[] = "batch item ";
+    const size_t at = why.find(phrase);
+    const char *digits = at == std::string::npos ? "" : why.c_str() + at + sizeof phrase - 1;
+    char *end = nullptr;
+    const unsigned long long named = std::strtoull(digits, &end, 10);
+    if (rc != GFS_E_UNSUPPORTED || end == digits || named >= n) throw std::runtime_error("gfasort_hip: " + why);
+    return (size_t)named;
+}
+
+namespace {
+struct Destroy {
+    void operator()(gfs_ctx *c) const { gfs_ctx_destroy(c); }
+    void operator()(gfs_batch *b) const { gfs_batch_destroy(b); }
+};
+using CtxHandle = std::unique_ptr<gfs_ctx, Destroy>;
+using BatchHandle = std::unique_ptr<gfs_batch, Destroy>;     // borrows its contexts: declared after them, so that it goes first
+struct Slot { CtxHandle ctx; FlatGraph f; };                  // a graph on the device, and the flattened graph its context reads
+}  // namespace
+
+// Flatten g and set a context up for it with setup(ctx).  Returns what setup returned: on GFS_NOTHING_TO_DO the context is gone
+// again, otherwise it is resident and `stats` says what it will run.
+template <class Setup>
+static int open_slot(Slot &s, const BidirectedGraph &g, gfs_stats &stats, Setup setup) {
+    s.f = g.flatten();
+    gfs_graph_view v = s.f.view();
+    gfs_ctx *c = nullptr;
+    check(gfs_ctx_create(&v, 0, &c));
+    s.ctx.reset(c);
+    const int rc = setup(c);
+    check(rc);
+    if (rc == GFS_NOTHING_TO_DO) s.ctx.reset();
+    else check(gfs_ctx_stats(c, &stats));
+    return rc;
+}
+
+// One gfs_batch of the contexts of `together` (indices into slots).  A graph the batch refuses (flags that rule the fused launch
+// out, more workgroups than one launch holds) is named by the error: it moves from `together` to `refused`, for the caller to
+// run alone, and the others are tried again.  Empty when nothing is left.
+static BatchHandle create_batch(const std::vector<Slot> &slots, std::vector<size_t> &together, std::vector<size_t> &refused, uint8_t verbose) {
+    while (!together.empty()) {
+        std::vector<gfs_ctx *> ctxs;
+        for (size_t i : together) ctxs.push_back(slots[i].ctx.get());
+        gfs_batch *b = nullptr;
+        const int rc = gfs_batch_create(ctxs.data(), ctxs.size(), nullptr, &b);
+        if (rc >= 0) return BatchHandle(b);
+        const std::string why = gfs_last_error();
+        const size_t named = refused_batch_item(rc, why, together.size());
+        if (verbose >= 1) std::cerr << "[gfasort_hip] batch: graph " << together[named] << " runs alone (" << why << ")\n";
+        refused.push_back(together[named]);
+        together.erase(together.begin() + (std::ptrdiff_t)named);
+    }
+    return {};
+}
+
+// keep_profile: the pair errors of every item of a resident batch at its own step_distance_ladder, in ONE gfs_batch_pair_errors:
+// the ladders are prefixes of the longest one (the rungs do not depend on the graph, only where they stop), so the longest is
+// measured for all and every item keeps its own rungs.  together[k]: the graph of the batch's k-th item.
+template <class Item>
+static void batch_profiles(gfs_batch *b, const std::vector<Slot> &slots, std::vector<Item> &items, const std::vector<size_t> &together) {
     std::vector<std::vector<uint64_t>> ladders;
     size_t longest = 0;
-    for (const FlatGraph *f : fs) {
-        ladders.push_back(step_distance_ladder(*f));
+    for (size_t i : together) {
+        ladders.push_back(step_distance_ladder(slots[i].f));
         if (ladders.back().size() > ladders[longest].size()) longest = ladders.size() - 1;
     }
     const std::vector<uint64_t> &zs = ladders[longest];
-    std::vector<gfs_pair_error> rows(fs.size() * zs.size());
+    std::vector<gfs_pair_error> rows(together.size() * zs.size());
     check(gfs_batch_pair_errors(b, zs.data(), zs.size(), rows.data(), nullptr, nullptr));
-    for (size_t k = 0; k < fs.size(); ++k)
-        out[k]->assign(rows.begin() + (std::ptrdiff_t)(k * zs.size()), rows.begin() + (std::ptrdiff_t)(k * zs.size() + ladders[k].size()));
+    for (size_t k = 0; k < together.size(); ++k)
+        items[together[k]].profile.assign(rows.begin() + (std::ptrdiff_t)(k * zs.size()), rows.begin() + (std::ptrdiff_t)(k * zs.size() + ladders[k].size()));
+}
+
+static void add_batch_stats(gfs_batch_stats &sum, const gfs_batch_stats &one) {
+    sum.items += one.items; sum.items_run += one.items_run; sum.launches += one.launches; sum.blocks += one.blocks;
+    sum.term_updates += one.term_updates; sum.attempts += one.attempts; sum.kernel_ms += one.kernel_ms; sum.total_ms += one.total_ms;
 }
 
 gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbose, const HipOptions &opt, bool keep_positions, bool keep_profile) {
-    struct Slot { gfs_ctx *ctx = nullptr; FlatGraph f; };
     std::vector<Slot> slots(items.size());
-    struct Cleanup {
-        std::vector<Slot> &s; gfs_batch *b = nullptr;
-        ~Cleanup() { if (b) gfs_batch_destroy(b); for (auto &x : s) if (x.ctx) gfs_ctx_destroy(x.ctx); }
-    } cleanup{slots};
     gfs_batch_stats bs{};
     // reorder the graph by its rank order, keep what was asked for, free the context
     auto apply = [&](size_t i, std::vector<double> &&x, const auto *order, size_t n) {
         BatchSortItem &it = items[i];
         const FlatGraph &f = slots[i].f;
-        check(gfs_ctx_stats(slots[i].ctx, &it.stats));
-        gfs_ctx_destroy(slots[i].ctx); slots[i].ctx = nullptr;
+        check(gfs_ctx_stats(slots[i].ctx.get(), &it.stats));
+        slots[i].ctx.reset();
         std::vector<Handle> ordering;
         ordering.reserve(n);
         for (size_t r = 0; r < n; ++r) ordering.push_back(Handle::forward(f.node_ids[order[r]]));   // idx -> handle, sgd.rs:649-662
@@ -276,7 +334,7 @@ gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbos
     };
     // a graph that runs alone: start positions, run, read back through its own context
     auto finish_alone = [&](size_t i) {
-        gfs_ctx *c = slots[i].ctx;
+        gfs_ctx *c = slots[i].ctx.get();
         check(gfs_ctx_init_positions(c));
         check(gfs_ctx_run(c, nullptr));
         std::vector<double> x(slots[i].f.node_len.size());
@@ -285,66 +343,35 @@ gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbos
         check(gfs_ctx_sort_order(c, order.data(), order.size()));
         apply(i, std::move(x), order.data(), order.size());
     };
-    std::vector<size_t> together;                                                     // indices into items: the batch's candidates
+    std::vector<size_t> together, refused;                                            // indices into items: the batch's candidates
     for (size_t i = 0; i < items.size(); ++i) {
         BatchSortItem &it = items[i];
         it.stats = gfs_stats{}; it.batched = false; it.positions.clear(); it.profile.clear();
         if (!it.graph || it.graph->node_count() == 0) continue;                       // sgd.rs:242-244
-        slots[i].f = it.graph->flatten();
-        gfs_graph_view v = slots[i].f.view();
-        gfs_sgd_params cp = it.params.to_c();
-        check(gfs_ctx_create(&v, 0, &slots[i].ctx));
-        const int rc = gfs_ctx_setup_1d(slots[i].ctx, &cp, &opt.cfg, nullptr, nullptr);
-        check(rc);
-        if (rc == GFS_NOTHING_TO_DO) {
+        const gfs_sgd_params cp = it.params.to_c();
+        if (open_slot(slots[i], *it.graph, it.stats, [&](gfs_ctx *c) { return gfs_ctx_setup_1d(c, &cp, &opt.cfg, nullptr, nullptr); }) == GFS_NOTHING_TO_DO)
             std::cerr << "[path_sgd] No paths with multiple steps found\n";          // sgd.rs:259
-            gfs_ctx_destroy(slots[i].ctx); slots[i].ctx = nullptr;
-            continue;
-        }
-        check(gfs_ctx_stats(slots[i].ctx, &it.stats));
-        if (it.stats.bundle == 1) together.push_back(i);                              // stays resident until the batch has run
+        else if (it.stats.bundle == 1) together.push_back(i);                         // stays resident until the batch has run
         else finish_alone(i);                                                         // a team-kernel graph: alone, now
     }
-    // A graph the batch refuses (flags that rule the fused launch out, more workgroups than one launch holds) is named by the
-    // error: it is taken out and runs alone, the others still run together.
-    std::vector<size_t> refused;
-    while (!together.empty() && !cleanup.b) {
-        std::vector<gfs_ctx *> ctxs;
-        for (size_t i : together) ctxs.push_back(slots[i].ctx);
-        const int rc = gfs_batch_create(ctxs.data(), ctxs.size(), nullptr, &cleanup.b);
-        if (rc != GFS_E_UNSUPPORTED) { check(rc); break; }
-        const std::string why = gfs_last_error();
-        unsigned long long named = 0;
-        const size_t at = why.find("batch item ");
-        if (at == std::string::npos || std::sscanf(why.c_str() + at, "batch item %llu", &named) != 1 || named >= together.size()) check(rc);
-        if (verbose >= 1) std::cerr << "[gfasort_hip] batch: graph " << together[named] << " runs alone (" << why << ")\n";
-        refused.push_back(together[named]);
-        together.erase(together.begin() + (std::ptrdiff_t)named);
-    }
-    if (cleanup.b) {
+    if (BatchHandle b = create_batch(slots, together, refused, verbose)) {
         // start positions, the run and the read-out of all its graphs: one launch each, two copies (K4b, K1f, K6b)
-        check(gfs_batch_init_positions(cleanup.b, nullptr));
-        check(gfs_batch_run(cleanup.b, nullptr));
-        check(gfs_batch_get_stats(cleanup.b, &bs));
+        check(gfs_batch_init_positions(b.get(), nullptr));
+        check(gfs_batch_run(b.get(), nullptr));
+        check(gfs_batch_get_stats(b.get(), &bs));
         std::vector<uint64_t> offsets(together.size() + 1);
-        check(gfs_batch_result_offsets(cleanup.b, offsets.data(), offsets.size()));
+        check(gfs_batch_result_offsets(b.get(), offsets.data(), offsets.size()));
         std::vector<double> x(offsets.back());
         std::vector<uint32_t> order(offsets.back());
         double readout_ms = 0.0;
-        check(gfs_batch_results(cleanup.b, x.data(), order.data(), offsets.back(), &readout_ms, nullptr));
+        check(gfs_batch_results(b.get(), x.data(), order.data(), offsets.back(), &readout_ms, nullptr));
         if (verbose >= 2) std::cerr << "[gfasort_hip] batch: read-out of " << together.size() << " graphs, " << readout_ms << " ms on the device\n";
-        if (keep_profile) {
-            std::vector<const FlatGraph *> fs;
-            std::vector<std::vector<gfs_pair_error> *> rows;
-            for (size_t i : together) { fs.push_back(&slots[i].f); rows.push_back(&items[i].profile); }
-            batch_profiles(cleanup.b, fs, rows);
-        }
-        gfs_batch_destroy(cleanup.b); cleanup.b = nullptr;                            // (before its contexts go)
+        if (keep_profile) batch_profiles(b.get(), slots, items, together);
+        b.reset();                                                                    // (before its contexts go)
         for (size_t k = 0; k < together.size(); ++k) {
-            const size_t i = together[k];
-            items[i].batched = true;
-            apply(i, std::vector<double>(x.begin() + (std::ptrdiff_t)offsets[k], x.begin() + (std::ptrdiff_t)offsets[k + 1]), order.data() + offsets[k],
-                  (size_t)(offsets[k + 1] - offsets[k]));
+            items[together[k]].batched = true;
+            apply(together[k], std::vector<double>(x.begin() + (std::ptrdiff_t)offsets[k], x.begin() + (std::ptrdiff_t)offsets[k + 1]),
+                  order.data() + offsets[k], (size_t)(offsets[k + 1] - offsets[k]));
         }
     }
     for (size_t i : refused) finish_alone(i);
@@ -382,16 +409,11 @@ Layout path_linear_sgd_layout(const BidirectedGraph &g, const LayoutSGDParams &p
 }
 
 gfs_batch_stats sgd_layout_batch(std::vector<BatchLayoutItem> &items, uint8_t verbose, const HipOptions &opt, bool keep_profile) {
-    struct Slot { gfs_ctx *ctx = nullptr; FlatGraph f; };
     std::vector<Slot> slots(items.size());
-    struct Cleanup {
-        std::vector<Slot> &s; gfs_batch *b = nullptr;
-        ~Cleanup() { if (b) gfs_batch_destroy(b); for (auto &x : s) if (x.ctx) gfs_ctx_destroy(x.ctx); }
-    } cleanup{slots};
     gfs_batch_stats bs{};
     // a graph that runs alone: the single call, after its context (if any) has left the device
     auto finish_alone = [&](size_t i) {
-        if (slots[i].ctx) { gfs_ctx_destroy(slots[i].ctx); slots[i].ctx = nullptr; }
+        slots[i].ctx.reset();
         items[i].layout = path_linear_sgd_layout(*items[i].graph, items[i].params, opt, &items[i].stats);
     };
     std::vector<size_t> candidates;                                                   // indices into items, of either dimension
@@ -402,63 +424,39 @@ gfs_batch_stats sgd_layout_batch(std::vector<BatchLayoutItem> &items, uint8_t ve
         it.layout = Layout(D, 0);
         if (!it.graph || it.graph->node_count() == 0) continue;                       // sgd.rs:780-782
         if (D != 2 && D != 3) { finish_alone(i); continue; }                          // no batch kernel for the dimension
-        slots[i].f = it.graph->flatten();
-        gfs_graph_view v = slots[i].f.view();
-        gfs_layout_params cp = it.params.to_c();
-        check(gfs_ctx_create(&v, 0, &slots[i].ctx));
-        const int rc = gfs_ctx_setup_nd(slots[i].ctx, &cp, &opt.cfg, nullptr, nullptr);
-        check(rc);
-        if (rc != GFS_NOTHING_TO_DO) check(gfs_ctx_stats(slots[i].ctx, &it.stats));
+        const gfs_layout_params cp = it.params.to_c();
+        const int rc = open_slot(slots[i], *it.graph, it.stats, [&](gfs_ctx *c) { return gfs_ctx_setup_nd(c, &cp, &opt.cfg, nullptr, nullptr); });
         if (rc == GFS_NOTHING_TO_DO || it.stats.bundle != 1) { it.stats = gfs_stats{}; finish_alone(i); continue; }   // (the single call says why)
         candidates.push_back(i);                                                      // stays resident until its batch has run
     }
     for (size_t D : {(size_t)2, (size_t)3}) {
         std::vector<size_t> together, refused;
         for (size_t i : candidates) if (items[i].params.dimensions == D) together.push_back(i);
-        while (!together.empty() && !cleanup.b) {                                     // sgd_sort_batch's refusal loop
-            std::vector<gfs_ctx *> ctxs;
-            for (size_t i : together) ctxs.push_back(slots[i].ctx);
-            const int rc = gfs_batch_create(ctxs.data(), ctxs.size(), nullptr, &cleanup.b);
-            if (rc != GFS_E_UNSUPPORTED) { check(rc); break; }
-            const std::string why = gfs_last_error();
-            unsigned long long named = 0;
-            const size_t at = why.find("batch item ");
-            if (at == std::string::npos || std::sscanf(why.c_str() + at, "batch item %llu", &named) != 1 || named >= together.size()) check(rc);
-            if (verbose >= 1) std::cerr << "[gfasort_hip] batch: graph " << together[named] << " runs alone (" << why << ")\n";
-            refused.push_back(together[named]);
-            together.erase(together.begin() + (std::ptrdiff_t)named);
-        }
-        if (cleanup.b) {
+        if (BatchHandle b = create_batch(slots, together, refused, verbose)) {
             // start coordinates, the run and the read-out of all its graphs: one call each (K4c, K2f, K6c)
             std::vector<uint64_t> offsets(together.size() + 1);
-            check(gfs_batch_result_offsets(cleanup.b, offsets.data(), offsets.size()));
+            check(gfs_batch_result_offsets(b.get(), offsets.data(), offsets.size()));
             std::vector<double> coords(offsets.back() * 2 * D);
             for (size_t k = 0; k < together.size(); ++k) {
                 const std::vector<double> c0 = default_layout_init(slots[together[k]].f, D, items[together[k]].params.seed);
                 std::copy(c0.begin(), c0.end(), coords.begin() + (std::ptrdiff_t)(offsets[k] * 2 * D));
             }
-            check(gfs_batch_upload_coords(cleanup.b, coords.data(), coords.size(), nullptr));
-            check(gfs_batch_run(cleanup.b, nullptr));
+            check(gfs_batch_upload_coords(b.get(), coords.data(), coords.size(), nullptr));
+            check(gfs_batch_run(b.get(), nullptr));
             gfs_batch_stats one{};
-            check(gfs_batch_get_stats(cleanup.b, &one));
-            bs.items += one.items; bs.items_run += one.items_run; bs.launches += one.launches; bs.blocks += one.blocks;
-            bs.term_updates += one.term_updates; bs.attempts += one.attempts; bs.kernel_ms += one.kernel_ms; bs.total_ms += one.total_ms;
+            check(gfs_batch_get_stats(b.get(), &one));
+            add_batch_stats(bs, one);
             double readout_ms = 0.0;
-            check(gfs_batch_coords(cleanup.b, coords.data(), coords.size(), &readout_ms, nullptr));
+            check(gfs_batch_coords(b.get(), coords.data(), coords.size(), &readout_ms, nullptr));
             if (verbose >= 2) std::cerr << "[gfasort_hip] batch: coordinates of " << together.size() << " graphs, " << readout_ms << " ms on the device\n";
-            if (keep_profile) {
-                std::vector<const FlatGraph *> fs;
-                std::vector<std::vector<gfs_pair_error> *> rows;
-                for (size_t i : together) { fs.push_back(&slots[i].f); rows.push_back(&items[i].profile); }
-                batch_profiles(cleanup.b, fs, rows);
-            }
-            gfs_batch_destroy(cleanup.b); cleanup.b = nullptr;                        // (before its contexts go)
+            if (keep_profile) batch_profiles(b.get(), slots, items, together);
+            b.reset();                                                                // (before its contexts go)
             for (size_t k = 0; k < together.size(); ++k) {
                 const size_t i = together[k];
                 BatchLayoutItem &it = items[i];
                 it.batched = true;
-                check(gfs_ctx_stats(slots[i].ctx, &it.stats));
-                gfs_ctx_destroy(slots[i].ctx); slots[i].ctx = nullptr;
+                check(gfs_ctx_stats(slots[i].ctx.get(), &it.stats));
+                slots[i].ctx.reset();
                 it.layout = Layout(D, slots[i].f.node_len.size());
                 std::copy(coords.begin() + (std::ptrdiff_t)(offsets[k] * 2 * D), coords.begin() + (std::ptrdiff_t)(offsets[k + 1] * 2 * D), it.layout.coords.begin());
             }

@@ -132,6 +132,11 @@ struct BatchLayoutItem {
 };
 // Returns the batches' figures, summed where both dimensions had one (all zero where no graph was batched).
 gfs_batch_stats sgd_layout_batch(std::vector<BatchLayoutItem> &items, uint8_t verbose, const HipOptions &opt = {}, bool keep_profile = false);
+// Which of the n contexts handed to gfs_batch_create its refusal names: rc is what the call returned and why its
+// gfs_last_error(), which reads "batch item K: ..." for a GFS_E_UNSUPPORTED.  Any other code, a text that names no item and a K
+// outside [0, n) are the library's error as it stands: thrown as std::runtime_error.  Both batch drivers read refusals through
+// this; it needs no device (host_selftest).
+size_t refused_batch_item(int rc, const std::string &why, size_t n);
 // sgd.rs:773.  Gaussian start of dims >= 1 is drawn here (Box-Muller on SplitMix64(seed); the
 // reference's rand_distr ziggurat stream is not reproduced).
 Layout path_linear_sgd_layout(const BidirectedGraph &g, const LayoutSGDParams &p, const HipOptions &opt = {},

@@ -69,6 +69,33 @@ def path_linear_sgd_layout(graph: FlatGraph, params: LayoutSGDParams, init: Opti
     return (lay, st) if return_stats else lay
 
 
+def _per_graph(v, n):
+    """One value for all n graphs, or one per graph: the list."""
+    return list(v) if isinstance(v, (list, tuple)) else [v] * n
+
+
+def _refused_item(e):
+    """Which of the contexts handed to hip.Batch its refusal names: GFS_E_UNSUPPORTED's text says which.  Any other code, or a
+    text that names no item, is the library's error as it stands."""
+    named = re.search(r"batch item (\d+)", str(e))
+    if e.code != -5 or not named:
+        raise e
+    return int(named.group(1))
+
+
+def _batch_of(held, candidates, max_blocks_per_launch):
+    """One hip.Batch of the contexts held[i], i in candidates.  A graph the batch refuses moves to the refused ones, for the
+    caller to run alone once the batch has run and is closed, and the others are tried again.  Returns (batch, or None when
+    nothing is left; the indices in it, in item order; the refused indices)."""
+    kept, refused = list(candidates), []
+    while kept:
+        try:
+            return hip.Batch([held[i] for i in kept], max_blocks_per_launch), kept, refused
+        except hip.GfsError as e:
+            refused.append(kept.pop(_refused_item(e)))
+    return None, kept, refused
+
+
 def path_sgd_sort_batch(graphs, params, cfg=None, max_blocks_per_launch: int = 0, device: int = 0):
     """path_sgd_sort over MANY graphs: the ones whose plan is the fused reference-stream kernel (graphs of fewer than 16384
     nodes under the default policy) run together as one hip.Batch — one persistent launch, or as few as fit the device, with
@@ -80,11 +107,15 @@ def path_sgd_sort_batch(graphs, params, cfg=None, max_blocks_per_launch: int = 0
     order (uint64 dense indices in ascending position order; empty likewise), stats (hip.Stats of the graph's context, None for
     an empty graph) and batched (whether it ran in the batch); and the batch's hip.BatchStats (None when nothing was batched)."""
     graphs = list(graphs)
-    per_graph = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * len(graphs)
-    params, cfgs = per_graph(params), per_graph(cfg)
+    params, cfgs = _per_graph(params, len(graphs)), _per_graph(cfg, len(graphs))
     if len(params) != len(graphs) or len(cfgs) != len(graphs):
         raise ValueError("params / cfg: one for all graphs or one per graph")
-    result = lambda ctx, batched: dict(positions=ctx.download(), order=ctx.sort_order(), stats=ctx.stats(), batched=batched)
+
+    def alone(ctx):
+        ctx.init_positions()
+        ctx.run()
+        return dict(positions=ctx.download(), order=ctx.sort_order(), stats=ctx.stats(), batched=False)
+
     out = [None] * len(graphs)
     held = {}                                                  # graph index -> its Context, for the batch's candidates
     try:
@@ -97,25 +128,15 @@ def path_sgd_sort_batch(graphs, params, cfg=None, max_blocks_per_launch: int = 0
                 rc = ctx.setup_1d(p, c)
                 if rc != hip.OK:                               # nothing to do
                     out[i]["stats"] = ctx.stats()
-                    continue
-                if ctx.stats().bundle == 1:                    # a candidate: initialised with the batch (or before its solo run)
+                elif ctx.stats().bundle == 1:                  # a candidate: initialised with the batch (or before its solo run)
                     held[i], ctx = ctx, None
-                    continue
-                ctx.init_positions()
-                ctx.run()
-                out[i] = result(ctx, False)
+                else:
+                    out[i] = alone(ctx)
             finally:
                 if ctx is not None:
                     ctx.close()
-        batched, batch, batch_stats = sorted(held), None, None
-        while batched and batch is None:
-            try:
-                batch = hip.Batch([held[i] for i in batched], max_blocks_per_launch)
-            except hip.GfsError as e:
-                named = re.search(r"batch item (\d+)", str(e))
-                if e.code != -5 or not named:                  # GFS_E_UNSUPPORTED names the item: that one runs alone
-                    raise
-                del batched[int(named.group(1))]
+        batch, batched, refused = _batch_of(held, sorted(held), max_blocks_per_launch)
+        batch_stats = None
         if batch is not None:
             try:
                 batch.init_positions()
@@ -126,11 +147,8 @@ def path_sgd_sort_batch(graphs, params, cfg=None, max_blocks_per_launch: int = 0
                 batch.close()
             for k, i in enumerate(batched):
                 out[i] = dict(positions=xs[k], order=orders[k], stats=held[i].stats(), batched=True)
-        for i, ctx in held.items():
-            if i not in batched:
-                ctx.init_positions()
-                ctx.run()
-                out[i] = result(ctx, False)
+        for i in refused:
+            out[i] = alone(held[i])
         return out, batch_stats
     finally:
         for ctx in held.values():
@@ -147,8 +165,7 @@ def path_linear_sgd_layout_batch(graphs, params, inits=None, cfg=None, max_block
     dict per graph, in order: layout (the Layout path_linear_sgd_layout returns), stats (hip.Stats, None for an empty graph)
     and batched; and a dict dimension -> hip.BatchStats of the batches that ran."""
     graphs = list(graphs)
-    per_graph = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * len(graphs)
-    params, cfgs = per_graph(params), per_graph(cfg)
+    params, cfgs = _per_graph(params, len(graphs)), _per_graph(cfg, len(graphs))
     inits = [None] * len(graphs) if inits is None else list(inits)
     if len(params) != len(graphs) or len(cfgs) != len(graphs) or len(inits) != len(graphs):
         raise ValueError("params / cfg / inits: one for all graphs or one per graph")
@@ -176,29 +193,21 @@ def path_linear_sgd_layout_batch(graphs, params, inits=None, cfg=None, max_block
                 alone(i)
         batch_stats = {}
         for D in (2, 3):
-            batched, batch = sorted(i for i in held if params[i].dimensions == D), None
-            while batched and batch is None:
+            batch, batched, refused = _batch_of(held, sorted(i for i in held if params[i].dimensions == D), max_blocks_per_launch)
+            if batch is not None:
                 try:
-                    batch = hip.Batch([held[i] for i in batched], max_blocks_per_launch)
-                except hip.GfsError as e:
-                    named = re.search(r"batch item (\d+)", str(e))
-                    if e.code != -5 or not named:              # GFS_E_UNSUPPORTED names the item: that one runs alone
-                        raise
-                    refused = batched.pop(int(named.group(1)))
-                    held.pop(refused).close()
-                    alone(refused)
-            if batch is None:
-                continue
-            try:
-                start = [inits[i] if inits[i] is not None else default_layout_init(graphs[i], D, params[i].seed) for i in batched]
-                batch.upload_coords(start)
-                batch.run()
-                batch_stats[D] = batch.stats()
-                coords, _ = batch.coords()
-            finally:
-                batch.close()
-            for k, i in enumerate(batched):
-                out[i] = dict(layout=Layout(D, graphs[i].n_nodes, coords[k].copy()), stats=held[i].stats(), batched=True)
+                    start = [inits[i] if inits[i] is not None else default_layout_init(graphs[i], D, params[i].seed) for i in batched]
+                    batch.upload_coords(start)
+                    batch.run()
+                    batch_stats[D] = batch.stats()
+                    coords, _ = batch.coords()
+                finally:
+                    batch.close()
+                for k, i in enumerate(batched):
+                    out[i] = dict(layout=Layout(D, graphs[i].n_nodes, coords[k].copy()), stats=held[i].stats(), batched=True)
+            for i in refused:
+                held.pop(i).close()                            # (the single call sets its own context up)
+                alone(i)
         return out, batch_stats
     finally:
         for ctx in held.values():

@@ -314,3 +314,18 @@ def test_cli_batch_writes_what_single_runs_write(tmp_path):
     r = subprocess.run([build.CLI, "--batch", str(tmp_path / "list.tsv"), "-p", "Y", "--layout-out", str(tmp_path / "l.tsv")],
                        capture_output=True, text=True)
     assert r.returncode != 0 and "--layout-out belongs to -p L" in r.stderr
+
+
+def test_cli_batch_sort_runs_every_refused_graph_alone(tmp_path):
+    """The list and flags above plus --hip-flags 4 (GFS_F_NO_FUSE: no fused launch, so no graph may be in a batch): the batch is
+    refused item after item until nothing is left, every graph runs alone after that, and writes what its single run writes."""
+    from util import cli_solo_and_batch
+    build.build_host()
+    names = [name for name, _ in FIXTURES]
+    flags = ["-p", "Y", "--streams", "1", "--iter-max", "10", "-v", "1", "--hip-flags", "4"]
+    solo, r = cli_solo_and_batch(build.CLI, tmp_path, names, flags, layouts=False)
+    assert all(s.returncode == 0 for s in solo), [s.stderr for s in solo]
+    assert r.returncode == 0, r.stderr
+    assert r.stderr.count("runs alone") == len(names) and "in the batch" not in r.stderr, r.stderr
+    for name in names:
+        assert (tmp_path / ("batch_" + name)).read_bytes() == (tmp_path / ("solo_" + name)).read_bytes(), name

@@ -329,3 +329,40 @@ def test_one_call_is_faster_than_the_per_item_loop():
         assert np.array_equal(_bits(coords[i]), _bits(xs[i])) and rows[i].tobytes() == loop_rows[i].tobytes(), i
     assert t_batch < t_loop, (t_batch, t_loop)
     b.close()
+
+
+def test_cli_batch_layout_runs_every_refused_graph_alone(tmp_path):
+    """-p L with the flags above plus --hip-flags 4 (GFS_F_NO_FUSE: no fused launch, so no graph may be in a batch): the batch is
+    refused item after item until nothing is left, every graph runs alone after that, and writes what its single run writes."""
+    from util import cli_solo_and_batch
+    build.build_host()
+    flags = ["-p", "L", "--streams", "1", "-v", "1", "--stress-profile", "--layout-iter", "1", "--hip-flags", "4"]
+    solo, r = cli_solo_and_batch(build.CLI, tmp_path, FIXTURES, flags, layouts=True)
+    assert all(s.returncode == 0 for s in solo), [s.stderr for s in solo]
+    assert r.returncode == 0, r.stderr
+    assert r.stderr.count("runs alone") == len(FIXTURES) and "in the batch" not in r.stderr, r.stderr
+    for name in FIXTURES:
+        assert (tmp_path / ("batch_" + name)).read_bytes() == (tmp_path / ("solo_" + name)).read_bytes(), name
+        tsv = (tmp_path / ("batch_" + name + ".tsv")).read_bytes()
+        assert tsv == (tmp_path / ("solo_" + name + ".tsv")).read_bytes() and tsv.count(b"\n") > 1, name
+
+
+def test_python_layout_batch_runs_a_refused_graph_alone():
+    """The layout twin of test_python_batch_sort_runs_a_refused_graph_alone.  One launch may hold one workgroup here: lil at 1000
+    streams (more than the 256 of one workgroup) cannot be in the batch and runs alone, after the batch; the other two still run
+    as a batch, each with the bits of its own single call at one stream."""
+    graphs = [load(name) for name in FIXTURES]
+    params = [_layout_params(g, 2, 5, min_term_updates=12000 if name.startswith("DRB1") else None) for g, name in zip(graphs, FIXTURES)]
+    one, wide = hip.make_config(n_streams=1), hip.make_config(n_streams=1000)
+    ctx = hip.Context(graphs[1])
+    assert ctx.setup_nd(params[1], wide) == hip.OK
+    assert ctx.stats().n_streams > 256 and ctx.stats().bundle == 1          # (the policy does not cap what was asked for)
+    ctx.close()
+    out, bs = S.path_linear_sgd_layout_batch(graphs, params, cfg=[one, wide, one], max_blocks_per_launch=1)
+    assert [r["batched"] for r in out] == [True, False, True]
+    assert list(bs) == [2] and (bs[2].items, bs[2].items_run) == (2, 2)
+    for i in (0, 2):
+        lay = S.path_linear_sgd_layout(graphs[i], params[i], cfg=one)
+        assert np.array_equal(_bits(out[i]["layout"].coords), _bits(lay.coords)), i
+    assert out[1]["stats"].n_streams == 1000 and np.isfinite(out[1]["layout"].coords).all()
+    assert out[1]["layout"].num_nodes == graphs[1].n_nodes

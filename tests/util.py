@@ -33,6 +33,22 @@ def load(name):
     return G.load_gfa(os.path.join(DATA, name))
 
 
+def cli_solo_and_batch(cli, tmp_path, names, flags, layouts):
+    """One `-i/-o` run per fixture (solo_NAME, and solo_NAME.tsv for a layout), then one `--batch LIST` run over all of them
+    (batch_NAME, batch_NAME.tsv), with the same flags.  Returns the completed processes: the solo ones, the batch's."""
+    import subprocess
+    solo, lines = [], []
+    for name in names:
+        src = os.path.join(DATA, name)
+        cmd = [cli, "-i", src, "-o", str(tmp_path / ("solo_" + name))] + flags
+        if layouts:
+            cmd += ["--layout-out", str(tmp_path / ("solo_" + name + ".tsv"))]
+        solo.append(subprocess.run(cmd, capture_output=True, text=True))
+        lines.append("\t".join([src, str(tmp_path / ("batch_" + name))] + ([str(tmp_path / ("batch_" + name + ".tsv"))] if layouts else [])) + "\n")
+    (tmp_path / "list.tsv").write_text("".join(lines))
+    return solo, subprocess.run([cli, "--batch", str(tmp_path / "list.tsv")] + flags, capture_output=True, text=True)
+
+
 def gaussian_init(g, dims, seed):
     """Caller-side init of layout dims >= 1 (the reference uses rand_distr StandardNormal, which is
     not restated): Box-Muller on SplitMix64(seed), scaled by sqrt(2N) like sgd.rs:836."""
