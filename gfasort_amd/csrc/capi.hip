@@ -3,6 +3,7 @@
 // points that stand where path_linear_sgd / path_linear_sgd_layout stand in the reference.  What a context launches is decided in
 // launch_policy.h; the host tables are host_tables.hip's; batches of contexts are capi_batch.hip's (capi_ctx.h is what the two share).
 #include "capi_ctx.h"
+#include "index_set.h"
 
 #include <algorithm>
 #include <chrono>
@@ -55,6 +56,7 @@ int gfs_warmup(int device) {
     HIPCHK(gfs::warm_module_1d_phased());
     laps.lap("module 1d");
     HIPCHK(gfs::warm_module_index());
+    HIPCHK(gfs::warm_module_index_set());
     HIPCHK(gfs::warm_module_quality());
     laps.lap("module index");
     HIPCHK(gfs::warm_module_nd());
@@ -279,17 +281,8 @@ int gfs_ctx_create(const gfs_graph_view *g, int device, gfs_ctx **out) {
 int gfs_ctx_create_with_layout(const gfs_graph_view *g, int device, const uint32_t *node_perm, gfs_ctx **out) {
     if (!g || !out) return fail(GFS_E_ARG, "null argument");
     *out = nullptr;
-    if (g->n_steps > (1ull << 40)) return fail(GFS_E_UNSUPPORTED, "more than 2^40 path steps");
-    if (g->n_nodes > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, "more than 2^31-1 nodes");
-    if (g->n_paths > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, "more than 2^31-1 paths");
-    if (g->n_steps && (!g->step_node || !g->step_is_rev)) return fail(GFS_E_ARG, "null step arrays");
-    if (!g->path_first_step) return fail(GFS_E_ARG, "null path_first_step");
-    if (g->n_nodes && !g->node_len) return fail(GFS_E_ARG, "null node_len");
-    if (g->path_first_step[0] != 0 || g->path_first_step[g->n_paths] != g->n_steps)
-        return fail(GFS_E_ARG, "path_first_step must start at 0 and end at n_steps");
-    for (uint64_t p = 0; p < g->n_paths; ++p)
-        if (g->path_first_step[p + 1] < g->path_first_step[p]) return fail(GFS_E_ARG, "path_first_step not monotone");
-    // (step_node's range is checked on the device, in the pass that derives the node layout)
+    if (int bad = gfs::check_view_counts(g, "")) return bad;               // (capi_ctx.h: shared with gfs_ctx_set_create)
+    if (int bad = gfs::check_view_paths(g, "")) return bad;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(GFS_E_HIP, "no HIP device available (libgfasort_hip has no CPU fallback)");
@@ -320,29 +313,14 @@ int gfs_ctx_create_with_layout(const gfs_graph_view *g, int device, const uint32
             seen[node_perm[k]] = 1; c->perm[k] = node_perm[k];
         }
     }
-    // Path records (host, P entries) and the facts the launch logic needs
+    // The facts the launch logic needs, with the refusals of over-long paths (capi_ctx.h), and the path records (host, P entries)
+    if (int bad = gfs::path_facts(g, c, "")) return bad;
     std::vector<uint4> prec(std::max<uint64_t>(g->n_paths, 1));
     for (uint64_t p = 0; p < g->n_paths; ++p) {
-        uint64_t b = g->path_first_step[p], e = g->path_first_step[p + 1];
-        uint32_t cnt = (uint32_t)(e - b);
-        if (e - b > 0xFFFFFFFFull) return fail(GFS_E_UNSUPPORTED, "a path with more than 2^32-1 steps");
+        const uint64_t b = g->path_first_step[p];
+        const uint32_t cnt = c->path_counts[p];
         prec[p].x = (uint32_t)b; prec[p].y = cnt;
         prec[p].z = cnt ? (uint32_t)(0u - cnt) % cnt : 0u; prec[p].w = (uint32_t)(b >> 32);
-        c->path_counts.push_back(cnt);
-        if (cnt > 1) c->valid_paths = true;                               // sgd.rs:250-256
-        c->max_path_steps = std::max(c->max_path_steps, cnt);
-    }
-    {   // a step record keeps 55 bits of a step's bp position (its top bits carry the crowding exponents): refuse longer paths
-        // instead of truncating them.  Cheap bound first (steps x longest node), the exact sum only where that fails.
-        uint32_t max_len = 0;
-        for (uint64_t k = 0; k < g->n_nodes; ++k) max_len = std::max(max_len, g->node_len[k]);
-        for (uint64_t p = 0; p < g->n_paths; ++p) {
-            const uint64_t b = g->path_first_step[p], e2 = g->path_first_step[p + 1];
-            if ((unsigned __int128)(e2 - b) * max_len < ((unsigned __int128)1 << 55)) continue;
-            unsigned __int128 bp = 0;
-            for (uint64_t s2 = b; s2 < e2; ++s2) { const uint32_t n = g->step_node[s2]; if (n < g->n_nodes) bp += g->node_len[n]; }
-            if (bp >= ((unsigned __int128)1 << 55)) return fail(GFS_E_UNSUPPORTED, "a path of 2^55 bp or more");
-        }
     }
     // K3 on the device: PathIndex::from_graph (sgd.rs:34-71) — the per-path exclusive prefix sum of
     // node lengths over the steps — written straight into the 16-byte step records
@@ -402,7 +380,7 @@ int gfs_ctx_create_with_layout(const gfs_graph_view *g, int device, const uint32
 }
 
 void gfs_ctx_destroy(gfs_ctx *c) {
-    if (!c) return;
+    if (!c || c->set_item) return;                                         // (a set's item goes with its set: gfs_ctx_set_destroy)
     (void)hipSetDevice(c->device);
     delete c;                                                              // (its buffers and events go here: the device is set)
 }

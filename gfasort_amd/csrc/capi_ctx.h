@@ -1,4 +1,4 @@
-// capi_ctx.h — what the two units of the C ABI share and nobody else includes: the resident context (capi.hip) as the batch
+// capi_ctx.h — what the units of the C ABI share and nobody else includes: the resident context (capi.hip) as the batch
 // entries (capi_batch.hip) read it, error reporting, and the few functions of capi.hip that a batch calls (the owners of its
 // memory and events: device_memory.h).  Nothing here is exported from the shared object.
 #pragma once
@@ -29,6 +29,7 @@ struct gfs_ctx {
     uint64_t n_nodes = 0, n_steps = 0, n_paths = 0;
     uint32_t max_path_steps = 0;
     bool valid_paths = false;
+    bool set_item = false;             // owned by a gfs_ctx_set (capi_set.hip): its index arrays are borrowed from the set's arena, gfs_ctx_destroy leaves it alone
     std::vector<uint32_t> path_counts;
     std::vector<uint32_t> perm;        // dense node index (ABI order) -> internal index (device layout of positions)
     // device mirror of PathIndex
@@ -64,6 +65,53 @@ struct gfs_ctx {
     uint64_t launches = 0;
     double total_ms = 0.0;
 };
+
+// What gfs_ctx_create checks of a graph view and derives from it on the host, shared with gfs_ctx_set_create (capi_set.hip), whose
+// item i is what gfs_ctx_create gives: one statement of each check, `prefix` ("" or "set item <i>: ") in front of its text.
+namespace gfs {
+// the checks that read no array
+static inline int check_view_counts(const gfs_graph_view *g, const std::string &prefix) {
+    if (g->n_steps > (1ull << 40)) return fail(GFS_E_UNSUPPORTED, prefix + "more than 2^40 path steps");
+    if (g->n_nodes > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, prefix + "more than 2^31-1 nodes");
+    if (g->n_paths > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, prefix + "more than 2^31-1 paths");
+    if (g->n_steps && (!g->step_node || !g->step_is_rev)) return fail(GFS_E_ARG, prefix + "null step arrays");
+    if (!g->path_first_step) return fail(GFS_E_ARG, prefix + "null path_first_step");
+    if (g->n_nodes && !g->node_len) return fail(GFS_E_ARG, prefix + "null node_len");
+    return GFS_OK;
+}
+// ... and those that read path_first_step (step_node's range is checked on the device, in the pass that derives the node layout)
+static inline int check_view_paths(const gfs_graph_view *g, const std::string &prefix) {
+    if (g->path_first_step[0] != 0 || g->path_first_step[g->n_paths] != g->n_steps)
+        return fail(GFS_E_ARG, prefix + "path_first_step must start at 0 and end at n_steps");
+    for (uint64_t p = 0; p < g->n_paths; ++p)
+        if (g->path_first_step[p + 1] < g->path_first_step[p]) return fail(GFS_E_ARG, prefix + "path_first_step not monotone");
+    return GFS_OK;
+}
+// The facts the launch logic needs (path_counts, valid_paths, max_path_steps), and the two refusals made with them: a path of more
+// than 2^32-1 steps, and — a step record keeps 55 bits of a step's bp position, its top bits carry the crowding exponents — a path
+// of 2^55 bp or more, refused instead of truncated (cheap bound first, steps x longest node; the exact sum only where that fails).
+static inline int path_facts(const gfs_graph_view *g, gfs_ctx *c, const std::string &prefix) {
+    c->path_counts.reserve(g->n_paths);
+    for (uint64_t p = 0; p < g->n_paths; ++p) {
+        const uint64_t b = g->path_first_step[p], e = g->path_first_step[p + 1];
+        if (e - b > 0xFFFFFFFFull) return fail(GFS_E_UNSUPPORTED, prefix + "a path with more than 2^32-1 steps");
+        const uint32_t cnt = (uint32_t)(e - b);
+        c->path_counts.push_back(cnt);
+        if (cnt > 1) c->valid_paths = true;                               // sgd.rs:250-256
+        if (cnt > c->max_path_steps) c->max_path_steps = cnt;
+    }
+    uint32_t max_len = 0;
+    for (uint64_t k = 0; k < g->n_nodes; ++k) if (g->node_len[k] > max_len) max_len = g->node_len[k];
+    for (uint64_t p = 0; p < g->n_paths; ++p) {
+        const uint64_t b = g->path_first_step[p], e = g->path_first_step[p + 1];
+        if ((unsigned __int128)(e - b) * max_len < ((unsigned __int128)1 << 55)) continue;
+        unsigned __int128 bp = 0;
+        for (uint64_t s = b; s < e; ++s) { const uint32_t n = g->step_node[s]; if (n < g->n_nodes) bp += g->node_len[n]; }
+        if (bp >= ((unsigned __int128)1 << 55)) return fail(GFS_E_UNSUPPORTED, prefix + "a path of 2^55 bp or more");
+    }
+    return GFS_OK;
+}
+}  // namespace gfs
 
 // capi.hip, for capi_batch.hip
 namespace gfs {

@@ -253,21 +253,65 @@ namespace {
 struct Destroy {
     void operator()(gfs_ctx *c) const { gfs_ctx_destroy(c); }
     void operator()(gfs_batch *b) const { gfs_batch_destroy(b); }
+    void operator()(gfs_ctx_set *s) const { gfs_ctx_set_destroy(s); }
 };
 using CtxHandle = std::unique_ptr<gfs_ctx, Destroy>;
 using BatchHandle = std::unique_ptr<gfs_batch, Destroy>;     // borrows its contexts: declared after them, so that it goes first
-struct Slot { CtxHandle ctx; FlatGraph f; };                  // a graph on the device, and the flattened graph its context reads
+// A graph on the device, and the flattened graph its context reads.  The context is its own, or an item of the drivers' context
+// set: gfs_ctx_destroy leaves an item alone (it goes with its set), so the handle of an item owns nothing, and ctx.reset() on
+// an item only lets go of it — its index arrays and what its setup allocated stay on the device until the set is destroyed at the
+// end of the driver (graphs of fewer than SET_MAX_NODES nodes: a few hundred KB each), where a context of its own is freed at once.
+struct Slot { CtxHandle ctx; FlatGraph f; };
+using SetHandle = std::unique_ptr<gfs_ctx_set, Destroy>;     // owns its items: declared before the slots and the batch, so that it goes last
+constexpr size_t SET_MAX_NODES = 16384;                       // graphs of fewer nodes are a batch's candidates under the default policy
 }  // namespace
 
-// Flatten g and set a context up for it with setup(ctx).  Returns what setup returned: on GFS_NOTHING_TO_DO the context is gone
-// again, otherwise it is resident and `stats` says what it will run.
+// The contexts of the graphs a batch can take — wanted(i), fewer than SET_MAX_NODES nodes, flags that ask for bundle 0 (auto) or
+// 1 — built in ONE gfs_ctx_set instead of one gfs_ctx_create each (K3b).  Their slots are flattened and hold their item; every
+// other slot is left for open_slot.  Empty when no graph qualifies.
+template <class Items, class Wanted>
+static SetHandle open_set(std::vector<Slot> &slots, const Items &items, const HipOptions &opt, uint8_t verbose, Wanted wanted) {
+    const uint32_t bundle = (opt.cfg.flags >> 16) & 0xFFu;
+    std::vector<size_t> idx;
+    std::vector<gfs_graph_view> views;
+    if (bundle > 1) return {};
+    for (size_t i = 0; i < items.size(); ++i) {
+        if (!items[i].graph || !wanted(i)) continue;
+        const size_t n = items[i].graph->node_count();
+        if (n == 0 || n >= SET_MAX_NODES) continue;
+        slots[i].f = items[i].graph->flatten();
+        idx.push_back(i);
+        views.push_back(slots[i].f.view());
+    }
+    if (idx.empty()) return {};
+    std::vector<const gfs_graph_view *> ptrs;
+    for (const gfs_graph_view &v : views) ptrs.push_back(&v);
+    gfs_ctx_set *s = nullptr;
+    check(gfs_ctx_set_create(ptrs.data(), ptrs.size(), 0, &s));
+    SetHandle set(s);
+    if (verbose >= 2) {
+        gfs_ctx_set_info info{};
+        check(gfs_ctx_set_get_info(s, &info));
+        std::cerr << "[gfasort_hip] batch: contexts of " << info.items << " graphs built together, " << info.build_ms << " ms, "
+                  << info.launches << " launches\n";
+    }
+    // (last, after everything that can throw: a slot must never hold an item of a set that has already gone)
+    for (size_t k = 0; k < idx.size(); ++k) slots[idx[k]].ctx.reset(gfs_ctx_set_item(s, k));
+    return set;
+}
+
+// Flatten g and create its context, unless open_set has done both, and set the context up with setup(ctx).  Returns what setup
+// returned: on GFS_NOTHING_TO_DO the slot has let go of its context (a context of its own is destroyed, an item stays with its
+// set), otherwise it is resident and `stats` says what it will run.
 template <class Setup>
 static int open_slot(Slot &s, const BidirectedGraph &g, gfs_stats &stats, Setup setup) {
-    s.f = g.flatten();
-    gfs_graph_view v = s.f.view();
-    gfs_ctx *c = nullptr;
-    check(gfs_ctx_create(&v, 0, &c));
-    s.ctx.reset(c);
+    gfs_ctx *c = s.ctx.get();
+    if (!c) {
+        s.f = g.flatten();
+        gfs_graph_view v = s.f.view();
+        check(gfs_ctx_create(&v, 0, &c));
+        s.ctx.reset(c);
+    }
     const int rc = setup(c);
     check(rc);
     if (rc == GFS_NOTHING_TO_DO) s.ctx.reset();
@@ -318,7 +362,9 @@ static void add_batch_stats(gfs_batch_stats &sum, const gfs_batch_stats &one) {
 }
 
 gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbose, const HipOptions &opt, bool keep_positions, bool keep_profile) {
+    SetHandle set;                                                                    // (outlives the slots and the batch)
     std::vector<Slot> slots(items.size());
+    set = open_set(slots, items, opt, verbose, [](size_t) { return true; });
     gfs_batch_stats bs{};
     // reorder the graph by its rank order, keep what was asked for, free the context
     auto apply = [&](size_t i, std::vector<double> &&x, const auto *order, size_t n) {
@@ -409,9 +455,11 @@ Layout path_linear_sgd_layout(const BidirectedGraph &g, const LayoutSGDParams &p
 }
 
 gfs_batch_stats sgd_layout_batch(std::vector<BatchLayoutItem> &items, uint8_t verbose, const HipOptions &opt, bool keep_profile) {
+    SetHandle set;                                                                    // (outlives the slots and the batch)
     std::vector<Slot> slots(items.size());
+    set = open_set(slots, items, opt, verbose, [&](size_t i) { return items[i].params.dimensions == 2 || items[i].params.dimensions == 3; });
     gfs_batch_stats bs{};
-    // a graph that runs alone: the single call, after its context (if any) has left the device
+    // a graph that runs alone: the single call, after the slot has let go of its context (an item of the set stays resident beside it)
     auto finish_alone = [&](size_t i) {
         slots[i].ctx.reset();
         items[i].layout = path_linear_sgd_layout(*items[i].graph, items[i].params, opt, &items[i].stats);

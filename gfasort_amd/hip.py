@@ -101,6 +101,12 @@ class BatchStats(C.Structure):
                 ("term_updates", C.c_uint64), ("attempts", C.c_uint64), ("kernel_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class ContextSetInfo(C.Structure):
+    """gfs_ctx_set_info: launches counts the library's own kernels and memsets one by one and each rocPRIM call as one."""
+    _fields_ = [("items", C.c_uint64), ("total_nodes", C.c_uint64), ("total_steps", C.c_uint64), ("total_paths", C.c_uint64),
+                ("launches", C.c_uint64), ("device_allocations", C.c_uint64), ("arena_bytes", C.c_uint64), ("build_ms", C.c_double)]
+
+
 PAIR_ERROR_DTYPE = np.dtype([("step_distance", "<u8"), ("pairs", "<u8"), ("sum_rel_sq", "<f8"), ("max_rel_sq", "<f8"),
                              ("sum_abs", "<f8"), ("sum_sq", "<f8")])
 
@@ -136,6 +142,7 @@ EXPORTS = [
     "gfs_batch_plan", "gfs_batch_create", "gfs_batch_run", "gfs_batch_get_stats", "gfs_batch_destroy",
     "gfs_batch_result_offsets", "gfs_batch_init_positions", "gfs_batch_results", "gfs_batch_debug_sort_cap",
     "gfs_batch_upload_coords", "gfs_batch_coords", "gfs_batch_pair_errors",
+    "gfs_ctx_set_plan", "gfs_ctx_set_create", "gfs_ctx_set_size", "gfs_ctx_set_item", "gfs_ctx_set_get_info", "gfs_ctx_set_destroy",
 ]
 SEGMENT_SORT_CAP = 8192                # GFS_SEGMENT_SORT_CAP
 
@@ -235,6 +242,15 @@ def lib():
         L.gfs_batch_upload_coords.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.gfs_batch_coords.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.gfs_batch_pair_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gfs_ctx_set_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.gfs_ctx_set_create.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
+        L.gfs_ctx_set_size.argtypes = [C.c_void_p]
+        L.gfs_ctx_set_size.restype = C.c_uint64
+        L.gfs_ctx_set_item.argtypes = [C.c_void_p, C.c_uint64]
+        L.gfs_ctx_set_item.restype = C.c_void_p
+        L.gfs_ctx_set_get_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.gfs_ctx_set_destroy.argtypes = [C.c_void_p]
+        L.gfs_ctx_set_destroy.restype = None
         _lib = L
     return _lib
 
@@ -510,20 +526,25 @@ class Rank:
 class Context:
     """gfs_ctx: the graph's PathIndex mirror, positions and RNG streams resident in HBM."""
 
-    def __init__(self, g, device=0, node_perm=None):
+    def __init__(self, g, device=0, node_perm=None, _borrowed=None):
         self._h = C.c_void_p()
         self.graph = g
+        self.dims = 0
+        self.params = None
+        self.cfg = None
+        self._owns = _borrowed is None
+        if not self._owns:                                     # an item of a ContextSet: the set destroys the handle
+            self._h, self._keep = C.c_void_p(_borrowed), None
+            return
         v, self._keep = make_view(g)
         if node_perm is not None:
             node_perm = np.ascontiguousarray(node_perm, dtype=np.uint32)
         check(lib().gfs_ctx_create_with_layout(C.byref(v), C.c_int(device), _ptr(node_perm), C.byref(self._h)))
-        self.dims = 0
-        self.params = None
-        self.cfg = None
 
     def close(self):
         if self._h:
-            lib().gfs_ctx_destroy(self._h)
+            if self._owns:
+                lib().gfs_ctx_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -696,6 +717,58 @@ class Context:
         b, e = C.c_uint64(0), C.c_uint64(0)
         check(lib().gfs_ctx_phase_window(self._h, C.c_int64(int(set_begin)), C.c_int64(int(set_end)), C.byref(b), C.byref(e)))
         return int(b.value), int(e.value)
+
+
+# ---- context sets: the contexts of many small graphs built in one pass ------------------------------
+def ctx_set_plan(n_nodes, n_steps, n_paths):
+    """gfs_ctx_set_plan (host only): (offsets as a uint64 array of shape (items, 5): step_rec, path_rec, path_len, perm, node_len;
+    arena_bytes)."""
+    nn, ns, npth = (np.ascontiguousarray(a, dtype=np.uint64) for a in (n_nodes, n_steps, n_paths))
+    n = nn.shape[0]
+    if ns.shape[0] != n or npth.shape[0] != n:
+        raise ValueError("one count of each kind per item")
+    off = np.zeros((max(n, 1), 5), dtype=np.uint64)
+    total = C.c_uint64(0)
+    check(lib().gfs_ctx_set_plan(_ptr(nn), _ptr(ns), _ptr(npth), C.c_uint64(n), _ptr(off), C.byref(total)))
+    return off[:n], int(total.value)
+
+
+class ContextSet:
+    """gfs_ctx_set: one Context per graph, all built in one pass over the graphs' disjoint union (allocations, copies and
+    launches do not grow with their number).  .contexts are ordinary Contexts — setup, runs, read-outs, hip.Batch — that do not
+    destroy their handle: close() (or the set's collection) destroys them all, after any Batch made from them."""
+
+    def __init__(self, graphs, device=0):
+        self._h = C.c_void_p()
+        self.contexts = []
+        graphs = list(graphs)
+        n = len(graphs)
+        views, self._keep = [], []
+        for g in graphs:
+            v, keep = make_view(g)
+            views.append(v)
+            self._keep.append(keep)
+        arr = (C.c_void_p * max(n, 1))(*[C.addressof(v) for v in views])
+        check(lib().gfs_ctx_set_create(arr if n else None, C.c_uint64(n), C.c_int(device), C.byref(self._h)))
+        self.contexts = [Context(g, _borrowed=lib().gfs_ctx_set_item(self._h, i)) for i, g in enumerate(graphs)]
+
+    def close(self):
+        if self._h:
+            for c in self.contexts:
+                c.close()
+            lib().gfs_ctx_set_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        out = ContextSetInfo()
+        check(lib().gfs_ctx_set_get_info(self._h, C.byref(out)))
+        return out
 
 
 # ---- batches: many configured contexts in one persistent launch -----------------------------------

@@ -83,6 +83,22 @@ def _refused_item(e):
     return int(named.group(1))
 
 
+SET_MAX_NODES = 16384          # graphs of fewer nodes are a batch's candidates under the default policy: created through one ContextSet
+
+
+def _open_set(graphs, cfgs, wanted, device):
+    """One hip.ContextSet for the graphs a batch can take — wanted(i), fewer than SET_MAX_NODES nodes, and a cfg that asks for
+    bundle 0 (auto) or 1 — so that their contexts cost one build, not one each.  Returns (the set or None, {graph index: its
+    Context}); the caller closes the set after everything made from its contexts."""
+    def bundle(c):
+        return ((int(c.flags) >> 16) & 0xFF) if c is not None else 0
+    idx = [i for i, g in enumerate(graphs) if wanted(i) and 0 < g.n_nodes < SET_MAX_NODES and bundle(cfgs[i]) in (0, 1)]
+    if not idx:
+        return None, {}
+    cset = hip.ContextSet([graphs[i] for i in idx], device=device)
+    return cset, dict(zip(idx, cset.contexts))
+
+
 def _batch_of(held, candidates, max_blocks_per_launch):
     """One hip.Batch of the contexts held[i], i in candidates.  A graph the batch refuses moves to the refused ones, for the
     caller to run alone once the batch has run and is closed, and the others are tried again.  Returns (batch, or None when
@@ -118,12 +134,13 @@ def path_sgd_sort_batch(graphs, params, cfg=None, max_blocks_per_launch: int = 0
 
     out = [None] * len(graphs)
     held = {}                                                  # graph index -> its Context, for the batch's candidates
+    cset, made = _open_set(graphs, cfgs, lambda i: True, device)
     try:
         for i, (g, p, c) in enumerate(zip(graphs, params, cfgs)):
             out[i] = dict(positions=np.zeros(0), order=np.zeros(0, dtype=np.uint64), stats=None, batched=False)
             if g.n_nodes == 0:
                 continue
-            ctx = hip.Context(g, device=device)
+            ctx = made[i] if i in made else hip.Context(g, device=device)
             try:
                 rc = ctx.setup_1d(p, c)
                 if rc != hip.OK:                               # nothing to do
@@ -153,6 +170,8 @@ def path_sgd_sort_batch(graphs, params, cfg=None, max_blocks_per_launch: int = 0
     finally:
         for ctx in held.values():
             ctx.close()
+        if cset is not None:
+            cset.close()
 
 
 def path_linear_sgd_layout_batch(graphs, params, inits=None, cfg=None, max_blocks_per_launch: int = 0, device: int = 0):
@@ -176,12 +195,13 @@ def path_linear_sgd_layout_batch(graphs, params, inits=None, cfg=None, max_block
         out[i] = dict(layout=lay, stats=st, batched=False)
 
     held = {}                                                  # graph index -> its Context, for the batches' candidates
+    cset, made = _open_set(graphs, cfgs, lambda i: params[i].dimensions in (2, 3), device)
     try:
         for i, (g, p, c) in enumerate(zip(graphs, params, cfgs)):
             if g.n_nodes == 0 or p.dimensions not in (2, 3):
                 alone(i)
                 continue
-            ctx = hip.Context(g, device=device)
+            ctx = made[i] if i in made else hip.Context(g, device=device)
             try:
                 rc = ctx.setup_nd(p, c)
                 if rc == hip.OK and ctx.stats().bundle == 1:
@@ -212,3 +232,5 @@ def path_linear_sgd_layout_batch(graphs, params, inits=None, cfg=None, max_block
     finally:
         for ctx in held.values():
             ctx.close()
+        if cset is not None:
+            cset.close()

@@ -447,6 +447,47 @@ int  gfs_batch_coords(gfs_batch *b, double *coords, uint64_t total, double *kern
 int  gfs_batch_pair_errors(gfs_batch *b, const uint64_t *zs, uint64_t n_z, gfs_pair_error *out /*[items][n_z]*/, double *kernel_ms /*nullable*/,
                            void *hip_stream);
 
+/* ---- context sets: the contexts of many small graphs built in one pass ----
+ * gfs_ctx_create costs about the same however small the graph is: a score of allocations, six blocking uploads, three sorts, a scan
+ * and up to 80 fixpoint rounds with a read-back each.  gfs_ctx_set_create builds n contexts from n views in ONE pass over their
+ * disjoint union — one arena for all index arrays, one scratch allocation, one pinned staging buffer; one packed copy up for the
+ * steps, path starts, orientations and the item table and one for the node lengths; one scan, two sorts and two fixpoints over the
+ * union; one copy of all node layouts back — so that allocations, copies and launches do not grow with n.  Everything the build
+ * computes is integer arithmetic, so item i holds, bit for bit, what gfs_ctx_create(graphs[i], device, &c) gives: step records
+ * (padding record included), path records, path lengths, node layout and the host-side facts.  Every entry that takes a gfs_ctx
+ * takes an item: setup, runs, upload and download, the read-outs, gfs_batch_create, the debug hooks.
+ * Ownership: the items belong to the set.  Their index arrays are borrowed from the set's arena; what gfs_ctx_setup_* allocates is
+ * each item's own and goes with it.  gfs_ctx_destroy on an item does nothing; gfs_ctx_set_destroy destroys every item.  The set
+ * must outlive any gfs_batch made from its items.
+ * Errors: gfs_ctx_create's, per item, with a text that begins "set item <i>: " and names the lowest failing item — first the
+ * checks that read only counts (with them GFS_E_UNSUPPORTED where the items TOGETHER pass one context's limits: 2^31-1 nodes,
+ * 2^31-1 paths, 2^40 steps), then those that read path_first_step, all before any device call; a step naming a node its item does
+ * not have is found on the device and gives GFS_E_ARG naming the lowest such item — also in an item of 0 nodes, the one case in
+ * which a set differs from gfs_ctx_create, which does not look at the steps of a graph without nodes.  GFS_E_ARG for null
+ * arguments or n == 0.  On any failure *out is NULL and nothing stays allocated.  There is no node_perm variant. */
+typedef struct gfs_ctx_set gfs_ctx_set;
+typedef struct gfs_ctx_set_info {
+    uint64_t items, total_nodes, total_steps, total_paths;
+    uint64_t launches;            /* of the build: the library's own kernel launches and hipMemsets, counted one by one, plus ONE per
+                                     rocPRIM call (two sorts, one scan: how many kernels each launches is rocPRIM's business and depends
+                                     on the size).  Fixpoint rounds go out four at a time, so the count steps with the longest chain of
+                                     any item, not with the number of items. */
+    uint64_t device_allocations;  /* hipMalloc + hipHostMalloc calls of the build */
+    uint64_t arena_bytes;         /* the one allocation the items' index arrays live in */
+    double   build_ms;            /* wall time inside gfs_ctx_set_create */
+} gfs_ctx_set_info;
+
+/* host only, no device: where item i's five index arrays lie in the arena — offsets[5 * i + k] bytes from its start, k = 0 step
+ * records (n_steps[i] + 1 of 16 B), 1 path records (16 B), 2 path lengths (8 B), 3 node layout (4 B), 4 node lengths (4 B); arrays
+ * of a kind are adjacent, every array starts 256-byte aligned, none overlap.  gfs_ctx_set_create lays its arena out with it. */
+int      gfs_ctx_set_plan(const uint64_t *n_nodes, const uint64_t *n_steps, const uint64_t *n_paths, uint64_t n,
+                          uint64_t *offsets /*[5*n]: step_rec, path_rec, path_len, perm, node_len*/, uint64_t *arena_bytes);
+int      gfs_ctx_set_create(const gfs_graph_view *const *graphs, uint64_t n, int device, gfs_ctx_set **out);
+uint64_t gfs_ctx_set_size(const gfs_ctx_set *s);
+gfs_ctx *gfs_ctx_set_item(gfs_ctx_set *s, uint64_t i);      /* owned by the set; NULL past the end */
+int      gfs_ctx_set_get_info(const gfs_ctx_set *s, gfs_ctx_set_info *out);
+void     gfs_ctx_set_destroy(gfs_ctx_set *s);               /* destroys every item */
+
 /* ---- multi-device runs (no reference equivalent: the reference is one process, src/sgd.rs:413-593) ----
  * Paths are sharded over `world` ranks, one rank per GPU (one process per GPU, or one host thread per GPU); every rank
  * performs its share of an iteration's term updates on its own replica of the positions; after every window of
