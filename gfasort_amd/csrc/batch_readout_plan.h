@@ -1,6 +1,7 @@
-// batch_readout_plan.h — which workgroup of a batch's flat read-out launches works on which item (K4c / K6c, K7g:
-// batch_quality_kernels.hip).  Host only and free of HIP: the kernels take every index from the tables built here, and
-// tests/test_batch_layout_host.py compiles it into a program of its own under the address and undefined-behaviour sanitizers.
+// batch_readout_plan.h — which workgroup, or which wave, of a batch's flat read-out launches works on which item (K4c / K6c, K7g:
+// batch_quality_kernels.hip; K7h / K7i / K7j: batch_diagnosis_kernels.hip), and where an item's rows lie in the packed results.
+// Host only and free of HIP: the kernels take every index from the tables built here, and tests/test_batch_layout_host.py and
+// tests/test_batch_diagnosis_host.py compile it into programs of their own under the address and undefined-behaviour sanitizers.
 #pragma once
 #include <stdint.h>
 
@@ -47,6 +48,42 @@ inline uint64_t coord_plan(const uint64_t *n_nodes, uint64_t n, uint32_t D, uint
 inline void block_item_table(const uint64_t *first_block, uint64_t n, uint32_t *block_item) {
     for (uint64_t i = 0; i < n; ++i)
         for (uint64_t b = first_block[i]; b < first_block[i + 1]; ++b) block_item[b] = (uint32_t)i;
+}
+
+// ---- K7d / K7e and their batch forms K7h / K7i: tiles of Q_TILE consecutive steps, one wave each -----------------------
+// A constant: what a tile yields does not depend on the grid that ran it (quality_kernels.hip).
+constexpr unsigned Q_TILE = 512, Q_TILE_ROUNDS = Q_TILE / 64, Q_TILE_MAX_BLOCKS = 16384;
+inline uint64_t quality_tiles_of(uint64_t n_steps) { return n_steps / Q_TILE + (n_steps % Q_TILE != 0); }
+
+// Item i owns quality_tiles_of(n_steps[i]) consecutive tiles of one flat tile space, none where it has no step.
+// first_tile[0..n]: prefix sums; returns the flat tiles (first_tile[n]).  Flat tile t of item i is the item's LOCAL tile
+// t - first_tile[i]: steps [local * Q_TILE, min(local * Q_TILE + Q_TILE, n_steps[i])) of the item's own table.
+inline uint64_t tile_plan(const uint64_t *n_steps, uint64_t n, uint64_t *first_tile) {
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; ++i) { first_tile[i] = total; total += quality_tiles_of(n_steps[i]); }
+    first_tile[n] = total;
+    return total;
+}
+// tile -> item: tile_item[t] = i for first_tile[i] <= t < first_tile[i + 1]; first_tile[n] entries (read per wave, never searched)
+inline void tile_item_table(const uint64_t *first_tile, uint64_t n, uint32_t *tile_item) { block_item_table(first_tile, n, tile_item); }
+
+// Where item i's rows start in a packed per-path or per-node output: first[0..n], prefix sums of count[0..n); returns the
+// total.  (Over the items' nodes these are gfs_batch_result_offsets; over their paths, gfs_batch_path_offsets.)
+inline uint64_t row_offsets(const uint64_t *count, uint64_t n, uint64_t *first) {
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; ++i) { first[i] = total; total += count[i]; }
+    first[n] = total;
+    return total;
+}
+
+// K7i's packed list of stretched pairs on the device: item i has room for min(cap, n_steps[i]) entries (it has fewer pairs
+// than steps), at first_pair[i]; first_pair[0..n]; returns the entries of all items.
+inline uint64_t stretched_room(uint64_t cap, uint64_t n_steps) { return cap < n_steps ? cap : n_steps; }
+inline uint64_t stretched_list_plan(const uint64_t *n_steps, uint64_t n, uint64_t cap, uint64_t *first_pair) {
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; ++i) { first_pair[i] = total; total += stretched_room(cap, n_steps[i]); }
+    first_pair[n] = total;
+    return total;
 }
 
 }  // namespace gfs

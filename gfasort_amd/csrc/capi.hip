@@ -747,6 +747,11 @@ int gfs::check_step_distances(const uint64_t *zs, uint64_t n_z, const gfs_pair_e
     for (uint64_t k = 0; k < n_z; ++k) if (zs[k] == 0) return fail(GFS_E_ARG, "a step distance of 0");
     return GFS_OK;
 }
+int gfs::check_diagnosis(uint64_t z, double ratio) {
+    if (z == 0) return fail(GFS_E_ARG, "a step distance of 0");
+    if (!(ratio >= 0.0)) return fail(GFS_E_ARG, "ratio must be a number >= 0");
+    return GFS_OK;
+}
 gfs_pair_error gfs::unpack_pair_error(uint64_t z, const uint64_t *w) {
     gfs_pair_error o{};
     o.step_distance = z; o.pairs = w[0];
@@ -855,14 +860,9 @@ int gfs_ctx_sort_quality(gfs_ctx *c, gfs_sort_quality *out) {
 }
 
 // ---- K7d / K7e / K7f: per path, per stretched pair, per node ------------------------------------------------------------
-static int check_diagnosis(uint64_t z, double ratio) {
-    if (z == 0) return fail(GFS_E_ARG, "a step distance of 0");
-    if (!(ratio >= 0.0)) return fail(GFS_E_ARG, "ratio must be a number >= 0");
-    return GFS_OK;
-}
 int gfs_ctx_path_errors(gfs_ctx *c, uint64_t z, double ratio, gfs_path_error *out, uint64_t n_paths, void *hip_stream) {
     if (!c || (!out && n_paths)) return fail(GFS_E_ARG, "null argument");
-    int rc = check_diagnosis(z, ratio);
+    int rc = gfs::check_diagnosis(z, ratio);
     if (rc) return rc;
     if (n_paths != c->n_paths) return fail(GFS_E_ARG, "n_paths does not match the context");
     if (!c->d_x) return fail(GFS_E_STATE, "the context has no positions (not set up)");
@@ -890,7 +890,7 @@ int gfs_ctx_stretched_pairs(gfs_ctx *c, uint64_t z, double ratio, gfs_stretched_
                             void *hip_stream) {
     if (!c || !total || (!out && cap)) return fail(GFS_E_ARG, "null argument");
     *total = 0;
-    int rc = check_diagnosis(z, ratio);
+    int rc = gfs::check_diagnosis(z, ratio);
     if (rc) return rc;
     if (!c->d_x) return fail(GFS_E_STATE, "the context has no positions (not set up)");
     static_assert(sizeof(gfs_stretched_pair) == 5 * 8, "K7e writes gfs_stretched_pair as 5 words");
@@ -915,7 +915,7 @@ int gfs_ctx_stretched_pairs(gfs_ctx *c, uint64_t z, double ratio, gfs_stretched_
 
 int gfs_ctx_node_errors(gfs_ctx *c, uint64_t z, double ratio, gfs_node_error *out, uint64_t n_nodes, void *hip_stream) {
     if (!c || (!out && n_nodes)) return fail(GFS_E_ARG, "null argument");
-    int rc = check_diagnosis(z, ratio);
+    int rc = gfs::check_diagnosis(z, ratio);
     if (rc) return rc;
     if (n_nodes != c->n_nodes) return fail(GFS_E_ARG, "n_nodes does not match the context");
     if (!c->d_x) return fail(GFS_E_STATE, "the context has no positions (not set up)");
@@ -1022,7 +1022,7 @@ int gfs_diagnose(const gfs_graph_view *g, uint64_t dims, const double *positions
                  gfs_path_error *paths_out, gfs_stretched_pair *pairs_out, uint64_t cap, uint64_t *total) {
     if (!g || !total || (!paths_out && g->n_paths) || (!pairs_out && cap)) return fail(GFS_E_ARG, "null argument");
     *total = 0;
-    int rc = check_diagnosis(z, ratio);
+    int rc = gfs::check_diagnosis(z, ratio);
     if (rc) return rc;
     if (dims > GFS_MAX_DIMS) return fail(GFS_E_ARG, "dims must be 0 (1D positions) or 1..8");
     for (uint64_t p = 0; p < g->n_paths; ++p) paths_out[p] = gfs_path_error{};

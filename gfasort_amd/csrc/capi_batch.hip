@@ -1,6 +1,7 @@
 // capi_batch.hip — the batch entries of the C ABI (include/gfasort_hip.h, gfs_batch_*): many configured contexts (capi.hip,
 // capi_ctx.h) in one persistent launch (K1f / K2f, sgd_kernels_batch.hip), and their start positions, read-outs, coordinates and
-// pair errors in one launch each (K4b / K6b, K4c / K6c, K7g).
+// pair errors in one launch each (K4b / K6b, K4c / K6c, K7g), and their diagnosis — errors per path, stretched pairs, errors per node —
+// in a constant number of launches (K7h, K7i, K7j).
 #include "capi_ctx.h"
 #include "sgd_batch.h"
 #include "batch_plan.h"
@@ -41,7 +42,8 @@ struct gfs_batch {
     gfs::Buffer h_packed{true};        // pinned staging of every read-out: copies land here at full rate, whatever the caller's pages are
     gfs::EventPair readout_timer;      // created on first use: start and stop on the stream, read after the synchronise
     // K4c / K6c and K7g (batch_quality_kernels.hip): one device buffer each, [what the host sends | what the kernels write], grown on demand
-    gfs::Buffer d_coords, d_quality;
+    gfs::Buffer d_coords, d_quality;   // (d_quality is also K7h-j's, batch_diagnosis_kernels.hip: tables, scratch, the scan's storage, results)
+    uint64_t tile_blocks = 0;          // gfs_batch_debug_tile_blocks: a cap on K7h's and K7i's grids, 0 = none
 };
 static_assert(GFS_SEGMENT_SORT_CAP == gfs::SEGMENT_SORT_CAP, "the header's cap is the network's");
 
@@ -507,6 +509,178 @@ int gfs_batch_pair_errors(gfs_batch *b, const uint64_t *zs, uint64_t n_z, gfs_pa
     HIPCHK(hipStreamSynchronize(st));
     const uint64_t *w = reinterpret_cast<const uint64_t *>(h + out_at);
     for (uint64_t r = 0; r < n * n_z; ++r) out[r] = gfs::unpack_pair_error(zs[r % n_z], &w[5 * r]);
+    read_kernel_ms(b->readout_timer, kernel_ms);
+    return GFS_OK;
+}
+
+// ---- K7h / K7i / K7j: gfs_ctx_path_errors, gfs_ctx_stretched_pairs and gfs_ctx_node_errors of every item ---------------------------
+// Where every item's tiles, paths, nodes, listed pairs and step-pass workgroups start (batch_readout_plan.h), from the contexts as
+// they are now.
+struct DiagPlan {
+    std::vector<uint64_t> steps, first_tile, first_path, first_node, first_pair, first_block;
+    uint64_t tiles = 0, paths = 0, nodes = 0, pairs = 0, row_blocks = 0;
+};
+static DiagPlan diag_plan(const gfs_batch *b, uint64_t cap) {
+    const uint64_t n = b->ctxs.size();
+    DiagPlan p;
+    std::vector<uint64_t> paths(n), nodes(n);
+    p.steps.resize(n);
+    for (uint64_t i = 0; i < n; ++i) { p.steps[i] = b->ctxs[i]->n_steps; paths[i] = b->ctxs[i]->n_paths; nodes[i] = b->ctxs[i]->n_nodes; }
+    for (std::vector<uint64_t> *v : {&p.first_tile, &p.first_path, &p.first_node, &p.first_pair, &p.first_block}) v->resize(n + 1);
+    p.tiles = gfs::tile_plan(p.steps.data(), n, p.first_tile.data());
+    p.paths = gfs::row_offsets(paths.data(), n, p.first_path.data());
+    p.nodes = gfs::row_offsets(nodes.data(), n, p.first_node.data());
+    p.pairs = gfs::stretched_list_plan(p.steps.data(), n, cap, p.first_pair.data());
+    p.row_blocks = gfs::quality_plan(p.steps.data(), n, p.first_block.data());
+    return p;
+}
+static void diag_items(const gfs_batch *b, const DiagPlan &p, gfs::DiagItem *items) {
+    for (uint64_t i = 0; i < b->ctxs.size(); ++i) {
+        const gfs_ctx *c = b->ctxs[i];
+        items[i] = gfs::DiagItem{c->d_step_rec, c->d_path_rec, c->d_x, c->d_perm, c->n_steps, c->n_nodes, c->n_paths, p.first_tile[i], p.first_path[i],
+                                 p.first_node[i], p.first_pair[i], (uint32_t)p.first_block[i], (uint32_t)(p.first_block[i + 1] - p.first_block[i])};
+    }
+}
+// gfs_ctx_*'s rules for z and ratio, then every item's state; no device call
+static int diag_check(const gfs_batch *b, uint64_t z, double ratio) {
+    int rc = gfs::check_diagnosis(z, ratio);
+    if (rc) return rc;
+    for (size_t i = 0; i < b->ctxs.size(); ++i)
+        if (!b->ctxs[i]->d_x || b->ctxs[i]->dims != b->dims)
+            return fail(GFS_E_STATE, "batch item " + std::to_string(i) + ": the context has no positions (not set up) or is no longer of the batch's dimensions");
+    if (b->ctxs.size() > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, "the batch's items exceed one table");
+    return GFS_OK;
+}
+static uint64_t words8(uint64_t bytes) { return (bytes + 7) / 8 * 8; }
+
+int gfs_batch_path_offsets(const gfs_batch *b, uint64_t *offsets, uint64_t n) {
+    if (!b || !offsets) return fail(GFS_E_ARG, "null argument");
+    if (n != b->ctxs.size() + 1) return fail(GFS_E_ARG, "offsets: need items + 1 entries");
+    offsets[0] = 0;
+    for (size_t i = 0; i < b->ctxs.size(); ++i) offsets[i + 1] = offsets[i] + b->ctxs[i]->n_paths;
+    return GFS_OK;
+}
+
+int gfs_batch_debug_tile_blocks(gfs_batch *b, uint64_t max_blocks) {
+    if (!b) return fail(GFS_E_ARG, "batch is null");
+    b->tile_blocks = max_blocks;
+    return GFS_OK;
+}
+
+int gfs_batch_path_errors(gfs_batch *b, uint64_t z, double ratio, gfs_path_error *out, uint64_t total_paths, double *kernel_ms, void *hip_stream) {
+    if (!b || (!out && total_paths)) return fail(GFS_E_ARG, "null argument");
+    int rc = diag_check(b, z, ratio);
+    if (rc) return rc;
+    const DiagPlan p = diag_plan(b, 0);
+    if (total_paths != p.paths) return fail(GFS_E_ARG, "total_paths is not the batch's path count (gfs_batch_path_offsets)");
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (p.paths == 0) return GFS_OK;
+    static_assert(sizeof(gfs_path_error) == 8 * 8, "K7h writes gfs_path_error as 8 words");
+    const uint64_t n = b->ctxs.size();
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    // device: [DiagItem table | tile table (whole words) | out | head partials | tail partials]; the first two go up in one copy
+    const uint64_t tiles_at = n * sizeof(gfs::DiagItem), out_at = tiles_at + words8(p.tiles * sizeof(uint32_t)), out_bytes = p.paths * sizeof(gfs_path_error);
+    const uint64_t head_at = out_at + out_bytes, tail_at = head_at + 5 * p.tiles * 8, bytes = tail_at + 5 * p.tiles * 8;
+    rc = b->h_packed.reserve(out_at + out_bytes);                          // (staging: the same offsets, less the partials)
+    if (!rc) rc = b->d_quality.reserve(bytes);
+    if (rc) return rc;
+    unsigned char *h = b->h_packed.as<unsigned char>(), *d = b->d_quality.as<unsigned char>();
+    diag_items(b, p, reinterpret_cast<gfs::DiagItem *>(h));
+    gfs::tile_item_table(p.first_tile.data(), n, reinterpret_cast<uint32_t *>(h + tiles_at));
+    HIPCHK(hipMemcpyAsync(d, h, out_at, hipMemcpyHostToDevice, st));
+    HIPCHK(b->readout_timer.start(st));
+    hipError_t e = gfs::batch_path_errors_device(reinterpret_cast<const gfs::DiagItem *>(d), reinterpret_cast<const uint32_t *>(d + tiles_at), (uint32_t)n,
+                                                 p.tiles, p.paths, (uint32_t)b->dims, z, ratio, reinterpret_cast<uint64_t *>(d + head_at),
+                                                 reinterpret_cast<uint64_t *>(d + tail_at), reinterpret_cast<uint64_t *>(d + out_at), b->tile_blocks, st);
+    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch path_errors launch: ") + hipGetErrorString(e));
+    HIPCHK(b->readout_timer.stop(st));
+    HIPCHK(hipMemcpyAsync(h + out_at, d + out_at, out_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::memcpy(out, h + out_at, out_bytes);
+    read_kernel_ms(b->readout_timer, kernel_ms);
+    return GFS_OK;
+}
+
+int gfs_batch_stretched_pairs(gfs_batch *b, uint64_t z, double ratio, gfs_stretched_pair *out, uint64_t cap, uint64_t *totals, double *kernel_ms,
+                              void *hip_stream) {
+    if (!b || !totals || (!out && cap)) return fail(GFS_E_ARG, "null argument");
+    int rc = diag_check(b, z, ratio);
+    if (rc) return rc;
+    const uint64_t n = b->ctxs.size();
+    for (uint64_t i = 0; i < n; ++i) totals[i] = 0;
+    if (kernel_ms) *kernel_ms = 0.0;
+    const DiagPlan p = diag_plan(b, cap);
+    if (p.tiles == 0) return GFS_OK;
+    static_assert(sizeof(gfs_stretched_pair) == 5 * 8, "K7i writes gfs_stretched_pair as 5 words");
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    size_t tmp_bytes = 0;
+    hipError_t e = gfs::batch_stretched_scan_bytes(p.tiles, &tmp_bytes);
+    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch stretched_pairs scan: ") + hipGetErrorString(e));
+    // device: [DiagItem table | tile table (whole words) | tile counts | offsets | list | the scan's storage]; the first two go up in one
+    // copy, offsets and list come back in one
+    const uint64_t tiles_at = n * sizeof(gfs::DiagItem), counts_at = tiles_at + words8(p.tiles * sizeof(uint32_t));
+    const uint64_t offsets_at = counts_at + (p.tiles + 1) * 8, list_at = offsets_at + (p.tiles + 1) * 8;
+    const uint64_t tmp_at = list_at + p.pairs * sizeof(gfs_stretched_pair), bytes = tmp_at + (tmp_bytes ? tmp_bytes : 8);
+    rc = b->h_packed.reserve(tmp_at);                                      // (staging: the same offsets, less the scan's storage)
+    if (!rc) rc = b->d_quality.reserve(bytes);
+    if (rc) return rc;
+    unsigned char *h = b->h_packed.as<unsigned char>(), *d = b->d_quality.as<unsigned char>();
+    diag_items(b, p, reinterpret_cast<gfs::DiagItem *>(h));
+    gfs::tile_item_table(p.first_tile.data(), n, reinterpret_cast<uint32_t *>(h + tiles_at));
+    HIPCHK(hipMemcpyAsync(d, h, counts_at, hipMemcpyHostToDevice, st));
+    HIPCHK(b->readout_timer.start(st));
+    e = gfs::batch_stretched_pairs_device(reinterpret_cast<const gfs::DiagItem *>(d), reinterpret_cast<const uint32_t *>(d + tiles_at), p.tiles,
+                                          (uint32_t)b->dims, z, ratio, reinterpret_cast<uint64_t *>(d + counts_at), reinterpret_cast<uint64_t *>(d + offsets_at),
+                                          p.pairs ? d + list_at : nullptr, cap, d + tmp_at, tmp_bytes, b->tile_blocks, st);
+    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch stretched_pairs launch: ") + hipGetErrorString(e));
+    HIPCHK(b->readout_timer.stop(st));
+    HIPCHK(hipMemcpyAsync(h + offsets_at, d + offsets_at, tmp_at - offsets_at, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t *offsets = reinterpret_cast<const uint64_t *>(h + offsets_at);
+    const gfs_stretched_pair *list = reinterpret_cast<const gfs_stretched_pair *>(h + list_at);
+    for (uint64_t i = 0; i < n; ++i) {
+        totals[i] = offsets[p.first_tile[i + 1]] - offsets[p.first_tile[i]];
+        const uint64_t listed = std::min(std::min(cap, p.steps[i]), totals[i]);
+        if (listed) std::memcpy(out + i * cap, list + p.first_pair[i], listed * sizeof(gfs_stretched_pair));
+    }
+    read_kernel_ms(b->readout_timer, kernel_ms);
+    return GFS_OK;
+}
+
+int gfs_batch_node_errors(gfs_batch *b, uint64_t z, double ratio, gfs_node_error *out, uint64_t total_nodes, double *kernel_ms, void *hip_stream) {
+    if (!b || (!out && total_nodes)) return fail(GFS_E_ARG, "null argument");
+    int rc = diag_check(b, z, ratio);
+    if (rc) return rc;
+    const DiagPlan p = diag_plan(b, 0);
+    if (total_nodes != p.nodes) return fail(GFS_E_ARG, "total_nodes is not the batch's node count (gfs_batch_result_offsets)");
+    if (p.row_blocks > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, "the batch's step tables exceed one launch");
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (p.nodes == 0) return GFS_OK;
+    static_assert(sizeof(gfs_node_error) == 3 * 8, "K7j writes gfs_node_error as 3 words");
+    const uint64_t n = b->ctxs.size();
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    // device: [DiagItem table | block table (whole words) | out | per slot: pairs, stretched, max]; the first two go up in one copy
+    const uint64_t blocks_at = n * sizeof(gfs::DiagItem), out_at = blocks_at + words8(p.row_blocks * sizeof(uint32_t));
+    const uint64_t out_bytes = p.nodes * sizeof(gfs_node_error), slots_at = out_at + out_bytes, bytes = slots_at + out_bytes;
+    rc = b->h_packed.reserve(out_at + out_bytes);                          // (staging: the same offsets, less the slots)
+    if (!rc) rc = b->d_quality.reserve(bytes);
+    if (rc) return rc;
+    unsigned char *h = b->h_packed.as<unsigned char>(), *d = b->d_quality.as<unsigned char>();
+    diag_items(b, p, reinterpret_cast<gfs::DiagItem *>(h));
+    gfs::block_item_table(p.first_block.data(), n, reinterpret_cast<uint32_t *>(h + blocks_at));
+    HIPCHK(hipMemcpyAsync(d, h, out_at, hipMemcpyHostToDevice, st));
+    HIPCHK(b->readout_timer.start(st));
+    hipError_t e = gfs::batch_node_errors_device(reinterpret_cast<const gfs::DiagItem *>(d), reinterpret_cast<const uint32_t *>(d + blocks_at), (uint32_t)n,
+                                                 p.row_blocks, p.nodes, (uint32_t)b->dims, z, ratio, reinterpret_cast<uint64_t *>(d + slots_at),
+                                                 reinterpret_cast<uint64_t *>(d + out_at), st);
+    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch node_errors launch: ") + hipGetErrorString(e));
+    HIPCHK(b->readout_timer.stop(st));
+    HIPCHK(hipMemcpyAsync(h + out_at, d + out_at, out_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::memcpy(out, h + out_at, out_bytes);
     read_kernel_ms(b->readout_timer, kernel_ms);
     return GFS_OK;
 }

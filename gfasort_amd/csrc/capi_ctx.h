@@ -118,6 +118,7 @@ namespace gfs {
 GFS_LOCAL void fill_kargs(const gfs_ctx *c, KArgs &a);
 GFS_LOCAL IterConsts iter_consts(const gfs_ctx *c, uint64_t k);
 GFS_LOCAL int check_step_distances(const uint64_t *zs, uint64_t n_z, const gfs_pair_error *out);
+GFS_LOCAL int check_diagnosis(uint64_t z, double ratio);   // K7d-f and K7h-j: z >= 1, ratio a number >= 0
 // five words of K7a / K7g { pairs, sum_rel_sq, max_rel_sq, sum_abs, sum_sq (f64 bits) } as the ABI's record for step distance z
 GFS_LOCAL gfs_pair_error unpack_pair_error(uint64_t z, const uint64_t *w);
 }  // namespace gfs

@@ -62,7 +62,7 @@ static void usage() {
         "       gfasort_hip --batch LIST -p L [the options above, except -i, -o, --layout-out and those of -p Y]\n"
         "                   (LIST: one in.gfa<TAB>out.gfa<TAB>layout.tsv per line; every graph is laid out as a -i/-o/--layout-out run\n"
         "                    lays it out, the small ones of 2 or 3 dimensions together in one persistent launch, the others alone.\n"
-        "                    With --stress-profile either kind of batch measures its graphs while they are resident)\n"
+        "                    With --stress-profile or --diagnose either kind of batch measures its graphs while they are resident)\n"
         "Pipeline characters: Y = path-guided SGD sort, L = nD layout (HIP engine).\n"
         "g, s, S, u exist in the reference but are not part of this build.\n";
 }
@@ -147,10 +147,10 @@ static void print_stress_profile(const std::vector<gfs_pair_error> &rows) {
 }
 
 // The report of the reference's sgd_diagnostics binary, for the positions a step ended with: z = 1.  f: the graph the positions
-// speak of (dense index); names: its paths'.
+// speak of (dense index); names: its paths'.  resident: the diagnosis, where a batch read it while the graph was resident.
 static void print_diagnosis(const FlatGraph &f, const std::vector<BiPath> &paths, size_t dims, const std::vector<double> &positions,
-                            double ratio) {
-    const LayoutDiagnosis d = layout_diagnosis(f, dims, positions, 1, ratio, 20);
+                            double ratio, const LayoutDiagnosis *resident = nullptr) {
+    const LayoutDiagnosis d = resident ? *resident : layout_diagnosis(f, dims, positions, 1, ratio, 20);
     char buf[512];
     std::cerr << "[gfasort] diagnosis: path orientation and adjacent-step errors\n";
     for (size_t p = 0; p < d.paths.size(); ++p) {
@@ -237,11 +237,12 @@ static void print_batch_stats(const gfs_batch_stats &bs) {
 }
 
 // --stress-profile and --diagnose of the positions a step ended with: x by dense index of f (dims = 0, a sort; f is the graph as
-// it was before the sort reordered it) or Layout.coords.  resident: the profile, where a batch read it while the graph was resident.
+// it was before the sort reordered it) or Layout.coords.  resident, resident_diagnosis: the profile and the diagnosis, where a batch
+// read them while the graph was resident.
 static void print_measures(const Args &args, const FlatGraph &f, const std::vector<BiPath> &paths, size_t dims, const std::vector<double> &x,
-                           const std::vector<gfs_pair_error> *resident = nullptr) {
+                           const std::vector<gfs_pair_error> *resident = nullptr, const LayoutDiagnosis *resident_diagnosis = nullptr) {
     if (args.stress_profile) print_stress_profile(resident ? *resident : layout_pair_errors(f, dims, x, step_distance_ladder(f)));
-    if (args.diagnose) print_diagnosis(f, paths, dims, x, args.diagnose_ratio);
+    if (args.diagnose) print_diagnosis(f, paths, dims, x, args.diagnose_ratio, resident_diagnosis);
 }
 
 static void print_layout_stress(const BidirectedGraph &g, const Layout &layout) {
@@ -305,8 +306,9 @@ static int run_batch(const Args &args) {
     if (args.phased) opt.cfg.flags |= GFS_F_PHASED;                                   // (-p Y only: parse_args)
     const bool measure = args.stress_profile || args.diagnose;
     try {
-        const gfs_batch_stats bs = layouts ? sgd_layout_batch(lays, (uint8_t)args.verbose, opt, args.stress_profile)
-                                           : sgd_sort_batch(sorts, (uint8_t)args.verbose, opt, measure, args.stress_profile);
+        const double diagnose_ratio = args.diagnose ? args.diagnose_ratio : -1.0;
+        const gfs_batch_stats bs = layouts ? sgd_layout_batch(lays, (uint8_t)args.verbose, opt, args.stress_profile, diagnose_ratio)
+                                           : sgd_sort_batch(sorts, (uint8_t)args.verbose, opt, measure, args.stress_profile, diagnose_ratio);
         for (size_t i = 0; i < files.size(); ++i) {
             const bool batched = layouts ? lays[i].batched : sorts[i].batched;
             const gfs_stats &st = layouts ? lays[i].stats : sorts[i].stats;
@@ -319,8 +321,9 @@ static int run_batch(const Args &args) {
             }
             if (!measure || x.empty()) continue;
             const std::vector<gfs_pair_error> *resident = !batched ? nullptr : layouts ? &lays[i].profile : &sorts[i].profile;
-            if (layouts) print_measures(args, graphs[i].flatten(), graphs[i].paths, lays[i].layout.dimensions, x, resident);
-            else print_measures(args, sorts[i].before, graphs[i].paths, 0, x, resident);
+            const LayoutDiagnosis *diagnosis = !batched || !args.diagnose ? nullptr : layouts ? &lays[i].diagnosis : &sorts[i].diagnosis;
+            if (layouts) print_measures(args, graphs[i].flatten(), graphs[i].paths, lays[i].layout.dimensions, x, resident, diagnosis);
+            else print_measures(args, sorts[i].before, graphs[i].paths, 0, x, resident, diagnosis);
         }
         if (args.verbose >= 1) print_batch_stats(bs);
     } catch (const std::exception &e) {

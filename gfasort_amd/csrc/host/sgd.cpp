@@ -356,12 +356,33 @@ static void batch_profiles(gfs_batch *b, const std::vector<Slot> &slots, std::ve
         items[together[k]].profile.assign(rows.begin() + (std::ptrdiff_t)(k * zs.size()), rows.begin() + (std::ptrdiff_t)(k * zs.size() + ladders[k].size()));
 }
 
+// diagnose_ratio >= 0: the diagnosis of every item of a resident batch at z = 1 and cap = 20, what layout_diagnosis gives one graph
+// at a time from a fresh context: one gfs_batch_path_errors and one gfs_batch_stretched_pairs for all of them.
+template <class Item>
+static void batch_diagnoses(gfs_batch *b, std::vector<Item> &items, const std::vector<size_t> &together, double ratio, uint8_t verbose) {
+    const uint64_t cap = 20;
+    std::vector<uint64_t> offsets(together.size() + 1), totals(together.size());
+    check(gfs_batch_path_offsets(b, offsets.data(), offsets.size()));
+    std::vector<gfs_path_error> paths(offsets.back());
+    std::vector<gfs_stretched_pair> pairs(together.size() * cap);
+    check(gfs_batch_path_errors(b, 1, ratio, paths.data(), paths.size(), nullptr, nullptr));
+    check(gfs_batch_stretched_pairs(b, 1, ratio, pairs.data(), cap, totals.data(), nullptr, nullptr));
+    for (size_t k = 0; k < together.size(); ++k) {
+        LayoutDiagnosis &d = items[together[k]].diagnosis;
+        d.paths.assign(paths.begin() + (std::ptrdiff_t)offsets[k], paths.begin() + (std::ptrdiff_t)offsets[k + 1]);
+        d.total = totals[k];
+        d.pairs.assign(pairs.begin() + (std::ptrdiff_t)(k * cap), pairs.begin() + (std::ptrdiff_t)(k * cap + std::min<uint64_t>(cap, totals[k])));
+    }
+    if (verbose >= 1) std::cerr << "[gfasort_hip] batch: diagnosis of " << together.size() << " graphs read while resident\n";
+}
+
 static void add_batch_stats(gfs_batch_stats &sum, const gfs_batch_stats &one) {
     sum.items += one.items; sum.items_run += one.items_run; sum.launches += one.launches; sum.blocks += one.blocks;
     sum.term_updates += one.term_updates; sum.attempts += one.attempts; sum.kernel_ms += one.kernel_ms; sum.total_ms += one.total_ms;
 }
 
-gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbose, const HipOptions &opt, bool keep_positions, bool keep_profile) {
+gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbose, const HipOptions &opt, bool keep_positions, bool keep_profile,
+                               double diagnose_ratio) {
     SetHandle set;                                                                    // (outlives the slots and the batch)
     std::vector<Slot> slots(items.size());
     set = open_set(slots, items, opt, verbose, [](size_t) { return true; });
@@ -392,7 +413,7 @@ gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbos
     std::vector<size_t> together, refused;                                            // indices into items: the batch's candidates
     for (size_t i = 0; i < items.size(); ++i) {
         BatchSortItem &it = items[i];
-        it.stats = gfs_stats{}; it.batched = false; it.positions.clear(); it.profile.clear();
+        it.stats = gfs_stats{}; it.batched = false; it.positions.clear(); it.profile.clear(); it.diagnosis = LayoutDiagnosis{};
         if (!it.graph || it.graph->node_count() == 0) continue;                       // sgd.rs:242-244
         const gfs_sgd_params cp = it.params.to_c();
         if (open_slot(slots[i], *it.graph, it.stats, [&](gfs_ctx *c) { return gfs_ctx_setup_1d(c, &cp, &opt.cfg, nullptr, nullptr); }) == GFS_NOTHING_TO_DO)
@@ -413,6 +434,7 @@ gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbos
         check(gfs_batch_results(b.get(), x.data(), order.data(), offsets.back(), &readout_ms, nullptr));
         if (verbose >= 2) std::cerr << "[gfasort_hip] batch: read-out of " << together.size() << " graphs, " << readout_ms << " ms on the device\n";
         if (keep_profile) batch_profiles(b.get(), slots, items, together);
+        if (diagnose_ratio >= 0.0) batch_diagnoses(b.get(), items, together, diagnose_ratio, verbose);
         b.reset();                                                                    // (before its contexts go)
         for (size_t k = 0; k < together.size(); ++k) {
             items[together[k]].batched = true;
@@ -454,7 +476,7 @@ Layout path_linear_sgd_layout(const BidirectedGraph &g, const LayoutSGDParams &p
     return l;
 }
 
-gfs_batch_stats sgd_layout_batch(std::vector<BatchLayoutItem> &items, uint8_t verbose, const HipOptions &opt, bool keep_profile) {
+gfs_batch_stats sgd_layout_batch(std::vector<BatchLayoutItem> &items, uint8_t verbose, const HipOptions &opt, bool keep_profile, double diagnose_ratio) {
     SetHandle set;                                                                    // (outlives the slots and the batch)
     std::vector<Slot> slots(items.size());
     set = open_set(slots, items, opt, verbose, [&](size_t i) { return items[i].params.dimensions == 2 || items[i].params.dimensions == 3; });
@@ -467,7 +489,7 @@ gfs_batch_stats sgd_layout_batch(std::vector<BatchLayoutItem> &items, uint8_t ve
     std::vector<size_t> candidates;                                                   // indices into items, of either dimension
     for (size_t i = 0; i < items.size(); ++i) {
         BatchLayoutItem &it = items[i];
-        it.stats = gfs_stats{}; it.batched = false; it.profile.clear();
+        it.stats = gfs_stats{}; it.batched = false; it.profile.clear(); it.diagnosis = LayoutDiagnosis{};
         const size_t D = it.params.dimensions;
         it.layout = Layout(D, 0);
         if (!it.graph || it.graph->node_count() == 0) continue;                       // sgd.rs:780-782
@@ -498,6 +520,7 @@ gfs_batch_stats sgd_layout_batch(std::vector<BatchLayoutItem> &items, uint8_t ve
             check(gfs_batch_coords(b.get(), coords.data(), coords.size(), &readout_ms, nullptr));
             if (verbose >= 2) std::cerr << "[gfasort_hip] batch: coordinates of " << together.size() << " graphs, " << readout_ms << " ms on the device\n";
             if (keep_profile) batch_profiles(b.get(), slots, items, together);
+            if (diagnose_ratio >= 0.0) batch_diagnoses(b.get(), items, together, diagnose_ratio, verbose);
             b.reset();                                                                // (before its contexts go)
             for (size_t k = 0; k < together.size(); ++k) {
                 const size_t i = together[k];

@@ -97,6 +97,13 @@ std::vector<Handle> path_sgd_sort(const BidirectedGraph &g, const PathSGDParams 
 // ygs.rs:195 — path_sgd_sort + apply_ordering.
 void sgd_sort_only(BidirectedGraph &g, const PathSGDParams &p, uint8_t verbose, const HipOptions &opt = {},
                    gfs_stats *stats = nullptr, std::vector<double> *positions_out = nullptr);
+// Which paths and pairs carry the error at step distance z (gfs_diagnose): one gfs_path_error per path, and the first `cap` of the
+// pairs (s, s + z) whose layout distance is more than `ratio` times their path distance, in step order, with their exact total.
+struct LayoutDiagnosis {
+    std::vector<gfs_path_error> paths;
+    std::vector<gfs_stretched_pair> pairs;
+    uint64_t total = 0;
+};
 // sgd_sort_only over MANY graphs (no reference equivalent; gfasort_hip --batch).  Graphs for which the policy picks reference streams
 // (fewer than 16384 nodes) run together as one gfs_batch — one persistent launch, or as few as fit the device —, the others alone,
 // one after the other; every graph is then reordered exactly as sgd_sort_only reorders it.  A graph that gfs_batch_create refuses
@@ -110,12 +117,16 @@ struct BatchSortItem {
     FlatGraph before;                      // keep_positions: the graph as it was flattened before the sort ...
     std::vector<double> positions;         // ... and the final positions by its dense index; empty where there was nothing to do
     std::vector<gfs_pair_error> profile;   // keep_profile, batched graphs: layout_pair_errors at step_distance_ladder, read while resident
+    LayoutDiagnosis diagnosis;             // diagnose_ratio >= 0, batched graphs: layout_diagnosis(before, 0, positions, 1, ratio, 20), read while resident
 };
 // Returns the batch's figures (all zero where no graph was batched).  Throws std::runtime_error on a HIP / argument error.
 // keep_profile: the batched graphs' pair errors at their step_distance_ladder are read from the batch while it is resident
 // (gfs_batch_pair_errors: one call for all of them), the figures layout_pair_errors gives for the kept positions.
+// diagnose_ratio >= 0 (either driver): the batched graphs' diagnosis at z = 1, that ratio and cap = 20 is read from the batch while it
+// is resident (gfs_batch_path_errors, gfs_batch_stretched_pairs: one call each for all of them), what layout_diagnosis gives for the
+// final positions; negative: not asked for.
 gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbose, const HipOptions &opt = {}, bool keep_positions = false,
-                               bool keep_profile = false);
+                               bool keep_profile = false, double diagnose_ratio = -1.0);
 // path_linear_sgd_layout over MANY graphs (no reference equivalent; gfasort_hip --batch -p L), the layout twin of sgd_sort_batch.
 // Every graph gets its own parameters and its own default_layout_init.  Graphs of 2 or 3 dimensions for which the policy picks
 // the pooled reference-stream kernel (stats.bundle == 1) run together, one gfs_batch per dimension: all start coordinates up
@@ -129,9 +140,11 @@ struct BatchLayoutItem {
     gfs_stats stats{};                     // the graph's own (a batched graph's kernel_ms is the batch's: 0 here)
     bool batched = false;
     std::vector<gfs_pair_error> profile;   // keep_profile, batched graphs: as BatchSortItem::profile, of the final coordinates
+    LayoutDiagnosis diagnosis;             // diagnose_ratio >= 0, batched graphs: as BatchSortItem::diagnosis, of the final coordinates
 };
 // Returns the batches' figures, summed where both dimensions had one (all zero where no graph was batched).
-gfs_batch_stats sgd_layout_batch(std::vector<BatchLayoutItem> &items, uint8_t verbose, const HipOptions &opt = {}, bool keep_profile = false);
+gfs_batch_stats sgd_layout_batch(std::vector<BatchLayoutItem> &items, uint8_t verbose, const HipOptions &opt = {}, bool keep_profile = false,
+                                 double diagnose_ratio = -1.0);
 // Which of the n contexts handed to gfs_batch_create its refusal names: rc is what the call returned and why its
 // gfs_last_error(), which reads "batch item K: ..." for a GFS_E_UNSUPPORTED.  Any other code, a text that names no item and a K
 // outside [0, n) are the library's error as it stands: thrown as std::runtime_error.  Both batch drivers read refusals through
@@ -153,13 +166,6 @@ std::vector<gfs_pair_error> layout_pair_errors(const FlatGraph &f, size_t dims, 
 std::vector<gfs_pair_error> layout_pair_errors(const BidirectedGraph &g, const Layout &layout, const std::vector<uint64_t> &zs);
 std::vector<gfs_pair_error> layout_pair_errors(const BidirectedGraph &g, const std::vector<double> &positions,
                                                const std::vector<uint64_t> &zs);
-// Which paths and pairs carry the error at step distance z (gfs_diagnose): one gfs_path_error per path, and the first `cap` of the
-// pairs (s, s + z) whose layout distance is more than `ratio` times their path distance, in step order, with their exact total.
-struct LayoutDiagnosis {
-    std::vector<gfs_path_error> paths;
-    std::vector<gfs_stretched_pair> pairs;
-    uint64_t total = 0;
-};
 LayoutDiagnosis layout_diagnosis(const FlatGraph &f, size_t dims, const std::vector<double> &positions, uint64_t z = 1,
                                  double ratio = 10.0, uint64_t cap = 20);
 // z = 1, 2, 3, 4, 6, 8, 12, 16, ...: every 2^k and 3 * 2^(k-1) below the longest path's step count

@@ -1,8 +1,9 @@
-// quality_device.h — the device functions K7 (quality_kernels.hip) and K7g (batch_quality_kernels.hip) share: the one per-pair
-// function and the fixed-tree reduction of a workgroup's five fields.  One text for both units, so that a batch's figures
-// are the per-item call's bit for bit.
+// quality_device.h — the device functions K7 (quality_kernels.hip) and its batch forms K7g (batch_quality_kernels.hip) and
+// K7h-j (batch_diagnosis_kernels.hip) share: the one per-pair function, the fixed-tree reduction of a workgroup's five fields,
+// and what a wave does with one tile, one path or one pair in K7d-f.  One text for all units, so that a batch's figures are
+// the per-item call's bit for bit.
 #pragma once
-#include "batch_readout_plan.h"                           // Q_BLOCK, Q_PAIRS_PER_THREAD, Q_MAX_BLOCKS
+#include "batch_readout_plan.h"                           // Q_BLOCK, Q_PAIRS_PER_THREAD, Q_MAX_BLOCKS, Q_TILE, Q_TILE_ROUNDS
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -72,6 +73,182 @@ __device__ __forceinline__ void store_block_partials(uint64_t (&v)[5], uint64_t 
             for (unsigned w = 1; w < Q_BLOCK / 64; ++w) t = combine(F::op(f), t, wave_part[w][f]);
             partials[((uint64_t)f * n_z + zi) * gridDim.x + blockIdx.x] = t;
         }
+    }
+}
+
+// ---- K7d / K7e / K7f and K7h / K7i / K7j: which paths, pairs and nodes carry the error ------------------------------------
+// The per-pair value is pair_error's; a counted pair is STRETCHED when d_layout / d_path > ratio, d_layout = err + d_path.
+// The bodies below are what ONE wave does with ONE tile (K7d, K7e), one path (K7d's combine) or one thread with one pair
+// (K7f): quality_kernels.hip hands them the tiles of one graph, batch_diagnosis_kernels.hip the LOCAL tiles of every item of a
+// batch on the item's own tables — one text, so that an item's rows are its own call's bit for bit.
+static constexpr uint32_t Q_NO_PATH = 0xFFFFFFFFu;                       // (a record's path has 31 bits)
+
+struct StretchedPair { uint64_t step_a, step_b, path; double d_path, d_layout; };    // = gfs_stretched_pair
+
+__device__ __forceinline__ bool pair_stretch(const uint4 ra, const uint4 rb, const double *x, const uint64_t n_nodes, const uint32_t dims,
+                                             const double ratio, double &err, double &rel_sq, double &d_path, double &d_layout,
+                                             bool &stretched) {
+    if (!pair_error(ra, rb, x, n_nodes, dims, err, rel_sq)) return false;
+    d_path = fabs((double)rec_pos(ra) - (double)rec_pos(rb));              // pair_error's own d_path
+    d_layout = err + d_path;
+    stretched = d_layout / d_path > ratio;
+    return true;
+}
+
+// ---- K7d ------------------------------------------------------------------------------------------------------------------
+// A step's contribution is five words combined as PairFields combines them: { steps | reverse_steps << 16 | pairs << 32 |
+// stretched << 48 (a tile has 512 steps: no counter leaves its 16 bits), sum_rel_sq, max_rel_sq, sum_abs, sum_sq }.
+// Per round a segmented inclusive scan over the wave (Hillis-Steele with shuffles, a fixed tree; the steps of a path are
+// one run, so "same path at distance off" means the same segment) after lane 0 took over the sum its path carried out of the
+// round before.  The lane on a path's LAST step holds the path's sum over the tile: where the path also began inside the
+// tile it is the path's result and is written as such; otherwise it is the tile's HEAD partial (the path of the tile's
+// first step).  The lane on the tile's last step, where its path goes on, stores the HEAD partial (a path that began at
+// or before the tile's first step) or the TAIL partial.  Every partial that K7d's second kernel reads is written by the
+// first one in the same call.
+__device__ __forceinline__ void store_path_error(uint64_t *out, const uint64_t p, const uint64_t (&cnt)[4], const uint64_t (&v)[5]) {
+    uint64_t *o = out + p * 8;                                             // = gfs_path_error
+    o[0] = cnt[0]; o[1] = cnt[1]; o[2] = cnt[2];
+    o[3] = v[1]; o[4] = v[2]; o[5] = v[3]; o[6] = v[4];
+    o[7] = cnt[3];
+}
+__device__ __forceinline__ void add_tile_counters(uint64_t (&cnt)[4], const uint64_t packed) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cnt[k] += (packed >> (16 * k)) & 0xFFFFu;
+}
+
+// One wave, tile `tile` of a table of n_steps steps: head / tail partials at tile * 5, rows of paths inside the tile at out.
+__device__ __forceinline__ void path_tile(const uint4 *step_rec, const uint64_t n_steps, const double *x, const uint64_t n_nodes,
+                                          const uint32_t dims, const uint64_t z, const double ratio, const uint64_t tile, const unsigned lane,
+                                          uint64_t *head, uint64_t *tail, uint64_t *out) {
+    const uint64_t lo = tile * Q_TILE, hi = lo + Q_TILE < n_steps ? lo + Q_TILE : n_steps;
+    const uint32_t first_path = rec_path(step_rec[lo]);
+    const bool head_open = lo > 0 && rec_path(step_rec[lo - 1]) == first_path;     // the first step's path began before the tile
+    bool carried = false;
+    uint64_t carry[5] = {0, 0, 0, 0, 0};
+    for (unsigned r = 0; r < Q_TILE_ROUNDS; ++r) {
+        const uint64_t s = lo + (uint64_t)r * 64 + lane;
+        uint32_t key = Q_NO_PATH, next = Q_NO_PATH;
+        uint64_t v[5] = {0, 0, 0, 0, 0};
+        if (s < hi) {
+            const uint4 ra = step_rec[s];
+            key = rec_path(ra);
+            if (s + 1 < n_steps) next = rec_path(step_rec[s + 1]);
+            v[0] = 1ull | ((uint64_t)(ra.y >> 31) << 16);
+            double err, rel, dp, dl;
+            bool st;
+            if (z < n_steps && s < n_steps - z && pair_stretch(ra, step_rec[s + z], x, n_nodes, dims, ratio, err, rel, dp, dl, st)) {
+                v[0] |= (1ull << 32) | ((uint64_t)st << 48);
+                v[1] = (uint64_t)__double_as_longlong(rel); v[2] = v[1];
+                v[3] = (uint64_t)__double_as_longlong(fabs(err)); v[4] = (uint64_t)__double_as_longlong(err * err);
+            }
+        }
+        if (lane == 0 && carried)
+#pragma unroll
+            for (int f = 0; f < 5; ++f) v[f] = combine(PairFields::op(f), carry[f], v[f]);
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t ku = (uint32_t)__shfl_up((int)key, off, 64);
+            const bool take = lane >= (unsigned)off && ku == key;
+#pragma unroll
+            for (int f = 0; f < 5; ++f) {
+                const uint64_t u = (uint64_t)__shfl_up((unsigned long long)v[f], off, 64);
+                if (take) v[f] = combine(PairFields::op(f), u, v[f]);
+            }
+        }
+        if (s < hi) {
+            if (next != key) {                                          // the path's last step
+                if (key == first_path && head_open) {
+#pragma unroll
+                    for (int f = 0; f < 5; ++f) head[tile * 5 + f] = v[f];
+                } else {
+                    uint64_t cnt[4] = {0, 0, 0, 0};
+                    add_tile_counters(cnt, v[0]);
+                    store_path_error(out, key, cnt, v);
+                }
+            } else if (s + 1 == hi) {                                   // the tile's last step, the path goes on
+                uint64_t *part = key == first_path ? head : tail;
+#pragma unroll
+                for (int f = 0; f < 5; ++f) part[tile * 5 + f] = v[f];
+            }
+        }
+        // lane 63's path goes on in the next round (all lanes agree: the values are lane 63's)
+        carried = __shfl((int)(s < hi && next == key), 63, 64) != 0;
+#pragma unroll
+        for (int f = 0; f < 5; ++f) carry[f] = (uint64_t)__shfl((unsigned long long)v[f], 63, 64);
+    }
+}
+
+// One wave, path p of a table whose record is pr = { first step lo, steps, -, first step hi }: the partials of the tiles the
+// path crosses, folded IN TILE ORDER (64 tiles are loaded at a time, one per lane, and taken in lane order; every lane folds
+// the same values).  A path inside one tile was written by the tile pass and is left alone; a path without steps gets zeros.
+__device__ __forceinline__ void path_fold(const uint4 pr, const uint64_t p, const unsigned lane, const uint64_t *head, const uint64_t *tail,
+                                          uint64_t *out) {
+    const uint64_t b = (uint64_t)pr.x | ((uint64_t)pr.w << 32), cnt = pr.y;
+    uint64_t acc[5] = {0, 0, 0, 0, 0}, counters[4] = {0, 0, 0, 0};      // (16 bits hold a tile's counters, not a path's)
+    if (cnt) {
+        const uint64_t tb = b / Q_TILE, te = (b + cnt - 1) / Q_TILE;
+        if (tb == te) return;
+        for (uint64_t base = tb; base <= te; base += 64) {
+            const uint64_t t = base + lane;
+            const unsigned n = te - base + 1 < 64 ? (unsigned)(te - base + 1) : 64u;
+            uint64_t v[5] = {0, 0, 0, 0, 0};
+            if (t <= te) {
+                const uint64_t *part = (t == tb && b % Q_TILE != 0) ? tail : head;
+#pragma unroll
+                for (int f = 0; f < 5; ++f) v[f] = part[t * 5 + f];
+            }
+            for (unsigned l = 0; l < n; ++l) {
+                add_tile_counters(counters, (uint64_t)__shfl((unsigned long long)v[0], (int)l, 64));
+#pragma unroll
+                for (int f = 1; f < 5; ++f)
+                    acc[f] = combine(PairFields::op(f), acc[f], (uint64_t)__shfl((unsigned long long)v[f], (int)l, 64));
+            }
+        }
+    }
+    if (lane == 0) store_path_error(out, p, counters, acc);
+}
+
+// ---- K7e ------------------------------------------------------------------------------------------------------------------
+// One wave, tile `tile`: its stretched pairs are counted (ballots); with a list, pair number at + (stretched pairs before it
+// in the tile) is written where that is < cap.  Returns `at` advanced by the tile's stretched pairs (all lanes agree).
+__device__ __forceinline__ uint64_t stretched_tile(const uint4 *step_rec, const uint64_t n_steps, const double *x, const uint64_t n_nodes,
+                                                   const uint32_t dims, const uint64_t z, const double ratio, const uint64_t tile,
+                                                   const unsigned lane, uint64_t at, StretchedPair *list, const uint64_t cap) {
+    const uint64_t lo = tile * Q_TILE, hi = lo + Q_TILE < n_steps ? lo + Q_TILE : n_steps;
+    for (unsigned r = 0; r < Q_TILE_ROUNDS; ++r) {
+        const uint64_t s = lo + (uint64_t)r * 64 + lane;
+        double err, rel, dp = 0.0, dl = 0.0;
+        bool st = false;
+        uint4 ra = make_uint4(0, 0, 0, 0);
+        if (s < hi && z < n_steps && s < n_steps - z) {
+            ra = step_rec[s];
+            if (!pair_stretch(ra, step_rec[s + z], x, n_nodes, dims, ratio, err, rel, dp, dl, st)) st = false;
+        }
+        const unsigned long long m = __ballot(st);
+        if (list && st) {
+            const uint64_t k = at + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
+            if (k < cap) list[k] = StretchedPair{s, s + z, (uint64_t)rec_path(ra), dp, dl};
+        }
+        at += (uint64_t)__popcll(m);
+    }
+    return at;
+}
+
+// ---- K7f ------------------------------------------------------------------------------------------------------------------
+// One thread, a counted pair (ra, rb) of relative error rel_sq.  Per node SLOT: pairs and stretched pairs that touch the node
+// (integer atomic adds; a pair from a node to itself counts once) and the largest rel_sq (unsigned 64-bit atomic max on the
+// bits of the non-negative double: same order as the values).  Sums of integers and a maximum do not depend on the order of
+// arrival.  The maximum only grows, so a plain load that already shows a value >= ours, however stale, makes the atomic
+// unnecessary.
+__device__ __forceinline__ void node_pair(const uint4 ra, const uint4 rb, const double rel_sq, const bool st, unsigned long long *pairs,
+                                          unsigned long long *stretched, unsigned long long *max_bits) {
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(rel_sq);
+    const uint32_t ends[2] = {ra.x, rb.x};
+    for (int k = 0; k < (ra.x == rb.x ? 1 : 2); ++k) {
+        const uint32_t slot = ends[k];
+        atomicAdd(&pairs[slot], 1ull);
+        if (st) atomicAdd(&stretched[slot], 1ull);
+        if (max_bits[slot] < bits) atomicMax(&max_bits[slot], bits);
     }
 }
 

@@ -173,145 +173,29 @@ hipError_t sort_quality_device(const uint4 *d_step_rec, uint64_t n_steps, const 
 //
 // Decomposition (K7d, K7e): the step table is cut into TILES of Q_TILE consecutive steps, a constant; one wave works a tile
 // off in Q_TILE / 64 rounds of 64 consecutive steps, so what a tile yields does not depend on the grid that ran it.  A pair
-// (s, s + z) belongs to the tile and to the path of s.
-static constexpr unsigned Q_TILE = 512, Q_TILE_ROUNDS = Q_TILE / 64, Q_TILE_MAX_BLOCKS = 16384;
-static constexpr uint32_t Q_NO_PATH = 0xFFFFFFFFu;                       // (a record's path has 31 bits)
-
-uint64_t quality_tiles(uint64_t n_steps) { return (n_steps + Q_TILE - 1) / Q_TILE; }
+// (s, s + z) belongs to the tile and to the path of s.  Q_TILE and the tile count: batch_readout_plan.h; what a wave does with
+// a tile, a path or a pair (pair_stretch, path_tile, path_fold, stretched_tile, node_pair): quality_device.h, shared with K7h-j.
+uint64_t quality_tiles(uint64_t n_steps) { return quality_tiles_of(n_steps); }
 static unsigned tile_blocks(uint64_t n_steps) {
     const uint64_t b = (quality_tiles(n_steps) + Q_BLOCK / 64 - 1) / (Q_BLOCK / 64);
     return (unsigned)(b < 1 ? 1 : (b > Q_TILE_MAX_BLOCKS ? Q_TILE_MAX_BLOCKS : b));
 }
 
-struct StretchedPair { uint64_t step_a, step_b, path; double d_path, d_layout; };    // = gfs_stretched_pair
-
-__device__ __forceinline__ bool pair_stretch(const uint4 ra, const uint4 rb, const double *x, const uint64_t n_nodes, const uint32_t dims,
-                                             const double ratio, double &err, double &rel_sq, double &d_path, double &d_layout,
-                                             bool &stretched) {
-    if (!pair_error(ra, rb, x, n_nodes, dims, err, rel_sq)) return false;
-    d_path = fabs((double)rec_pos(ra) - (double)rec_pos(rb));              // pair_error's own d_path
-    d_layout = err + d_path;
-    stretched = d_layout / d_path > ratio;
-    return true;
-}
-
 // ---- K7d ------------------------------------------------------------------------------------------------------------------
-// A step's contribution is five words combined as PairFields combines them: { steps | reverse_steps << 16 | pairs << 32 |
-// stretched << 48 (a tile has 512 steps: no counter leaves its 16 bits), sum_rel_sq, max_rel_sq, sum_abs, sum_sq }.
-// Per round a segmented inclusive scan over the wave (Hillis-Steele with shuffles, a fixed tree; the steps of a path are
-// one run, so "same path at distance off" means the same segment) after lane 0 took over the sum its path carried out of the
-// round before.  The lane on a path's LAST step holds the path's sum over the tile: where the path also began inside the
-// tile it is the path's result and is written as such; otherwise it is the tile's HEAD partial (the path of the tile's
-// first step).  The lane on the tile's last step, where its path goes on, stores the HEAD partial (a path that began at
-// or before the tile's first step) or the TAIL partial.  Every partial that K7d's second kernel reads is written by the
-// first one in the same call.
-__device__ __forceinline__ void store_path_error(uint64_t *out, const uint64_t p, const uint64_t (&cnt)[4], const uint64_t (&v)[5]) {
-    uint64_t *o = out + p * 8;                                             // = gfs_path_error
-    o[0] = cnt[0]; o[1] = cnt[1]; o[2] = cnt[2];
-    o[3] = v[1]; o[4] = v[2]; o[5] = v[3]; o[6] = v[4];
-    o[7] = cnt[3];
-}
-__device__ __forceinline__ void add_tile_counters(uint64_t (&cnt)[4], const uint64_t packed) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) cnt[k] += (packed >> (16 * k)) & 0xFFFFu;
-}
-
 __global__ void __launch_bounds__(Q_BLOCK) path_tiles_kernel(const uint4 *step_rec, const uint64_t n_steps, const double *x, const uint64_t n_nodes,
                                                              const uint32_t dims, const uint64_t z, const double ratio, const uint64_t n_tiles,
                                                              uint64_t *head, uint64_t *tail, uint64_t *out) {
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint64_t tile = (uint64_t)blockIdx.x * (Q_BLOCK / 64) + wave; tile < n_tiles; tile += (uint64_t)gridDim.x * (Q_BLOCK / 64)) {
-        const uint64_t lo = tile * Q_TILE, hi = lo + Q_TILE < n_steps ? lo + Q_TILE : n_steps;
-        const uint32_t first_path = rec_path(step_rec[lo]);
-        const bool head_open = lo > 0 && rec_path(step_rec[lo - 1]) == first_path;     // the first step's path began before the tile
-        bool carried = false;
-        uint64_t carry[5] = {0, 0, 0, 0, 0};
-        for (unsigned r = 0; r < Q_TILE_ROUNDS; ++r) {
-            const uint64_t s = lo + (uint64_t)r * 64 + lane;
-            uint32_t key = Q_NO_PATH, next = Q_NO_PATH;
-            uint64_t v[5] = {0, 0, 0, 0, 0};
-            if (s < hi) {
-                const uint4 ra = step_rec[s];
-                key = rec_path(ra);
-                if (s + 1 < n_steps) next = rec_path(step_rec[s + 1]);
-                v[0] = 1ull | ((uint64_t)(ra.y >> 31) << 16);
-                double err, rel, dp, dl;
-                bool st;
-                if (z < n_steps && s < n_steps - z && pair_stretch(ra, step_rec[s + z], x, n_nodes, dims, ratio, err, rel, dp, dl, st)) {
-                    v[0] |= (1ull << 32) | ((uint64_t)st << 48);
-                    v[1] = (uint64_t)__double_as_longlong(rel); v[2] = v[1];
-                    v[3] = (uint64_t)__double_as_longlong(fabs(err)); v[4] = (uint64_t)__double_as_longlong(err * err);
-                }
-            }
-            if (lane == 0 && carried)
-#pragma unroll
-                for (int f = 0; f < 5; ++f) v[f] = combine(PairFields::op(f), carry[f], v[f]);
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t ku = (uint32_t)__shfl_up((int)key, off, 64);
-                const bool take = lane >= (unsigned)off && ku == key;
-#pragma unroll
-                for (int f = 0; f < 5; ++f) {
-                    const uint64_t u = (uint64_t)__shfl_up((unsigned long long)v[f], off, 64);
-                    if (take) v[f] = combine(PairFields::op(f), u, v[f]);
-                }
-            }
-            if (s < hi) {
-                if (next != key) {                                          // the path's last step
-                    if (key == first_path && head_open) {
-#pragma unroll
-                        for (int f = 0; f < 5; ++f) head[tile * 5 + f] = v[f];
-                    } else {
-                        uint64_t cnt[4] = {0, 0, 0, 0};
-                        add_tile_counters(cnt, v[0]);
-                        store_path_error(out, key, cnt, v);
-                    }
-                } else if (s + 1 == hi) {                                   // the tile's last step, the path goes on
-                    uint64_t *part = key == first_path ? head : tail;
-#pragma unroll
-                    for (int f = 0; f < 5; ++f) part[tile * 5 + f] = v[f];
-                }
-            }
-            // lane 63's path goes on in the next round (all lanes agree: the values are lane 63's)
-            carried = __shfl((int)(s < hi && next == key), 63, 64) != 0;
-#pragma unroll
-            for (int f = 0; f < 5; ++f) carry[f] = (uint64_t)__shfl((unsigned long long)v[f], 63, 64);
-        }
-    }
+    for (uint64_t tile = (uint64_t)blockIdx.x * (Q_BLOCK / 64) + wave; tile < n_tiles; tile += (uint64_t)gridDim.x * (Q_BLOCK / 64))
+        path_tile(step_rec, n_steps, x, n_nodes, dims, z, ratio, tile, lane, head, tail, out);
 }
 
-// One wave per path: the partials of the tiles a path crosses, folded IN TILE ORDER (64 tiles are loaded at a time, one per
-// lane, and taken in lane order; every lane folds the same values).  A path inside one tile was written by the tile pass;
-// a path without steps gets zeros.  path_rec: { first step lo, steps, -, first step hi }.
+// One wave per path (path_fold).  path_rec: { first step lo, steps, -, first step hi }.
 __global__ void __launch_bounds__(Q_BLOCK) path_combine_kernel(const uint4 *path_rec, const uint64_t n_paths, const uint64_t *head,
                                                                const uint64_t *tail, uint64_t *out) {
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint64_t p = (uint64_t)blockIdx.x * (Q_BLOCK / 64) + wave; p < n_paths; p += (uint64_t)gridDim.x * (Q_BLOCK / 64)) {
-        const uint4 pr = path_rec[p];
-        const uint64_t b = (uint64_t)pr.x | ((uint64_t)pr.w << 32), cnt = pr.y;
-        uint64_t acc[5] = {0, 0, 0, 0, 0}, counters[4] = {0, 0, 0, 0};      // (16 bits hold a tile's counters, not a path's)
-        if (cnt) {
-            const uint64_t tb = b / Q_TILE, te = (b + cnt - 1) / Q_TILE;
-            if (tb == te) continue;
-            for (uint64_t base = tb; base <= te; base += 64) {
-                const uint64_t t = base + lane;
-                const unsigned n = te - base + 1 < 64 ? (unsigned)(te - base + 1) : 64u;
-                uint64_t v[5] = {0, 0, 0, 0, 0};
-                if (t <= te) {
-                    const uint64_t *part = (t == tb && b % Q_TILE != 0) ? tail : head;
-#pragma unroll
-                    for (int f = 0; f < 5; ++f) v[f] = part[t * 5 + f];
-                }
-                for (unsigned l = 0; l < n; ++l) {
-                    add_tile_counters(counters, (uint64_t)__shfl((unsigned long long)v[0], (int)l, 64));
-#pragma unroll
-                    for (int f = 1; f < 5; ++f)
-                        acc[f] = combine(PairFields::op(f), acc[f], (uint64_t)__shfl((unsigned long long)v[f], (int)l, 64));
-                }
-            }
-        }
-        if (lane == 0) store_path_error(out, p, counters, acc);
-    }
+    for (uint64_t p = (uint64_t)blockIdx.x * (Q_BLOCK / 64) + wave; p < n_paths; p += (uint64_t)gridDim.x * (Q_BLOCK / 64))
+        path_fold(path_rec[p], p, lane, head, tail, out);
 }
 
 // d_head, d_tail: 5 * quality_tiles(n_steps) words each; d_out: n_paths gfs_path_error (8 words each).  Asynchronous on st.
@@ -338,25 +222,9 @@ __global__ void __launch_bounds__(Q_BLOCK) stretched_tiles_kernel(const uint4 *s
                                                                   uint64_t *counts, const uint64_t *offsets, StretchedPair *list, const uint64_t cap) {
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint64_t tile = (uint64_t)blockIdx.x * (Q_BLOCK / 64) + wave; tile < n_tiles; tile += (uint64_t)gridDim.x * (Q_BLOCK / 64)) {
-        const uint64_t lo = tile * Q_TILE, hi = lo + Q_TILE < n_steps ? lo + Q_TILE : n_steps;
         uint64_t at = list ? offsets[tile] : 0;                             // number of the tile's next stretched pair
         if (list && at >= cap) continue;
-        for (unsigned r = 0; r < Q_TILE_ROUNDS; ++r) {
-            const uint64_t s = lo + (uint64_t)r * 64 + lane;
-            double err, rel, dp = 0.0, dl = 0.0;
-            bool st = false;
-            uint4 ra = make_uint4(0, 0, 0, 0);
-            if (s < hi && z < n_steps && s < n_steps - z) {
-                ra = step_rec[s];
-                if (!pair_stretch(ra, step_rec[s + z], x, n_nodes, dims, ratio, err, rel, dp, dl, st)) st = false;
-            }
-            const unsigned long long m = __ballot(st);
-            if (list && st) {
-                const uint64_t k = at + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
-                if (k < cap) list[k] = StretchedPair{s, s + z, (uint64_t)rec_path(ra), dp, dl};
-            }
-            at += (uint64_t)__popcll(m);
-        }
+        at = stretched_tile(step_rec, n_steps, x, n_nodes, dims, z, ratio, tile, lane, at, list, cap);
         if (!list && lane == 0) counts[tile] = at;
     }
 }
@@ -392,10 +260,7 @@ hipError_t stretched_pairs_device(const uint4 *d_step_rec, uint64_t n_steps, con
 }
 
 // ---- K7f ------------------------------------------------------------------------------------------------------------------
-// Per node SLOT: pairs and stretched pairs that touch the node (integer atomic adds; a pair from a node to itself counts
-// once) and the largest rel_sq (unsigned 64-bit atomic max on the bits of the non-negative double: same order as the
-// values).  Sums of integers and a maximum do not depend on the order of arrival.  The maximum only grows, so a plain load
-// that already shows a value >= ours, however stale, makes the atomic unnecessary.  slots: [pairs | stretched | max],
+// Per node SLOT (node_pair, quality_device.h): integer atomic adds and an atomic max on bits.  slots: [pairs | stretched | max],
 // n_nodes words each, zeroed by the caller.
 __global__ void __launch_bounds__(Q_BLOCK) node_errors_kernel(const uint4 *step_rec, const uint64_t n_steps, const double *x, const uint64_t n_nodes,
                                                               const uint32_t dims, const uint64_t z, const double ratio,
@@ -408,14 +273,7 @@ __global__ void __launch_bounds__(Q_BLOCK) node_errors_kernel(const uint4 *step_
         double err, rel, dp, dl;
         bool st;
         if (!pair_stretch(ra, rb, x, n_nodes, dims, ratio, err, rel, dp, dl, st)) continue;
-        const unsigned long long bits = (unsigned long long)__double_as_longlong(rel);
-        const uint32_t ends[2] = {ra.x, rb.x};
-        for (int k = 0; k < (ra.x == rb.x ? 1 : 2); ++k) {
-            const uint32_t slot = ends[k];
-            atomicAdd(&pairs[slot], 1ull);
-            if (st) atomicAdd(&stretched[slot], 1ull);
-            if (max_bits[slot] < bits) atomicMax(&max_bits[slot], bits);
-        }
+        node_pair(ra, rb, rel, st, pairs, stretched, max_bits);
     }
 }
 // out[k] = { pairs, stretched, max_rel_sq } of dense node k (= gfs_node_error)

@@ -102,6 +102,38 @@ struct QualityItem {
 hipError_t batch_pair_errors_device(const QualityItem *d_items, const uint32_t *d_block_item, uint32_t n_items, uint64_t row_blocks,
                                     uint32_t dims, const uint64_t *d_zs, uint32_t n_z, uint64_t *d_partials, uint64_t *d_out, hipStream_t st);
 
+// batch_diagnosis_kernels.hip (K7h, K7i, K7j): K7d / K7e / K7f of every item of a batch, for one step distance z and one ratio.
+// step_rec, path_rec, x and perm are the item's context's.  first_tile, first_path, first_node, first_pair: where the item's
+// tiles (tile_plan), paths and nodes (row_offsets) and its room in the packed list of stretched pairs (stretched_list_plan) start;
+// first_block, blocks: K7g's plan (quality_plan).  All of it from batch_readout_plan.h.
+struct DiagItem {
+    const uint4 *step_rec, *path_rec;
+    const double *x;
+    const uint32_t *perm;
+    uint64_t n_steps, n_nodes, n_paths;
+    uint64_t first_tile, first_path, first_node, first_pair;
+    uint32_t first_block, blocks;
+};
+// max_blocks (K7h, K7i): a cap on the grids over flat tiles and paths below Q_TILE_MAX_BLOCKS, 0 = none (a test hook: a tile's
+// yield does not depend on the grid).
+// K7h: d_tile_item: n_tiles entries; d_head, d_tail: 5 words per flat tile; d_out: 8 words per path of the union, item i's rows at
+// first_path, as path_errors_device writes them for one.  Two launches.  Asynchronous.
+hipError_t batch_path_errors_device(const DiagItem *d_items, const uint32_t *d_tile_item, uint32_t n_items, uint64_t n_tiles, uint64_t n_paths,
+                                    uint32_t dims, uint64_t z, double ratio, uint64_t *d_head, uint64_t *d_tail, uint64_t *d_out,
+                                    uint64_t max_blocks, hipStream_t st);
+// K7i: d_counts, d_offsets: n_tiles + 1 words each; item i's total is d_offsets[first_tile[i + 1]] - d_offsets[first_tile[i]];
+// d_list (nullable: count only): the first min(cap, total) pairs of item i at first_pair, in ascending step_a, the entries
+// stretched_pairs_device writes for one; d_tmp, tmp_bytes: batch_stretched_scan_bytes(n_tiles).  Two launches, a memset, one scan.
+// Asynchronous: the cap is tested on the device.
+hipError_t batch_stretched_scan_bytes(uint64_t n_tiles, size_t *bytes);
+hipError_t batch_stretched_pairs_device(const DiagItem *d_items, const uint32_t *d_tile_item, uint64_t n_tiles, uint32_t dims, uint64_t z,
+                                        double ratio, uint64_t *d_counts, uint64_t *d_offsets, void *d_list, uint64_t cap, void *d_tmp,
+                                        size_t tmp_bytes, uint64_t max_blocks, hipStream_t st);
+// K7j: d_block_item: row_blocks entries; d_slots, d_out: 3 words per node of the union; d_out by dense index, item i's rows at
+// first_node, as node_errors_device writes them for one.  Two launches and a memset.  Asynchronous.
+hipError_t batch_node_errors_device(const DiagItem *d_items, const uint32_t *d_block_item, uint32_t n_items, uint64_t row_blocks, uint64_t n_nodes,
+                                    uint32_t dims, uint64_t z, double ratio, uint64_t *d_slots, uint64_t *d_out, hipStream_t st);
+
 // quality_kernels.hip (K7): read-outs of the resident positions.  They write their own output buffers only.
 // Workgroups of the step passes: a function of n_steps alone, so that a result does not depend on the device.
 unsigned quality_blocks(uint64_t n_steps);

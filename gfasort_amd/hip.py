@@ -142,6 +142,7 @@ EXPORTS = [
     "gfs_batch_plan", "gfs_batch_create", "gfs_batch_run", "gfs_batch_get_stats", "gfs_batch_destroy",
     "gfs_batch_result_offsets", "gfs_batch_init_positions", "gfs_batch_results", "gfs_batch_debug_sort_cap",
     "gfs_batch_upload_coords", "gfs_batch_coords", "gfs_batch_pair_errors",
+    "gfs_batch_path_offsets", "gfs_batch_path_errors", "gfs_batch_stretched_pairs", "gfs_batch_node_errors", "gfs_batch_debug_tile_blocks",
     "gfs_ctx_set_plan", "gfs_ctx_set_create", "gfs_ctx_set_size", "gfs_ctx_set_item", "gfs_ctx_set_get_info", "gfs_ctx_set_destroy",
 ]
 SEGMENT_SORT_CAP = 8192                # GFS_SEGMENT_SORT_CAP
@@ -242,6 +243,11 @@ def lib():
         L.gfs_batch_upload_coords.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.gfs_batch_coords.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.gfs_batch_pair_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gfs_batch_path_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.gfs_batch_path_errors.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.gfs_batch_stretched_pairs.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gfs_batch_node_errors.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.gfs_batch_debug_tile_blocks.argtypes = [C.c_void_p, C.c_uint64]
         L.gfs_ctx_set_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.gfs_ctx_set_create.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
         L.gfs_ctx_set_size.argtypes = [C.c_void_p]
@@ -875,6 +881,56 @@ class Batch:
         ms = C.c_double(0.0)
         check(lib().gfs_batch_pair_errors(self._h, _ptr(zs), C.c_uint64(zs.shape[0]), _ptr(out), C.byref(ms), C.c_void_p(stream or 0)))
         return (out, float(ms.value)) if return_ms else out
+
+    # ---- the diagnosis of every item (K7h / K7i / K7j): one step distance and one ratio for the whole batch ----
+    def path_offsets(self):
+        """offsets[i] = first path of item i in the packed rows of path_errors(); offsets[items] = their number."""
+        off = np.zeros(len(self.contexts) + 1, dtype=np.uint64)
+        check(lib().gfs_batch_path_offsets(self._h, _ptr(off), C.c_uint64(off.shape[0])))
+        return off
+
+    def path_errors(self, z=1, ratio=10.0, stream=None, return_ms=False):
+        """Context.path_errors(z, ratio) of every item in two launches: a list of per-item views of one packed PATH_ERROR_DTYPE
+        array, item i's bit for bit what contexts[i].path_errors(z, ratio) returns."""
+        off = self.path_offsets()
+        out = np.zeros(int(off[-1]), dtype=PATH_ERROR_DTYPE)
+        ms = C.c_double(0.0)
+        check(lib().gfs_batch_path_errors(self._h, C.c_uint64(z), C.c_double(ratio), _ptr(out), C.c_uint64(out.shape[0]), C.byref(ms),
+                                          C.c_void_p(stream or 0)))
+        rows = [out[int(off[i]):int(off[i + 1])] for i in range(len(self.contexts))]
+        return (rows, float(ms.value)) if return_ms else rows
+
+    def stretched_pairs(self, z=1, ratio=10.0, cap=1024, out=None, stream=None, return_ms=False):
+        """Context.stretched_pairs(z, ratio, cap) of every item in two launches and one scan: (list of rows[:min(cap, total_i)], a
+        STRETCHED_PAIR_DTYPE array per item in ascending step_a, step and path numbers the item's own; totals as a uint64 array).
+        out: a caller's (items, cap) array to write into (entries beyond an item's list stay as they are)."""
+        cap, n = int(cap), len(self.contexts)
+        if out is None:
+            out = np.zeros((n, cap), dtype=STRETCHED_PAIR_DTYPE)
+        if out.dtype != STRETCHED_PAIR_DTYPE or out.shape != (n, cap) or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous STRETCHED_PAIR_DTYPE array of shape (items, cap)")
+        totals = np.zeros(n, dtype=np.uint64)
+        ms = C.c_double(0.0)
+        check(lib().gfs_batch_stretched_pairs(self._h, C.c_uint64(z), C.c_double(ratio), _ptr(out) if cap else None, C.c_uint64(cap),
+                                              _ptr(totals), C.byref(ms), C.c_void_p(stream or 0)))
+        rows = [out[i, :min(cap, int(totals[i]))] for i in range(n)]
+        return (rows, totals, float(ms.value)) if return_ms else (rows, totals)
+
+    def node_errors(self, z=1, ratio=10.0, stream=None, return_ms=False):
+        """Context.node_errors(z, ratio) of every item in two launches: a list of per-item views of one packed NODE_ERROR_DTYPE
+        array, by dense node index, item i's at result_offsets()[i]."""
+        off = self.result_offsets()
+        out = np.zeros(int(off[-1]), dtype=NODE_ERROR_DTYPE)
+        ms = C.c_double(0.0)
+        check(lib().gfs_batch_node_errors(self._h, C.c_uint64(z), C.c_double(ratio), _ptr(out), C.c_uint64(out.shape[0]), C.byref(ms),
+                                          C.c_void_p(stream or 0)))
+        rows = [out[int(off[i]):int(off[i + 1])] for i in range(len(self.contexts))]
+        return (rows, float(ms.value)) if return_ms else rows
+
+    def debug_tile_blocks(self, n):
+        """Test hook: at most n workgroups in the grids over tiles and paths of path_errors() and stretched_pairs() (0 restores the
+        default).  No result depends on it."""
+        check(lib().gfs_batch_debug_tile_blocks(self._h, C.c_uint64(int(n))))
 
 
 # ---- one-shot entry points ---------------------------------------------------------------------

@@ -187,7 +187,11 @@ def device_diagnosis(ctx, z=1, ratio=10.0, worst=10):
     """Which paths carry the error of the positions resident in `ctx` (a hip.Context) at step distance z: dict(rows, worst).
     rows: per path dict(path, steps, reverse_steps, pairs, rms_rel, max_rel, stretched), rms_rel = sqrt(sum_rel_sq / pairs);
     worst: the indices of the `worst` paths with the largest rms_rel, largest first (ties: lower index first)."""
-    pe = ctx.path_errors(z, ratio)
+    return diagnosis_rows(ctx.path_errors(z, ratio), worst)
+
+
+def diagnosis_rows(pe, worst=10):
+    """dict(rows, worst) of device_diagnosis from the rows of gfs_path_error of one graph."""
     rows = []
     for p, r in enumerate(pe):
         n = int(r["pairs"])
@@ -196,6 +200,12 @@ def device_diagnosis(ctx, z=1, ratio=10.0, worst=10):
                          stretched=int(r["stretched"])))
     order = sorted(range(len(rows)), key=lambda p: (-rows[p]["rms_rel"], p))
     return dict(rows=rows, worst=order[:worst])
+
+
+def batch_diagnosis(batch, z=1, ratio=10.0, worst=10):
+    """device_diagnosis of every item of a hip.Batch, read in one call while the batch is resident (Batch.path_errors): a list,
+    item i's entry exactly what device_diagnosis(batch.contexts[i], z, ratio, worst) returns."""
+    return [diagnosis_rows(pe, worst) for pe in batch.path_errors(z, ratio)]
 
 
 # ---- rank agreement ------------------------------------------------------------------------------

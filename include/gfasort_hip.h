@@ -446,6 +446,32 @@ int  gfs_batch_coords(gfs_batch *b, double *coords, uint64_t total, double *kern
  * but out. */
 int  gfs_batch_pair_errors(gfs_batch *b, const uint64_t *zs, uint64_t n_z, gfs_pair_error *out /*[items][n_z]*/, double *kernel_ms /*nullable*/,
                            void *hip_stream);
+/* The diagnosis of every item, for sorts and layouts alike, one step distance z and one ratio for the whole batch (DESIGN.md §3,
+ * K7h / K7i / K7j): what gfs_ctx_path_errors, gfs_ctx_stretched_pairs and gfs_ctx_node_errors give one item at a time, field for
+ * field and the doubles bit for bit (a tile of 512 steps yields the same whoever runs it, a path's tiles are folded in tile order,
+ * per node only integer sums and a maximum are accumulated), in a number of launches that does not depend on the number of items:
+ * paths 2 launches; pairs 2 launches, a memset and one scan; nodes 2 launches and a memset.  Tables go up in one copy through the
+ * batch's pinned staging, results come back in one; scratch is the batch's, nothing is allocated per call once it has grown.
+ *   gfs_batch_path_offsets   host only: offsets[i] = sum of n_paths of items 0..i-1, offsets[items] = total_paths; n = items + 1
+ *   gfs_batch_path_errors    out[offsets[i] + p] = path p of item i; total_paths must be offsets[items]
+ *   gfs_batch_stretched_pairs  totals[i] = item i's exact number of stretched pairs; out[i * cap + k], k < min(cap, totals[i]), its
+ *                            first pairs in ascending step_a, step and path numbers the item's own; entries past that are left
+ *                            untouched; out may be NULL when cap = 0.  The cap is applied on the device: one synchronise
+ *   gfs_batch_node_errors    out[offsets[i] + k] = dense node k of item i, offsets those of gfs_batch_result_offsets; total_nodes
+ *                            must be offsets[items]
+ * GFS_E_ARG for a null batch or pointer, z == 0, a ratio that is NaN or negative, or a wrong total (gfs_ctx_*'s rules); GFS_E_STATE,
+ * naming the item, for a context without positions or no longer of the batch's dimensions; all checked before any device call and
+ * before anything is written.  *kernel_ms (nullable): HIP events around the launches.  Every entry runs on hip_stream and
+ * synchronises; nothing but the outputs is written: positions, RNG streams and counters are untouched. */
+int  gfs_batch_path_offsets(const gfs_batch *b, uint64_t *offsets, uint64_t n);
+int  gfs_batch_path_errors(gfs_batch *b, uint64_t z, double ratio, gfs_path_error *out, uint64_t total_paths, double *kernel_ms /*nullable*/,
+                           void *hip_stream);
+int  gfs_batch_stretched_pairs(gfs_batch *b, uint64_t z, double ratio, gfs_stretched_pair *out /*[items][cap], NULL when cap = 0*/, uint64_t cap,
+                               uint64_t *totals /*[items]*/, double *kernel_ms /*nullable*/, void *hip_stream);
+int  gfs_batch_node_errors(gfs_batch *b, uint64_t z, double ratio, gfs_node_error *out, uint64_t total_nodes, double *kernel_ms /*nullable*/,
+                           void *hip_stream);
+/* test hook: caps the grids over flat tiles and paths of K7h and K7i at max_blocks workgroups; 0 restores the default.  No result changes. */
+int  gfs_batch_debug_tile_blocks(gfs_batch *b, uint64_t max_blocks);
 
 /* ---- context sets: the contexts of many small graphs built in one pass ----
  * gfs_ctx_create costs about the same however small the graph is: a score of allocations, six blocking uploads, three sorts, a scan
