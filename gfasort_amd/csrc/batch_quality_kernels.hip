@@ -67,28 +67,12 @@ __global__ void __launch_bounds__(Q_BLOCK) batch_pair_errors_kernel(const Qualit
 }
 
 // partials[field][zi][first_block .. first_block + blocks) of item blockIdx.x -> out[item][zi][field], summed in workgroup
-// order by thread 0; the others stage a tile in LDS (reduce_partials_kernel's loop).  grid (items, n_z).
+// order by thread 0 (reduce_item_partials, quality_device.h: reduce_partials_kernel's loop).  grid (items, n_z).
 __global__ void __launch_bounds__(Q_BLOCK) batch_reduce_partials_kernel(const QualityItem *items, const uint64_t *partials, const uint32_t row_blocks,
                                                                         uint64_t *out) {
-    __shared__ uint64_t tile[5][Q_BLOCK];
     const QualityItem it = items[blockIdx.x];
-    const uint32_t zi = blockIdx.y, n_z = gridDim.y, n_blocks = it.blocks;
-    uint64_t acc[5] = {0, 0, 0, 0, 0};                                     // (0 is +0.0 too)
-    for (uint32_t base = 0; base < n_blocks; base += Q_BLOCK) {
-        const uint32_t n = n_blocks - base < Q_BLOCK ? n_blocks - base : Q_BLOCK;
-        if (threadIdx.x < n)
-#pragma unroll
-            for (int f = 0; f < 5; ++f) tile[f][threadIdx.x] = partials[((uint64_t)f * n_z + zi) * row_blocks + it.first_block + base + threadIdx.x];
-        __syncthreads();
-        if (threadIdx.x == 0)
-            for (uint32_t b = 0; b < n; ++b)
-#pragma unroll
-                for (int f = 0; f < 5; ++f) acc[f] = combine(PairFields::op(f), acc[f], tile[f][b]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int f = 0; f < 5; ++f) out[((uint64_t)blockIdx.x * n_z + zi) * 5 + f] = acc[f];
+    reduce_item_partials<PairFields>(partials, gridDim.y, blockIdx.y, row_blocks, it.first_block, it.blocks,
+                                     out + ((uint64_t)blockIdx.x * gridDim.y + blockIdx.y) * 5);
 }
 
 hipError_t batch_pair_errors_device(const QualityItem *d_items, const uint32_t *d_block_item, uint32_t n_items, uint64_t row_blocks,

@@ -2,9 +2,11 @@
 //   K4b  initial positions of every item (K4, index_kernels.hip, without its rocPRIM scans and allocations)
 //   K6b  positions in dense order and rank order of every item (K6 without its radix passes): a graph of a few thousand nodes
 //        fits in one workgroup's LDS, where a bitonic network sorts its (key, dense index) pairs
-// The network's arithmetic is segment_sort.h's, which the host runs serially in its tests.
+// The network's arithmetic is segment_sort.h's, which the host runs serially in its tests; what a workgroup does with it, and the
+// scan of a chunk, are segment_device.h's.
 #include "sgd_host.h"
 #include "segment_sort.h"
+#include "segment_device.h"
 #include "sort_key.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,10 +15,7 @@ namespace gfs {
 
 // ---- K6b -----------------------------------------------------------------------------------------
 // Workgroup b sorts item items[b]; all items of a launch have the same padded length P (the launch's LDS: P keys, then P
-// indices) and the block is segment_block(P), so every thread is live in every loop below.  Element t of the segment is held by
-// thread t % blockDim.x: a partner at distance j < 64 is lane ^ j of the same wave, and those stages run in registers over wave
-// shuffles, a chunk of blockDim.x elements at a time; the stages with j >= 64 exchange through LDS, consecutive lanes on
-// consecutive 8-byte keys (no bank conflict), with a barrier each.  P = 8192: 28 LDS stages and 13 wave passes for 91 stages.
+// indices) and the block is segment_block(P).  The network itself is segment_device.h's segment_network, which K7k shares.
 __global__ void __launch_bounds__(1024) segment_sort_kernel(const ReadoutItem *items, double *positions, uint32_t *order) {
     extern __shared__ __align__(16) unsigned char smem[];
     const ReadoutItem it = items[blockIdx.x];
@@ -34,33 +33,7 @@ __global__ void __launch_bounds__(1024) segment_sort_kernel(const ReadoutItem *i
         keys[t] = key; index[t] = idx;
     }
     __syncthreads();
-    for (uint32_t k = 2; k <= P; k <<= 1) {
-        uint32_t j = k >> 1;
-        for (; j >= SEGMENT_WAVE; j >>= 1) {
-            for (uint32_t q = tid; q < P / 2; q += B) {
-                const uint32_t lo = segment_pair_low(q, j), hi = segment_partner(lo, j);
-                const uint64_t k_lo = keys[lo], k_hi = keys[hi];
-                const uint32_t i_lo = index[lo], i_hi = index[hi];
-                if (segment_takes_other(lo, k, j, k_lo, i_lo, k_hi, i_hi)) {
-                    keys[lo] = k_hi; keys[hi] = k_lo;
-                    index[lo] = i_hi; index[hi] = i_lo;
-                }
-            }
-            __syncthreads();
-        }
-        const uint32_t j_wave = j;                                          // min(k / 2, 32)
-        for (uint32_t t = tid; t < P; t += B) {                            // (P and B are multiples of 64: whole waves)
-            uint64_t key = keys[t];
-            uint32_t idx = index[t];
-            for (j = j_wave; j >= 1; j >>= 1) {
-                const uint64_t k_other = __shfl_xor((unsigned long long)key, (int)j);
-                const uint32_t i_other = __shfl_xor(idx, (int)j);
-                if (segment_takes_other(t, k, j, key, idx, k_other, i_other)) { key = k_other; idx = i_other; }
-            }
-            keys[t] = key; index[t] = idx;
-        }
-        __syncthreads();
-    }
+    segment_network(keys, index, P, B, tid);
     for (uint32_t t = tid; t < n; t += B) order[it.offset + t] = index[t];
 }
 
@@ -80,35 +53,20 @@ hipError_t sort_segments_device(const ReadoutItem *d_items, uint32_t count, uint
 
 // ---- K4b -----------------------------------------------------------------------------------------
 // x[perm[k]] = sum of node_len[0 .. k) (sgd.rs:286-294) for item items[blockIdx.x]: chunks of one block, an inclusive scan over the
-// wave by shuffles, the waves' totals through LDS, the running sum carried from chunk to chunk.  Integer arithmetic: the result
-// does not depend on the launch shape.
+// wave by shuffles, the waves' totals through LDS (segment_device.h block_scan_chunk, which K7k shares), the running sum carried
+// from chunk to chunk.  Integer arithmetic: the result does not depend on the launch shape.
 constexpr uint32_t INIT_BLOCK = 256;
 __global__ void __launch_bounds__(INIT_BLOCK) batch_init_positions_kernel(const ReadoutItem *items) {
     __shared__ uint64_t wave_total[INIT_BLOCK / 64];
     const ReadoutItem it = items[blockIdx.x];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint64_t carry = 0;
     for (uint64_t base = 0; base < it.n; base += INIT_BLOCK) {             // (the same trips for every thread)
         const uint64_t k = base + threadIdx.x;
         const uint64_t len = k < it.n ? (uint64_t)it.node_len[k] : 0ull;
-        uint64_t incl = len;
-#pragma unroll
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint64_t up = __shfl_up((unsigned long long)incl, d);
-            if (lane >= d) incl += up;
-        }
-        if (lane == 63) wave_total[wave] = incl;
-        __syncthreads();
-        uint64_t before = 0, total = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < INIT_BLOCK / 64; ++w) {
-            const uint64_t s = wave_total[w];
-            if (w < wave) before += s;
-            total += s;
-        }
-        if (k < it.n) it.x[it.perm[k]] = (double)(carry + before + incl - len);   // the reference accumulates in usize and converts (sgd.rs:291)
+        uint64_t total;
+        const uint64_t before = block_scan_chunk(len, wave_total, INIT_BLOCK / 64, total);
+        if (k < it.n) it.x[it.perm[k]] = (double)(carry + before);         // the reference accumulates in usize and converts (sgd.rs:291)
         carry += total;
-        __syncthreads();
     }
 }
 

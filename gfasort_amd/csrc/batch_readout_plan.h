@@ -1,8 +1,11 @@
 // batch_readout_plan.h — which workgroup, or which wave, of a batch's flat read-out launches works on which item (K4c / K6c, K7g:
-// batch_quality_kernels.hip; K7h / K7i / K7j: batch_diagnosis_kernels.hip), and where an item's rows lie in the packed results.
-// Host only and free of HIP: the kernels take every index from the tables built here, and tests/test_batch_layout_host.py and
-// tests/test_batch_diagnosis_host.py compile it into programs of their own under the address and undefined-behaviour sanitizers.
+// batch_quality_kernels.hip; K7h / K7i / K7j: batch_diagnosis_kernels.hip; K7k: batch_sort_quality_kernels.hip), where an item's
+// rows lie in the packed results, and in which order the one-workgroup-per-item launches (K6b, K7k) take the items.
+// Host only and free of HIP: the kernels take every index from the tables built here, and tests/test_batch_layout_host.py,
+// tests/test_batch_diagnosis_host.py and tests/test_batch_sort_quality_host.py compile it into programs of their own under the
+// address and undefined-behaviour sanitizers.
 #pragma once
+#include "segment_sort.h"                                 // segment_padded, SEGMENT_SORT_CAP (free of HIP as well)
 #include <stdint.h>
 
 namespace gfs {
@@ -84,6 +87,31 @@ inline uint64_t stretched_list_plan(const uint64_t *n_steps, uint64_t n, uint64_
     for (uint64_t i = 0; i < n; ++i) { first_pair[i] = total; total += stretched_room(cap, n_steps[i]); }
     first_pair[n] = total;
     return total;
+}
+
+// ---- K6b / K7k: one launch per padded segment length -------------------------------------------------------------------
+// An item of at most `cap` nodes (cap <= SEGMENT_SORT_CAP) is sorted in LDS by one workgroup, in a launch with the other items of
+// its padded length (the launch's LDS and block are sized by it); one of more nodes takes K6, alone.
+constexpr uint64_t SEGMENT_ABOVE_CAP = ~0ull;
+inline uint64_t segment_group_of(uint64_t n_nodes, uint64_t cap) { return n_nodes <= cap ? (uint64_t)segment_padded((uint32_t)n_nodes) : SEGMENT_ABOVE_CAP; }
+// order[0..n): the items by ascending padded length, those above the cap last, item order kept among equals (what a stable sort
+// by segment_group_of gives).  Returns how many are within the cap: order[0 .. that) are the launches' rows.
+inline uint64_t segment_launch_order(const uint64_t *n_nodes, uint64_t n, uint64_t cap, uint64_t *order) {
+    uint64_t at = 0, within = 0;
+    for (uint64_t P = SEGMENT_WAVE;; P <<= 1) {
+        const uint64_t group = P <= SEGMENT_SORT_CAP ? P : SEGMENT_ABOVE_CAP;
+        if (group == SEGMENT_ABOVE_CAP) within = at;
+        for (uint64_t i = 0; i < n; ++i) if (segment_group_of(n_nodes[i], cap) == group) order[at++] = i;
+        if (group == SEGMENT_ABOVE_CAP) break;
+    }
+    return within;
+}
+// the row behind the last one of the launch that starts at row `first` (< within): the rows of one padded length
+inline uint64_t segment_launch_end(const uint64_t *n_nodes, const uint64_t *order, uint64_t first, uint64_t within, uint64_t cap) {
+    const uint64_t P = segment_group_of(n_nodes[order[first]], cap);
+    uint64_t end = first;
+    while (end < within && segment_group_of(n_nodes[order[end]], cap) == P) ++end;
+    return end;
 }
 
 }  // namespace gfs

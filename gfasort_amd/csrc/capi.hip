@@ -1018,6 +1018,19 @@ int gfs_pair_errors(const gfs_graph_view *g, uint64_t dims, const double *positi
     return rc;
 }
 
+int gfs_sort_quality_of(const gfs_graph_view *g, const double *positions, gfs_sort_quality *out) {
+    if (!g || !out) return fail(GFS_E_ARG, "null argument");
+    if (g->n_nodes && !positions) return fail(GFS_E_ARG, "positions buffer is null");
+    *out = gfs_sort_quality{};
+    if (g->n_nodes == 0) return GFS_NOTHING_TO_DO;
+    gfs_ctx *c = nullptr;
+    int rc = positions_only_ctx(g, 0, positions, &c);
+    if (rc) return rc;
+    rc = gfs_ctx_sort_quality(c, out);
+    gfs_ctx_destroy(c);
+    return rc;
+}
+
 int gfs_diagnose(const gfs_graph_view *g, uint64_t dims, const double *positions, uint64_t z, double ratio,
                  gfs_path_error *paths_out, gfs_stretched_pair *pairs_out, uint64_t cap, uint64_t *total) {
     if (!g || !total || (!paths_out && g->n_paths) || (!pairs_out && cap)) return fail(GFS_E_ARG, "null argument");

@@ -1,7 +1,7 @@
 // capi_batch.hip — the batch entries of the C ABI (include/gfasort_hip.h, gfs_batch_*): many configured contexts (capi.hip,
 // capi_ctx.h) in one persistent launch (K1f / K2f, sgd_kernels_batch.hip), and their start positions, read-outs, coordinates and
 // pair errors in one launch each (K4b / K6b, K4c / K6c, K7g), and their diagnosis — errors per path, stretched pairs, errors per node —
-// in a constant number of launches (K7h, K7i, K7j).
+// and their sort quality in a constant number of launches (K7h, K7i, K7j; K7k).
 #include "capi_ctx.h"
 #include "sgd_batch.h"
 #include "batch_plan.h"
@@ -262,6 +262,11 @@ static std::vector<uint64_t> batch_offsets(const gfs_batch *b) {
     for (size_t i = 0; i < b->ctxs.size(); ++i) offsets[i + 1] = offsets[i] + b->ctxs[i]->n_nodes;
     return offsets;
 }
+static std::vector<uint64_t> batch_nodes(const gfs_batch *b) {
+    std::vector<uint64_t> nodes(b->ctxs.size());
+    for (size_t i = 0; i < nodes.size(); ++i) nodes[i] = b->ctxs[i]->n_nodes;
+    return nodes;
+}
 // the checks gfs_ctx_init_positions and gfs_ctx_sort_order make, on every item; no device call
 static int batch_readout_check(const gfs_batch *b) {
     if (b->dims != 0) return fail(GFS_E_UNSUPPORTED, "a batch of layouts has no start positions or rank order (dims=" + std::to_string(b->dims) +
@@ -339,30 +344,24 @@ int gfs_batch_results(gfs_batch *b, double *positions, uint32_t *order, uint64_t
     double *const d_positions = b->d_positions.as<double>();
     uint32_t *const d_order = b->d_order.as<uint32_t>();
     // items within the cap by the length of their padded segment: one launch per length, its LDS and block sized by it; the others after them
-    std::vector<uint64_t> by_len(b->ctxs.size());
-    std::iota(by_len.begin(), by_len.end(), 0ull);
-    auto padded_of = [&](uint64_t i) -> uint64_t {
-        const uint64_t n = b->ctxs[i]->n_nodes;
-        return n <= b->sort_cap ? gfs::segment_padded((uint32_t)n) : ~0ull;
-    };
-    std::stable_sort(by_len.begin(), by_len.end(), [&](uint64_t a, uint64_t c) { return padded_of(a) < padded_of(c); });
+    const std::vector<uint64_t> nodes = batch_nodes(b);
+    std::vector<uint64_t> by_len(nodes.size());
+    const uint64_t within = gfs::segment_launch_order(nodes.data(), nodes.size(), b->sort_cap, by_len.data());
     rc = batch_readout_table(b, by_len, st);
     if (rc) return rc;
     HIPCHK(b->readout_timer.start(st));
-    size_t first = 0;
-    while (first < by_len.size() && padded_of(by_len[first]) != ~0ull) {
-        const uint64_t P = padded_of(by_len[first]);
-        size_t end = first;
-        while (end < by_len.size() && padded_of(by_len[end]) == P) ++end;
-        for (size_t at = first; at < end; at += 0x7FFFFFFFull) {           // (a grid's x dimension)
-            const uint32_t count = (uint32_t)std::min<size_t>(end - at, 0x7FFFFFFFull);
+    for (uint64_t first = 0; first < within;) {
+        const uint64_t P = gfs::segment_group_of(nodes[by_len[first]], b->sort_cap);
+        const uint64_t end = gfs::segment_launch_end(nodes.data(), by_len.data(), first, within, b->sort_cap);
+        for (uint64_t at = first; at < end; at += 0x7FFFFFFFull) {         // (a grid's x dimension)
+            const uint32_t count = (uint32_t)std::min<uint64_t>(end - at, 0x7FFFFFFFull);
             hipError_t e = gfs::sort_segments_device(b->d_readout.as<gfs::ReadoutItem>() + at, count, (uint32_t)P, positions ? d_positions : nullptr, d_order, st);
             if (e != hipSuccess) return fail(GFS_E_HIP, std::string("segment sort launch: ") + hipGetErrorString(e));
         }
         first = end;
     }
     // above the cap: K6 (rocPRIM radix sort) once each, into the same packed arrays
-    for (size_t r = first; r < by_len.size(); ++r) {
+    for (size_t r = within; r < by_len.size(); ++r) {
         const gfs_ctx *c = b->ctxs[by_len[r]];
         const gfs::ReadoutItem &it = b->h_readout[r];
         const uint64_t n = c->n_nodes, need = n * (2 * 8 + 2 * 4);
@@ -513,6 +512,99 @@ int gfs_batch_pair_errors(gfs_batch *b, const uint64_t *zs, uint64_t n_z, gfs_pa
     return GFS_OK;
 }
 
+// ---- K7k: gfs_ctx_sort_quality of every item of a batch of 1D sorts (batch_sort_quality_kernels.hip) ------------------------------
+static uint64_t words8(uint64_t bytes) { return (bytes + 7) / 8 * 8; }
+
+int gfs_batch_sort_quality(gfs_batch *b, gfs_sort_quality *out, uint64_t n, double *kernel_ms, void *hip_stream) {
+    if (!b) return fail(GFS_E_ARG, "batch is null");
+    if (!out) return fail(GFS_E_ARG, "out is null");
+    if (n != b->ctxs.size()) return fail(GFS_E_ARG, "n is not the batch's item count");
+    if (b->dims != 0) return fail(GFS_E_UNSUPPORTED, "a batch of layouts has no sort quality (dims=" + std::to_string(b->dims) +
+                                                          "): use gfs_batch_pair_errors and gfs_batch_path_errors");
+    for (uint64_t i = 0; i < n; ++i) {
+        const gfs_ctx *c = b->ctxs[i];
+        if (c->dims != 0 || (c->n_nodes && !c->d_x)) return fail(GFS_E_STATE, "batch item " + std::to_string(i) + ": needs a 1D context that has been set up");
+    }
+    if (n > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, "the batch's items exceed one table");
+    const std::vector<uint64_t> nodes = batch_nodes(b), first_node = batch_offsets(b);
+    std::vector<uint64_t> steps(n), first_block(n + 1), by_len(n);
+    for (uint64_t i = 0; i < n; ++i) steps[i] = b->ctxs[i]->n_steps;
+    const uint64_t row_blocks = gfs::quality_plan(steps.data(), n, first_block.data()), total_nodes = first_node.back();
+    if (row_blocks > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, "the batch's step tables exceed one launch");
+    const uint64_t within = gfs::segment_launch_order(nodes.data(), n, b->sort_cap, by_len.data());
+    if (kernel_ms) *kernel_ms = 0.0;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipDeviceSynchronize());                                        // as gfs_ctx_sort_quality: nothing of an item is in flight
+    hipStream_t st = (hipStream_t)hip_stream;
+    // device: [ReadoutItem rows, in launch order | SortQualityItem table | block table (whole words) | out words | totals by row |
+    // sorted positions, packed by item | partials]; the first three go up in one copy, out and totals come back in one
+    const uint64_t items_at = n * sizeof(gfs::ReadoutItem), blocks_at = items_at + n * sizeof(gfs::SortQualityItem);
+    const uint64_t out_at = blocks_at + words8(row_blocks * sizeof(uint32_t)), totals_at = out_at + n * 5 * 8, spos_at = totals_at + n * 8;
+    const uint64_t partials_at = spos_at + total_nodes * 8, bytes = partials_at + 5 * row_blocks * 8;
+    int rc = b->h_packed.reserve(spos_at);                                 // (staging: the same offsets, less positions and partials)
+    if (!rc) rc = b->d_quality.reserve(bytes);
+    if (rc) return rc;
+    unsigned char *h = b->h_packed.as<unsigned char>(), *d = b->d_quality.as<unsigned char>();
+    uint64_t *const d_spos = reinterpret_cast<uint64_t *>(d + spos_at), *const d_totals = reinterpret_cast<uint64_t *>(d + totals_at);
+    gfs::ReadoutItem *h_rows = reinterpret_cast<gfs::ReadoutItem *>(h);
+    gfs::SortQualityItem *h_items = reinterpret_cast<gfs::SortQualityItem *>(h + items_at);
+    for (uint64_t r = 0; r < n; ++r) {                                     // from the contexts as they are now (positions may have been bound anew)
+        const gfs_ctx *c = b->ctxs[by_len[r]];
+        gfs::ReadoutItem &it = h_rows[r];
+        it.x = c->d_x; it.perm = c->d_perm; it.node_len = c->d_node_len;
+        it.offset = first_node[by_len[r]];
+        it.n = (uint32_t)c->n_nodes;                                       // (a context has fewer than 2^31 nodes)
+        it.padded = r < within ? (uint32_t)gfs::segment_group_of(c->n_nodes, b->sort_cap) : 0;
+    }
+    for (uint64_t i = 0; i < n; ++i) {
+        const gfs_ctx *c = b->ctxs[i];
+        h_items[i] = gfs::SortQualityItem{c->d_step_rec, d_spos + first_node[i], c->n_steps, (uint32_t)first_block[i], (uint32_t)(first_block[i + 1] - first_block[i])};
+    }
+    gfs::block_item_table(first_block.data(), n, reinterpret_cast<uint32_t *>(h + blocks_at));
+    HIPCHK(hipMemcpyAsync(d, h, blocks_at + row_blocks * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(b->readout_timer.start(st));
+    for (uint64_t first = 0; first < within;) {
+        const uint64_t P = gfs::segment_group_of(nodes[by_len[first]], b->sort_cap);
+        const uint64_t end = gfs::segment_launch_end(nodes.data(), by_len.data(), first, within, b->sort_cap);
+        hipError_t e = gfs::batch_sorted_positions_device(reinterpret_cast<const gfs::ReadoutItem *>(d) + first, (uint32_t)(end - first), (uint32_t)P, d_spos,
+                                                          d_totals + first, st);
+        if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch sorted positions launch: ") + hipGetErrorString(e));
+        first = end;
+    }
+    // above the cap: K6 and K7c's own scan and scatter once each, into the same packed positions
+    std::vector<uint64_t> long_total(n - within, 0);
+    for (uint64_t r = within; r < n; ++r) {
+        const gfs_ctx *c = b->ctxs[by_len[r]];
+        const uint64_t nn = c->n_nodes, sort_bytes = nn * (2 * 8 + 2 * 4);
+        HIPCHK(hipStreamSynchronize(st));                                  // (K6 runs on the null stream)
+        rc = b->d_sort_tmp.reserve(sort_bytes + (nn + 1) * 8);             // [K6's scratch | prefix]
+        if (rc) return rc;
+        uint32_t *d_sorted = nullptr;
+        hipError_t e = gfs::sort_order_device(c->d_x, c->d_perm, nn, 1, b->d_sort_tmp.p, &d_sorted);
+        if (e != hipSuccess) return fail(GFS_E_HIP, "batch item " + std::to_string(by_len[r]) + ": sort_order_device: " + hipGetErrorString(e));
+        e = gfs::sorted_positions_device(d_sorted, c->d_node_len, c->d_perm, nn, reinterpret_cast<uint64_t *>(b->d_sort_tmp.as<unsigned char>() + sort_bytes),
+                                         d_spos + first_node[by_len[r]], &long_total[r - within], st);
+        if (e != hipSuccess) return fail(GFS_E_HIP, "batch item " + std::to_string(by_len[r]) + ": sorted_positions_device: " + hipGetErrorString(e));
+        HIPCHK(hipStreamSynchronize(st));                                  // (the scratch is the next item's)
+    }
+    hipError_t e = gfs::batch_sort_quality_device(reinterpret_cast<const gfs::SortQualityItem *>(d + items_at), reinterpret_cast<const uint32_t *>(d + blocks_at),
+                                                  (uint32_t)n, row_blocks, reinterpret_cast<uint64_t *>(d + partials_at), reinterpret_cast<uint64_t *>(d + out_at), st);
+    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch sort_quality launch: ") + hipGetErrorString(e));
+    HIPCHK(b->readout_timer.stop(st));
+    HIPCHK(hipMemcpyAsync(h + out_at, d + out_at, spos_at - out_at, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    read_kernel_ms(b->readout_timer, kernel_ms);
+    const uint64_t *w = reinterpret_cast<const uint64_t *>(h + out_at), *totals = reinterpret_cast<const uint64_t *>(h + totals_at);
+    for (uint64_t r = 0; r < n; ++r)
+        if ((r < within ? totals[r] : long_total[r - within]) >= (1ull << 53))
+            return fail(GFS_E_UNSUPPORTED, "batch item " + std::to_string(by_len[r]) + ": a graph of 2^53 bp or more");
+    for (uint64_t i = 0; i < n; ++i) {
+        out[i].steps = w[5 * i]; out[i].abs_err_sum = w[5 * i + 1]; out[i].genomic_sum = w[5 * i + 2];
+        std::memcpy(&out[i].sq_err_sum, &w[5 * i + 3], 8);
+    }
+    return GFS_OK;
+}
+
 // ---- K7h / K7i / K7j: gfs_ctx_path_errors, gfs_ctx_stretched_pairs and gfs_ctx_node_errors of every item ---------------------------
 // Where every item's tiles, paths, nodes, listed pairs and step-pass workgroups start (batch_readout_plan.h), from the contexts as
 // they are now.
@@ -551,7 +643,6 @@ static int diag_check(const gfs_batch *b, uint64_t z, double ratio) {
     if (b->ctxs.size() > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, "the batch's items exceed one table");
     return GFS_OK;
 }
-static uint64_t words8(uint64_t bytes) { return (bytes + 7) / 8 * 8; }
 
 int gfs_batch_path_offsets(const gfs_batch *b, uint64_t *offsets, uint64_t n) {
     if (!b || !offsets) return fail(GFS_E_ARG, "null argument");

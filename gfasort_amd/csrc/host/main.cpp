@@ -29,6 +29,7 @@ struct Args {
     bool stress_profile = false;                   // after a Y or an L step: the exhaustive error per step distance
     bool diagnose = false;                         // after a Y or an L step: errors per path and the stretched adjacent pairs
     double diagnose_ratio = 10.0;
+    bool sort_quality = false;                     // after a Y step: measure_layout_quality's figures for the sorted graph
 };
 
 static void usage() {
@@ -55,6 +56,10 @@ static void usage() {
         "                                       its steps, forward and reverse steps, counted pairs, rms relative error and stretched\n"
         "                                       pairs, then the first 20 stretched pairs — those whose layout distance is more than\n"
         "                                       R (default 10) times their path distance; computed on the device)\n"
+        "                   [--sort-quality]   (after every Y step, on stderr: the figures of the reference's measure_layout_quality for\n"
+        "                                     the graph as the step sorted it — counted steps, the sums of absolute error and of genomic\n"
+        "                                     distance, rmse, mae and relative error in bp; computed on the device, all integers but\n"
+        "                                     one sum added in a fixed order.  Refused for a pipeline without a Y step)\n"
         "       gfasort_hip --batch LIST -p Y [the options above, except -i, -o and those of -p L]\n"
         "                   (LIST: one in.gfa<TAB>out.gfa per line; every graph is sorted as a -i/-o run sorts it, the small ones —\n"
         "                    those that run reference streams — together in one persistent launch that fills the device, the\n"
@@ -62,7 +67,8 @@ static void usage() {
         "       gfasort_hip --batch LIST -p L [the options above, except -i, -o, --layout-out and those of -p Y]\n"
         "                   (LIST: one in.gfa<TAB>out.gfa<TAB>layout.tsv per line; every graph is laid out as a -i/-o/--layout-out run\n"
         "                    lays it out, the small ones of 2 or 3 dimensions together in one persistent launch, the others alone.\n"
-        "                    With --stress-profile or --diagnose either kind of batch measures its graphs while they are resident)\n"
+        "                    With --stress-profile or --diagnose either kind of batch, and with --sort-quality a batch of sorts, measures its\n"
+        "                    graphs while they are resident)\n"
         "Pipeline characters: Y = path-guided SGD sort, L = nD layout (HIP engine).\n"
         "g, s, S, u exist in the reference but are not part of this build.\n";
 }
@@ -89,6 +95,7 @@ static bool parse_args(int argc, char **argv, Args &a) {
         else if (f == "--phased-sampler") { a.phased = true; }
         else if (f == "--stress-profile") { a.stress_profile = true; }
         else if (f == "--diagnose") { a.diagnose = true; }
+        else if (f == "--sort-quality") { a.sort_quality = true; }
         else if (f == "--diagnose-ratio") { if (!(v = need(i))) return false; a.diagnose_ratio = std::stod(v); }
         else if (f == "--hip-flags") { if (!(v = need(i))) return false; a.flags = (uint32_t)std::stoul(v); }
         else if (f == "-h" || f == "--help") { usage(); exit(0); }
@@ -97,6 +104,10 @@ static bool parse_args(int argc, char **argv, Args &a) {
     if (a.phased && (a.reference_sampler || (a.bundle != 0 && a.bundle != 64))) {
         std::cerr << "error: --phased-sampler switches between the reference sampler and bundles of 64: not with --reference-sampler or --bundle "
                   << a.bundle << "\n";
+        return false;
+    }
+    if (a.sort_quality && a.pipeline.find('Y') == std::string::npos) {
+        std::cerr << "error: --sort-quality measures the graph as a Y step sorted it: -p " << a.pipeline << " has no Y step\n";
         return false;
     }
     if (!a.batch_list.empty()) {
@@ -236,13 +247,23 @@ static void print_batch_stats(const gfs_batch_stats &bs) {
               << (bs.kernel_ms > 0 ? (double)bs.term_updates / bs.kernel_ms / 1e6 : 0.0) << " G updates/s), run " << bs.total_ms << " ms\n";
 }
 
+// --sort-quality: one line, every figure an integer or a double derived from integers and one sum of a fixed order (SortQuality)
+static void print_sort_quality(const SortQuality &q) {
+    char buf[256];
+    snprintf(buf, sizeof buf, "steps=%llu abs_err_sum=%llu genomic_sum=%llu rmse_bp=%.17g mae_bp=%.17g relative_error=%.17g", (unsigned long long)q.steps,
+             (unsigned long long)q.abs_err_sum, (unsigned long long)q.genomic_sum, q.rmse, q.mae, q.relative_error);
+    std::cerr << "[gfasort] sort quality: " << buf << "\n";
+}
+
 // --stress-profile and --diagnose of the positions a step ended with: x by dense index of f (dims = 0, a sort; f is the graph as
 // it was before the sort reordered it) or Layout.coords.  resident, resident_diagnosis: the profile and the diagnosis, where a batch
-// read them while the graph was resident.
+// read them while the graph was resident.  --sort-quality (sorts only) likewise, resident_quality.
 static void print_measures(const Args &args, const FlatGraph &f, const std::vector<BiPath> &paths, size_t dims, const std::vector<double> &x,
-                           const std::vector<gfs_pair_error> *resident = nullptr, const LayoutDiagnosis *resident_diagnosis = nullptr) {
+                           const std::vector<gfs_pair_error> *resident = nullptr, const LayoutDiagnosis *resident_diagnosis = nullptr,
+                           const SortQuality *resident_quality = nullptr) {
     if (args.stress_profile) print_stress_profile(resident ? *resident : layout_pair_errors(f, dims, x, step_distance_ladder(f)));
     if (args.diagnose) print_diagnosis(f, paths, dims, x, args.diagnose_ratio, resident_diagnosis);
+    if (args.sort_quality && dims == 0) print_sort_quality(resident_quality ? *resident_quality : sort_quality(f, x));
 }
 
 static void print_layout_stress(const BidirectedGraph &g, const Layout &layout) {
@@ -304,11 +325,11 @@ static int run_batch(const Args &args) {
     }
     HipOptions opt; opt.cfg.n_streams = args.streams; opt.cfg.flags = args.flags | GFS_F_BUNDLE(args.bundle);
     if (args.phased) opt.cfg.flags |= GFS_F_PHASED;                                   // (-p Y only: parse_args)
-    const bool measure = args.stress_profile || args.diagnose;
+    const bool measure = args.stress_profile || args.diagnose || args.sort_quality;
     try {
         const double diagnose_ratio = args.diagnose ? args.diagnose_ratio : -1.0;
         const gfs_batch_stats bs = layouts ? sgd_layout_batch(lays, (uint8_t)args.verbose, opt, args.stress_profile, diagnose_ratio)
-                                           : sgd_sort_batch(sorts, (uint8_t)args.verbose, opt, measure, args.stress_profile, diagnose_ratio);
+                                           : sgd_sort_batch(sorts, (uint8_t)args.verbose, opt, measure, args.stress_profile, diagnose_ratio, args.sort_quality);
         for (size_t i = 0; i < files.size(); ++i) {
             const bool batched = layouts ? lays[i].batched : sorts[i].batched;
             const gfs_stats &st = layouts ? lays[i].stats : sorts[i].stats;
@@ -323,7 +344,7 @@ static int run_batch(const Args &args) {
             const std::vector<gfs_pair_error> *resident = !batched ? nullptr : layouts ? &lays[i].profile : &sorts[i].profile;
             const LayoutDiagnosis *diagnosis = !batched || !args.diagnose ? nullptr : layouts ? &lays[i].diagnosis : &sorts[i].diagnosis;
             if (layouts) print_measures(args, graphs[i].flatten(), graphs[i].paths, lays[i].layout.dimensions, x, resident, diagnosis);
-            else print_measures(args, sorts[i].before, graphs[i].paths, 0, x, resident, diagnosis);
+            else print_measures(args, sorts[i].before, graphs[i].paths, 0, x, resident, diagnosis, batched && args.sort_quality ? &sorts[i].quality : nullptr);
         }
         if (args.verbose >= 1) print_batch_stats(bs);
     } catch (const std::exception &e) {
@@ -373,7 +394,7 @@ int main(int argc, char **argv) {
 
     bool have_layout = false;
     Layout layout;
-    const bool measure = args.stress_profile || args.diagnose;
+    const bool measure = args.stress_profile || args.diagnose || args.sort_quality;
     // the warm-up thread is NOT joined here: flattening and parameter scans need no GPU, and the first HIP
     // call of the SGD step simply waits inside the runtime for whatever initialisation is still going on
     auto t_s0 = std::chrono::steady_clock::now();

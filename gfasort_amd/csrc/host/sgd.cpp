@@ -376,13 +376,20 @@ static void batch_diagnoses(gfs_batch *b, std::vector<Item> &items, const std::v
     if (verbose >= 1) std::cerr << "[gfasort_hip] batch: diagnosis of " << together.size() << " graphs read while resident\n";
 }
 
+// keep_sort_quality: gfs_ctx_sort_quality of every item of a resident batch of sorts, in ONE gfs_batch_sort_quality
+static void batch_sort_qualities(gfs_batch *b, std::vector<BatchSortItem> &items, const std::vector<size_t> &together) {
+    std::vector<gfs_sort_quality> rows(together.size());
+    check(gfs_batch_sort_quality(b, rows.data(), rows.size(), nullptr, nullptr));
+    for (size_t k = 0; k < together.size(); ++k) items[together[k]].quality = SortQuality::from_sums(rows[k]);
+}
+
 static void add_batch_stats(gfs_batch_stats &sum, const gfs_batch_stats &one) {
     sum.items += one.items; sum.items_run += one.items_run; sum.launches += one.launches; sum.blocks += one.blocks;
     sum.term_updates += one.term_updates; sum.attempts += one.attempts; sum.kernel_ms += one.kernel_ms; sum.total_ms += one.total_ms;
 }
 
 gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbose, const HipOptions &opt, bool keep_positions, bool keep_profile,
-                               double diagnose_ratio) {
+                               double diagnose_ratio, bool keep_sort_quality) {
     SetHandle set;                                                                    // (outlives the slots and the batch)
     std::vector<Slot> slots(items.size());
     set = open_set(slots, items, opt, verbose, [](size_t) { return true; });
@@ -414,6 +421,7 @@ gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbos
     for (size_t i = 0; i < items.size(); ++i) {
         BatchSortItem &it = items[i];
         it.stats = gfs_stats{}; it.batched = false; it.positions.clear(); it.profile.clear(); it.diagnosis = LayoutDiagnosis{};
+        it.quality = SortQuality{};
         if (!it.graph || it.graph->node_count() == 0) continue;                       // sgd.rs:242-244
         const gfs_sgd_params cp = it.params.to_c();
         if (open_slot(slots[i], *it.graph, it.stats, [&](gfs_ctx *c) { return gfs_ctx_setup_1d(c, &cp, &opt.cfg, nullptr, nullptr); }) == GFS_NOTHING_TO_DO)
@@ -435,6 +443,7 @@ gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbos
         if (verbose >= 2) std::cerr << "[gfasort_hip] batch: read-out of " << together.size() << " graphs, " << readout_ms << " ms on the device\n";
         if (keep_profile) batch_profiles(b.get(), slots, items, together);
         if (diagnose_ratio >= 0.0) batch_diagnoses(b.get(), items, together, diagnose_ratio, verbose);
+        if (keep_sort_quality) batch_sort_qualities(b.get(), items, together);
         b.reset();                                                                    // (before its contexts go)
         for (size_t k = 0; k < together.size(); ++k) {
             items[together[k]].batched = true;
@@ -578,6 +587,25 @@ std::vector<gfs_pair_error> layout_pair_errors(const FlatGraph &f, size_t dims, 
     gfs_graph_view v = f.view();
     check(gfs_pair_errors(&v, dims, positions.data(), zs.data(), zs.size(), out.data()));
     return out;
+}
+
+SortQuality SortQuality::from_sums(const gfs_sort_quality &q) {
+    SortQuality o;
+    o.steps = q.steps; o.abs_err_sum = q.abs_err_sum; o.genomic_sum = q.genomic_sum; o.sq_err_sum = q.sq_err_sum;
+    if (q.steps) {
+        o.rmse = std::sqrt(q.sq_err_sum / (double)q.steps);
+        o.mae = (double)q.abs_err_sum / (double)q.steps;
+        if (q.genomic_sum) o.relative_error = o.mae / ((double)q.genomic_sum / (double)q.steps);
+    }
+    return o;
+}
+
+SortQuality sort_quality(const FlatGraph &f, const std::vector<double> &x) {
+    if (x.size() != f.node_len.size()) throw std::runtime_error("sort_quality: positions do not match the graph");
+    gfs_graph_view v = f.view();
+    gfs_sort_quality q{};
+    check(gfs_sort_quality_of(&v, x.data(), &q));
+    return SortQuality::from_sums(q);
 }
 
 std::vector<gfs_pair_error> layout_pair_errors(const BidirectedGraph &g, const Layout &layout, const std::vector<uint64_t> &zs) {

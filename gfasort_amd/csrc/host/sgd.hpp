@@ -104,6 +104,14 @@ struct LayoutDiagnosis {
     std::vector<gfs_stretched_pair> pairs;
     uint64_t total = 0;
 };
+// measure_layout_quality.rs:100-208 for a sort's positions (gfs_sort_quality): the four sums, and the figures the reference derives
+// from them (:162-208) — mse = sq_err_sum / steps, rmse = sqrt(mse), mae = abs_err_sum / steps, relative_error = mae / (genomic_sum /
+// steps), each one double operation on exact inputs; zeros without a counted step.
+struct SortQuality {
+    uint64_t steps = 0, abs_err_sum = 0, genomic_sum = 0;
+    double sq_err_sum = 0.0, rmse = 0.0, mae = 0.0, relative_error = 0.0;
+    static SortQuality from_sums(const gfs_sort_quality &q);
+};
 // sgd_sort_only over MANY graphs (no reference equivalent; gfasort_hip --batch).  Graphs for which the policy picks reference streams
 // (fewer than 16384 nodes) run together as one gfs_batch — one persistent launch, or as few as fit the device —, the others alone,
 // one after the other; every graph is then reordered exactly as sgd_sort_only reorders it.  A graph that gfs_batch_create refuses
@@ -118,6 +126,7 @@ struct BatchSortItem {
     std::vector<double> positions;         // ... and the final positions by its dense index; empty where there was nothing to do
     std::vector<gfs_pair_error> profile;   // keep_profile, batched graphs: layout_pair_errors at step_distance_ladder, read while resident
     LayoutDiagnosis diagnosis;             // diagnose_ratio >= 0, batched graphs: layout_diagnosis(before, 0, positions, 1, ratio, 20), read while resident
+    SortQuality quality;                   // keep_sort_quality, batched graphs: sort_quality(before, positions), read while resident
 };
 // Returns the batch's figures (all zero where no graph was batched).  Throws std::runtime_error on a HIP / argument error.
 // keep_profile: the batched graphs' pair errors at their step_distance_ladder are read from the batch while it is resident
@@ -125,8 +134,10 @@ struct BatchSortItem {
 // diagnose_ratio >= 0 (either driver): the batched graphs' diagnosis at z = 1, that ratio and cap = 20 is read from the batch while it
 // is resident (gfs_batch_path_errors, gfs_batch_stretched_pairs: one call each for all of them), what layout_diagnosis gives for the
 // final positions; negative: not asked for.
+// keep_sort_quality: the batched graphs' sort quality is read from the batch while it is resident (gfs_batch_sort_quality: one call for
+// all of them), what sort_quality gives for the kept positions.
 gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbose, const HipOptions &opt = {}, bool keep_positions = false,
-                               bool keep_profile = false, double diagnose_ratio = -1.0);
+                               bool keep_profile = false, double diagnose_ratio = -1.0, bool keep_sort_quality = false);
 // path_linear_sgd_layout over MANY graphs (no reference equivalent; gfasort_hip --batch -p L), the layout twin of sgd_sort_batch.
 // Every graph gets its own parameters and its own default_layout_init.  Graphs of 2 or 3 dimensions for which the policy picks
 // the pooled reference-stream kernel (stats.bundle == 1) run together, one gfs_batch per dimension: all start coordinates up
@@ -168,6 +179,8 @@ std::vector<gfs_pair_error> layout_pair_errors(const BidirectedGraph &g, const s
                                                const std::vector<uint64_t> &zs);
 LayoutDiagnosis layout_diagnosis(const FlatGraph &f, size_t dims, const std::vector<double> &positions, uint64_t z = 1,
                                  double ratio = 10.0, uint64_t cap = 20);
+// How good a sort is as a sort (gfs_sort_quality_of): x by dense index of f, measured on the device.  Throws as layout_pair_errors.
+SortQuality sort_quality(const FlatGraph &f, const std::vector<double> &x);
 // z = 1, 2, 3, 4, 6, 8, 12, 16, ...: every 2^k and 3 * 2^(k-1) below the longest path's step count
 std::vector<uint64_t> step_distance_ladder(const FlatGraph &f);
 

@@ -1,6 +1,7 @@
-// quality_device.h — the device functions K7 (quality_kernels.hip) and its batch forms K7g (batch_quality_kernels.hip) and
-// K7h-j (batch_diagnosis_kernels.hip) share: the one per-pair function, the fixed-tree reduction of a workgroup's five fields,
-// and what a wave does with one tile, one path or one pair in K7d-f.  One text for all units, so that a batch's figures are
+// quality_device.h — the device functions K7 (quality_kernels.hip) and its batch forms K7g (batch_quality_kernels.hip),
+// K7h-j (batch_diagnosis_kernels.hip) and K7k (batch_sort_quality_kernels.hip) share: the one per-pair function, the fixed-tree
+// reduction of a workgroup's five fields and the sum of an item's partials, K7c's pass over adjacent steps, and what a wave does
+// with one tile, one path or one pair in K7d-f.  One text for all units, so that a batch's figures are
 // the per-item call's bit for bit.
 #pragma once
 #include "batch_readout_plan.h"                           // Q_BLOCK, Q_PAIRS_PER_THREAD, Q_MAX_BLOCKS, Q_TILE, Q_TILE_ROUNDS
@@ -72,6 +73,51 @@ __device__ __forceinline__ void store_block_partials(uint64_t (&v)[5], uint64_t 
             uint64_t t = wave_part[0][f];
             for (unsigned w = 1; w < Q_BLOCK / 64; ++w) t = combine(F::op(f), t, wave_part[w][f]);
             partials[((uint64_t)f * n_z + zi) * gridDim.x + blockIdx.x] = t;
+        }
+    }
+}
+
+// One item's partials[field][zi][first_block .. first_block + n_blocks) of a row of row_blocks workgroups -> out[0..5), summed in
+// workgroup order from zero by thread 0; the others only stage a tile of partials in LDS so that the serial chain runs at LDS
+// latency.  One workgroup of Q_BLOCK threads; K7's own launches have first_block = 0 and row_blocks = n_blocks.
+template <typename F>
+__device__ __forceinline__ void reduce_item_partials(const uint64_t *partials, const uint32_t n_z, const uint32_t zi, const uint32_t row_blocks,
+                                                     const uint32_t first_block, const uint32_t n_blocks, uint64_t *out) {
+    __shared__ uint64_t tile[5][Q_BLOCK];
+    uint64_t acc[5] = {0, 0, 0, 0, 0};                                     // (0 is +0.0 too)
+    for (uint32_t base = 0; base < n_blocks; base += Q_BLOCK) {
+        const uint32_t n = n_blocks - base < Q_BLOCK ? n_blocks - base : Q_BLOCK;
+        if (threadIdx.x < n)
+#pragma unroll
+            for (int f = 0; f < 5; ++f) tile[f][threadIdx.x] = partials[((uint64_t)f * n_z + zi) * row_blocks + first_block + base + threadIdx.x];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (uint32_t b = 0; b < n; ++b)
+#pragma unroll
+                for (int f = 0; f < 5; ++f) acc[f] = combine(F::op(f), acc[f], tile[f][b]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int f = 0; f < 5; ++f) out[f] = acc[f];
+}
+
+// ---- K7c and K7k: adjacent steps of every path (measure_layout_quality.rs:130-160) -------------------------------------------
+// One thread's pairs (s, s + 1), the thread being threadIdx.x of workgroup `block` of a grid of `blocks` workgroups of Q_BLOCK: s =
+// block * Q_BLOCK + threadIdx.x, then in strides of blocks * Q_BLOCK, below n_steps - 1.  spos: the sorted position of every node, by slot.  Reads step_rec[0..n_steps) only.  All integers but sq_sum, which is added in the order of s.
+__device__ __forceinline__ void sort_quality_pairs(const uint4 *step_rec, const uint64_t n_steps, const uint64_t *spos, const uint32_t block,
+                                                   const uint32_t blocks, uint64_t &steps, uint64_t &abs_sum, uint64_t &gen_sum, double &sq_sum) {
+    if (n_steps > 1) {
+        const uint64_t n = n_steps - 1, stride = (uint64_t)blocks * Q_BLOCK;
+        for (uint64_t s = (uint64_t)block * Q_BLOCK + threadIdx.x; s < n; s += stride) {
+            const uint4 ra = step_rec[s], rb = step_rec[s + 1];
+            if (rec_path(ra) != rec_path(rb) || ra.x == Q_NO_NODE) continue;               // :139-144
+            const uint64_t gd = rec_pos(rb) - rec_pos(ra);                                 // = the first node's length
+            const uint64_t pa = spos[ra.x], pb = rb.x == Q_NO_NODE ? 0ull : spos[rb.x];    // :149-150 unwrap_or(0.0)
+            const uint64_t ld = pb > pa ? pb - pa : pa - pb;
+            const uint64_t ae = ld > gd ? ld - gd : gd - ld;
+            ++steps; abs_sum += ae; gen_sum += gd;
+            sq_sum += (double)ae * (double)ae;
         }
     }
 }

@@ -28,28 +28,11 @@ namespace gfs {
 // (pair_error) and the fixed-tree reduction of a workgroup (combine, store_block_partials): quality_device.h, shared with K7g.
 unsigned quality_blocks(uint64_t n_steps) { return quality_blocks_of(n_steps); }
 
-// partials[field][zi][0..n_blocks) -> out[zi][field], summed in workgroup order by thread 0; the others only stage a
-// tile of partials in LDS so that the serial chain runs at LDS latency.  One workgroup per step distance.
+// partials[field][zi][0..n_blocks) -> out[zi][field], summed in workgroup order by thread 0 (reduce_item_partials,
+// quality_device.h).  One workgroup per step distance.
 template <typename F>
 __global__ void __launch_bounds__(Q_BLOCK) reduce_partials_kernel(const uint64_t *partials, const uint32_t n_blocks, uint64_t *out) {
-    __shared__ uint64_t tile[5][Q_BLOCK];
-    const uint32_t zi = blockIdx.x, n_z = gridDim.x;
-    uint64_t acc[5] = {0, 0, 0, 0, 0};                                     // (0 is +0.0 too)
-    for (uint32_t base = 0; base < n_blocks; base += Q_BLOCK) {
-        const uint32_t n = n_blocks - base < Q_BLOCK ? n_blocks - base : Q_BLOCK;
-        if (threadIdx.x < n)
-#pragma unroll
-            for (int f = 0; f < 5; ++f) tile[f][threadIdx.x] = partials[((uint64_t)f * n_z + zi) * n_blocks + base + threadIdx.x];
-        __syncthreads();
-        if (threadIdx.x == 0)
-            for (uint32_t b = 0; b < n; ++b)
-#pragma unroll
-                for (int f = 0; f < 5; ++f) acc[f] = combine(F::op(f), acc[f], tile[f][b]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int f = 0; f < 5; ++f) out[(uint64_t)zi * 5 + f] = acc[f];
+    reduce_item_partials<F>(partials, gridDim.x, blockIdx.x, n_blocks, 0, n_blocks, out + (uint64_t)blockIdx.x * 5);
 }
 
 // ---- K7a ------------------------------------------------------------------------------------------------------------------
@@ -122,33 +105,21 @@ __global__ void scatter_sorted_pos_kernel(const uint64_t *prefix, const uint32_t
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += stride) spos[perm[order[r]]] = prefix[r];
 }
-// adjacent steps of every path (measure_layout_quality.rs:130-160).  Reads step_rec[0..n_steps) only.
+// adjacent steps of every path (sort_quality_pairs, quality_device.h).  Reads step_rec[0..n_steps) only.
 __global__ void __launch_bounds__(Q_BLOCK) sort_quality_kernel(const uint4 *step_rec, const uint64_t n_steps, const uint64_t *spos, uint64_t *partials) {
     uint64_t steps = 0, abs_sum = 0, gen_sum = 0;
     double sq_sum = 0.0;
-    if (n_steps > 1) {
-        const uint64_t n = n_steps - 1, stride = (uint64_t)gridDim.x * Q_BLOCK;
-        for (uint64_t s = (uint64_t)blockIdx.x * Q_BLOCK + threadIdx.x; s < n; s += stride) {
-            const uint4 ra = step_rec[s], rb = step_rec[s + 1];
-            if (rec_path(ra) != rec_path(rb) || ra.x == Q_NO_NODE) continue;               // :139-144
-            const uint64_t gd = rec_pos(rb) - rec_pos(ra);                                 // = the first node's length
-            const uint64_t pa = spos[ra.x], pb = rb.x == Q_NO_NODE ? 0ull : spos[rb.x];    // :149-150 unwrap_or(0.0)
-            const uint64_t ld = pb > pa ? pb - pa : pa - pb;
-            const uint64_t ae = ld > gd ? ld - gd : gd - ld;
-            ++steps; abs_sum += ae; gen_sum += gd;
-            sq_sum += (double)ae * (double)ae;
-        }
-    }
+    sort_quality_pairs(step_rec, n_steps, spos, blockIdx.x, gridDim.x, steps, abs_sum, gen_sum, sq_sum);
     uint64_t v[5] = {steps, abs_sum, gen_sum, (uint64_t)__double_as_longlong(sq_sum), 0};
     store_block_partials<SortFields>(v, partials, 1, 0);
 }
 
-// d_order: rank -> dense index (sort_order_device).  d_prefix: n_nodes + 1 words, d_spos: n_nodes words, d_partials:
-// 5 * quality_blocks(n_steps) words, d_out: 5 words { steps, abs_err_sum, genomic_sum (u64), sq_err_sum (f64 bits), 0 }.
-// *total_len_out = the graph's length in bp; at 2^53 and beyond the pass is not run (the caller refuses).  Synchronous.
-hipError_t sort_quality_device(const uint4 *d_step_rec, uint64_t n_steps, const uint32_t *d_order, const uint32_t *d_node_len,
-                               const uint32_t *d_perm, uint64_t n_nodes, uint64_t *d_prefix, uint64_t *d_spos, uint64_t *d_partials,
-                               uint64_t *d_out, uint64_t *total_len_out, hipStream_t st) {
+// The two halves of K7c, which a batch calls apart for its items above the sort cap (K7k, capi_batch.hip).
+// First half.  d_order: rank -> dense index (sort_order_device).  d_prefix: n_nodes + 1 words; d_spos: n_nodes words, by slot.
+// *total_len_out = the graph's length in bp; at 2^53 and beyond d_spos is not written (the caller refuses).  Synchronous up to
+// the launch that writes d_spos.
+hipError_t sorted_positions_device(const uint32_t *d_order, const uint32_t *d_node_len, const uint32_t *d_perm, uint64_t n_nodes,
+                                   uint64_t *d_prefix, uint64_t *d_spos, uint64_t *total_len_out, hipStream_t st) {
     auto lens = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), RankLen{d_order, d_node_len, n_nodes});
     size_t tmp_bytes = 0;
     hipError_t e = rocprim::exclusive_scan(nullptr, tmp_bytes, lens, d_prefix, (uint64_t)0, (size_t)(n_nodes + 1), rocprim::plus<uint64_t>(), st);
@@ -158,14 +129,28 @@ hipError_t sort_quality_device(const uint4 *d_step_rec, uint64_t n_steps, const 
     e = rocprim::exclusive_scan(d_tmp.p, tmp_bytes, lens, d_prefix, (uint64_t)0, (size_t)(n_nodes + 1), rocprim::plus<uint64_t>(), st);
     if (e == hipSuccess) e = hipMemcpyAsync(total_len_out, d_prefix + n_nodes, 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    d_tmp.reset();                                                         // (here, before the launches below: not at the end of scope)
+    d_tmp.reset();                                                         // (here, before the launch below: not at the end of scope)
     if (e != hipSuccess || *total_len_out >= (1ull << 53)) return e;
-    const unsigned blocks = quality_blocks(n_steps);
     hipLaunchKernelGGL(scatter_sorted_pos_kernel, dim3(1024), dim3(256), 0, st, d_prefix, d_order, d_perm, d_spos, n_nodes);
+    return hipGetLastError();
+}
+// Second half.  d_partials: 5 * quality_blocks(n_steps) words, d_out: 5 words { steps, abs_err_sum, genomic_sum (u64), sq_err_sum
+// (f64 bits), 0 }.  Synchronous.
+hipError_t sort_quality_steps_device(const uint4 *d_step_rec, uint64_t n_steps, const uint64_t *d_spos, uint64_t *d_partials, uint64_t *d_out,
+                                     hipStream_t st) {
+    const unsigned blocks = quality_blocks(n_steps);
     hipLaunchKernelGGL(sort_quality_kernel, dim3(blocks), dim3(Q_BLOCK), 0, st, d_step_rec, n_steps, d_spos, d_partials);
     hipLaunchKernelGGL(reduce_partials_kernel<SortFields>, dim3(1), dim3(Q_BLOCK), 0, st, d_partials, blocks, d_out);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    return hipStreamSynchronize(st);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : hipStreamSynchronize(st);
+}
+// Both: at a length of 2^53 bp and beyond the pass is not run (the caller refuses).  Synchronous.
+hipError_t sort_quality_device(const uint4 *d_step_rec, uint64_t n_steps, const uint32_t *d_order, const uint32_t *d_node_len,
+                               const uint32_t *d_perm, uint64_t n_nodes, uint64_t *d_prefix, uint64_t *d_spos, uint64_t *d_partials,
+                               uint64_t *d_out, uint64_t *total_len_out, hipStream_t st) {
+    const hipError_t e = sorted_positions_device(d_order, d_node_len, d_perm, n_nodes, d_prefix, d_spos, total_len_out, st);
+    if (e != hipSuccess || *total_len_out >= (1ull << 53)) return e;
+    return sort_quality_steps_device(d_step_rec, n_steps, d_spos, d_partials, d_out, st);
 }
 
 // ---- K7d / K7e / K7f: which paths, pairs and nodes carry the error -----------------------------------------------------------

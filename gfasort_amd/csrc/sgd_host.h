@@ -134,6 +134,24 @@ hipError_t batch_stretched_pairs_device(const DiagItem *d_items, const uint32_t 
 hipError_t batch_node_errors_device(const DiagItem *d_items, const uint32_t *d_block_item, uint32_t n_items, uint64_t row_blocks, uint64_t n_nodes,
                                     uint32_t dims, uint64_t z, double ratio, uint64_t *d_slots, uint64_t *d_out, hipStream_t st);
 
+// batch_sort_quality_kernels.hip (K7k): K7c of every item of a batch of 1D sorts.
+// a: count items of one padded length <= SEGMENT_SORT_CAP, one workgroup each (ReadoutItem as for K6b; offset = the item's first
+// node in d_spos): d_spos[offset + slot] = the sorted position of the node in that slot, as sorted_positions_device writes it for
+// one; d_totals[row] = the item's length in bp.  Asynchronous.
+hipError_t batch_sorted_positions_device(const ReadoutItem *d_items, uint32_t count, uint32_t padded, uint64_t *d_spos, uint64_t *d_totals,
+                                         hipStream_t st);
+// b, c: spos = the item's part of d_spos; first_block, blocks: K7g's plan (quality_plan).
+struct SortQualityItem {
+    const uint4 *step_rec;
+    const uint64_t *spos;
+    uint64_t n_steps;
+    uint32_t first_block, blocks;
+};
+// d_block_item: row_blocks entries; d_partials: 5 * row_blocks words; d_out: 5 words per item, as sort_quality_steps_device writes
+// them for one.  Two launches.  Asynchronous.
+hipError_t batch_sort_quality_device(const SortQualityItem *d_items, const uint32_t *d_block_item, uint32_t n_items, uint64_t row_blocks,
+                                     uint64_t *d_partials, uint64_t *d_out, hipStream_t st);
+
 // quality_kernels.hip (K7): read-outs of the resident positions.  They write their own output buffers only.
 // Workgroups of the step passes: a function of n_steps alone, so that a result does not depend on the device.
 unsigned quality_blocks(uint64_t n_steps);
@@ -146,7 +164,12 @@ hipError_t pair_list_device(const uint4 *d_step_rec, uint64_t n_steps, const dou
                             const uint64_t *d_step_a, const uint64_t *d_step_b, uint64_t n, double *d_rel_sq, hipStream_t st);
 // K7c: d_order from sort_order_device; d_prefix: n_nodes + 1 words, d_spos: n_nodes, d_partials: 5 * quality_blocks(n_steps),
 // d_out: 5 words { steps, abs_err_sum, genomic_sum (u64), sq_err_sum (f64 bits), 0 }; not run where *total_len_out >= 2^53.
-// Synchronous.
+// Synchronous.  Its two halves, which K7k calls apart for items above the sort cap: the sorted position of every node by slot
+// (d_spos is not written where *total_len_out >= 2^53), and the step pass with its reduce.
+hipError_t sorted_positions_device(const uint32_t *d_order, const uint32_t *d_node_len, const uint32_t *d_perm, uint64_t n_nodes,
+                                   uint64_t *d_prefix, uint64_t *d_spos, uint64_t *total_len_out, hipStream_t st);
+hipError_t sort_quality_steps_device(const uint4 *d_step_rec, uint64_t n_steps, const uint64_t *d_spos, uint64_t *d_partials, uint64_t *d_out,
+                                     hipStream_t st);
 hipError_t sort_quality_device(const uint4 *d_step_rec, uint64_t n_steps, const uint32_t *d_order, const uint32_t *d_node_len,
                                const uint32_t *d_perm, uint64_t n_nodes, uint64_t *d_prefix, uint64_t *d_spos, uint64_t *d_partials,
                                uint64_t *d_out, uint64_t *total_len_out, hipStream_t st);

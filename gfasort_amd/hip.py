@@ -7,6 +7,7 @@ import os
 import numpy as np
 
 from . import build as _build
+from .quality import sort_quality_figures
 
 NO_NODE = 0xFFFFFFFF
 MAX_DIMS = 8
@@ -110,6 +111,8 @@ class ContextSetInfo(C.Structure):
 PAIR_ERROR_DTYPE = np.dtype([("step_distance", "<u8"), ("pairs", "<u8"), ("sum_rel_sq", "<f8"), ("max_rel_sq", "<f8"),
                              ("sum_abs", "<f8"), ("sum_sq", "<f8")])
 
+SORT_QUALITY_DTYPE = np.dtype([("steps", "<u8"), ("abs_err_sum", "<u8"), ("genomic_sum", "<u8"), ("sq_err_sum", "<f8")])   # gfs_sort_quality
+
 # gfs_path_error, gfs_stretched_pair, gfs_node_error (K7d, K7e, K7f)
 PATH_ERROR_DTYPE = np.dtype([("steps", "<u8"), ("reverse_steps", "<u8"), ("pairs", "<u8"), ("sum_rel_sq", "<f8"), ("max_rel_sq", "<f8"),
                              ("sum_abs", "<f8"), ("sum_sq", "<f8"), ("stretched", "<u8")])
@@ -138,6 +141,7 @@ EXPORTS = [
     "gfs_rank_finish_buffer", "gfs_rank_finish_end", "gfs_rank_run",
     "gfs_ctx_debug_step_records", "gfs_ctx_debug_kshift", "gfs_phase_window", "gfs_ctx_phase_window",
     "gfs_ctx_pair_errors", "gfs_stress_sample_pairs", "gfs_ctx_stress_of_pairs", "gfs_ctx_sort_quality", "gfs_pair_errors",
+    "gfs_sort_quality_of", "gfs_batch_sort_quality",
     "gfs_ctx_path_errors", "gfs_ctx_stretched_pairs", "gfs_ctx_node_errors", "gfs_diagnose",
     "gfs_batch_plan", "gfs_batch_create", "gfs_batch_run", "gfs_batch_get_stats", "gfs_batch_destroy",
     "gfs_batch_result_offsets", "gfs_batch_init_positions", "gfs_batch_results", "gfs_batch_debug_sort_cap",
@@ -248,6 +252,8 @@ def lib():
         L.gfs_batch_stretched_pairs.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gfs_batch_node_errors.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.gfs_batch_debug_tile_blocks.argtypes = [C.c_void_p, C.c_uint64]
+        L.gfs_sort_quality_of.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gfs_batch_sort_quality.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.gfs_ctx_set_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.gfs_ctx_set_create.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
         L.gfs_ctx_set_size.argtypes = [C.c_void_p]
@@ -393,6 +399,18 @@ def pair_errors(g, positions, zs, dims=0):
     out = np.zeros(zs.shape[0], dtype=PAIR_ERROR_DTYPE)
     check(lib().gfs_pair_errors(C.byref(v), C.c_uint64(dims), _ptr(x), _ptr(zs), C.c_uint64(zs.shape[0]), _ptr(out)))
     return out
+
+
+def sort_quality(g, positions):
+    """gfs_sort_quality_of: measure_layout_quality.rs on the graph sorted by a finished result's 1D positions x[n_nodes] (dense
+    index), measured on device 0.  The dict Context.sort_quality() returns."""
+    v, keep = make_view(g)
+    x = np.ascontiguousarray(positions, dtype=np.float64)
+    if x.shape[0] != g.n_nodes:
+        raise ValueError("positions length does not match the graph")
+    q = SortQuality()
+    check(lib().gfs_sort_quality_of(C.byref(v), _ptr(x), C.byref(q)))
+    return sort_quality_figures(q.steps, q.abs_err_sum, q.genomic_sum, q.sq_err_sum)
 
 
 def diagnose(g, positions, z=1, ratio=10.0, cap=1024, dims=0):
@@ -667,11 +685,7 @@ class Context:
         measure_layout_quality.rs derives from them (mse, rmse, mae, relative_error)."""
         q = SortQuality()
         check(lib().gfs_ctx_sort_quality(self._h, C.byref(q)))
-        steps, abs_sum, gen = int(q.steps), int(q.abs_err_sum), int(q.genomic_sum)
-        mse = q.sq_err_sum / steps if steps else 0.0
-        mae = abs_sum / steps if steps else 0.0
-        return dict(steps=steps, abs_err_sum=abs_sum, genomic_sum=gen, sq_err_sum=float(q.sq_err_sum), mse=mse,
-                    rmse=float(np.sqrt(mse)), mae=mae, relative_error=(mae / (gen / steps)) if gen > 0 else 0.0)
+        return sort_quality_figures(q.steps, q.abs_err_sum, q.genomic_sum, q.sq_err_sum)
 
     def path_errors(self, z=1, ratio=10.0, stream=None):
         """gfs_ctx_path_errors: per path, its steps, reverse steps, K7a's sums over its pairs (s, s + z) and how many of them
@@ -926,6 +940,16 @@ class Batch:
                                           C.c_void_p(stream or 0)))
         rows = [out[int(off[i]):int(off[i + 1])] for i in range(len(self.contexts))]
         return (rows, float(ms.value)) if return_ms else rows
+
+    def sort_quality(self, stream=None, return_kernel_ms=False):
+        """Context.sort_quality() of every item of a batch of 1D sorts, in one launch per padded segment length, one step launch
+        and one reduce launch: a list of dicts, item i's field for field what contexts[i].sort_quality() returns."""
+        n = len(self.contexts)
+        out = np.zeros(n, dtype=SORT_QUALITY_DTYPE)
+        ms = C.c_double(0.0)
+        check(lib().gfs_batch_sort_quality(self._h, _ptr(out), C.c_uint64(n), C.byref(ms), C.c_void_p(stream or 0)))
+        rows = [sort_quality_figures(r["steps"], r["abs_err_sum"], r["genomic_sum"], float(r["sq_err_sum"])) for r in out]
+        return (rows, float(ms.value)) if return_kernel_ms else rows
 
     def debug_tile_blocks(self, n):
         """Test hook: at most n workgroups in the grids over tiles and paths of path_errors() and stretched_pairs() (0 restores the

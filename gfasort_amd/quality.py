@@ -11,6 +11,7 @@ diagnostic binaries, RNG-free wherever the reference is (SURVEY.md §8c(4), §7 
                         stress draws uniform pairs and is dominated by the handful of short-range pairs it happens to hit.
 * `device_profile`   — the exhaustive relative error per step distance, computed ON THE DEVICE from a resident context
                         (hip.Context.pair_errors, K7): the RNG-free replacement for `stress_by_scale`'s sampled octaves.
+* `sort_quality_figures` — mse / rmse / mae / relative error from the four sums K7c and K7k return for the sorted graph.
 * `kendall_tau`, `spearman_rho`, `oriented` — rank agreement of two sorts (a 1D layout is mirror-invariant).
 * `inversions_vs_chain` — exact count of adjacent inversions against a known chain order (P1 graphs).
 """
@@ -200,6 +201,17 @@ def diagnosis_rows(pe, worst=10):
                          stretched=int(r["stretched"])))
     order = sorted(range(len(rows)), key=lambda p: (-rows[p]["rms_rel"], p))
     return dict(rows=rows, worst=order[:worst])
+
+
+def sort_quality_figures(steps, abs_err_sum, genomic_sum, sq_err_sum):
+    """dict(steps, abs_err_sum, genomic_sum, sq_err_sum, mse, rmse, mae, relative_error) from the four sums of gfs_sort_quality,
+    as measure_layout_quality.rs:162-208 derives them: the one derivation hip.Context.sort_quality, hip.Batch.sort_quality and
+    hip.sort_quality share."""
+    steps, abs_sum, gen = int(steps), int(abs_err_sum), int(genomic_sum)
+    mse = sq_err_sum / steps if steps else 0.0
+    mae = abs_sum / steps if steps else 0.0
+    return dict(steps=steps, abs_err_sum=abs_sum, genomic_sum=gen, sq_err_sum=float(sq_err_sum), mse=mse,
+                rmse=float(np.sqrt(mse)), mae=mae, relative_error=(mae / (gen / steps)) if gen > 0 else 0.0)
 
 
 def batch_diagnosis(batch, z=1, ratio=10.0, worst=10):

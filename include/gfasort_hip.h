@@ -315,6 +315,9 @@ int gfs_ctx_sort_quality(gfs_ctx *ctx, gfs_sort_quality *out);
  * dims = 0: positions is x[n_nodes] by dense index; dims = 1..GFS_MAX_DIMS: Layout.coords order, n_nodes*2*dims. */
 int gfs_pair_errors(const gfs_graph_view *g, uint64_t dims, const double *positions, const uint64_t *zs, uint64_t n_z,
                     gfs_pair_error *out);
+/* one-shot, as gfs_pair_errors is for K7a: builds a context on device 0, uploads x[n_nodes] by dense index, measures.  (gfs_sort_quality
+ * is the result's type, so the entry is gfs_sort_quality_of.) */
+int gfs_sort_quality_of(const gfs_graph_view *g, const double *positions, gfs_sort_quality *out);
 
 /* ---- where the error sits (K7d, K7e, K7f): per path, per pair, per node, at ONE step distance z ----
  * The pairs, the per-pair formula and its skips are those above.  With d_layout = err + d_path, a counted pair is STRETCHED when
@@ -472,6 +475,18 @@ int  gfs_batch_node_errors(gfs_batch *b, uint64_t z, double ratio, gfs_node_erro
                            void *hip_stream);
 /* test hook: caps the grids over flat tiles and paths of K7h and K7i at max_blocks workgroups; 0 restores the default.  No result changes. */
 int  gfs_batch_debug_tile_blocks(gfs_batch *b, uint64_t max_blocks);
+
+/* ---- the sort quality of every item (K7k): gfs_ctx_sort_quality of a whole batch of 1D sorts in one call ----
+ * One launch per padded segment length present (at most 8), one step launch and one reduce launch, whatever the number of items;
+ * an item of more than GFS_SEGMENT_SORT_CAP nodes takes gfs_ctx_sort_quality's own sort and scan once.  The inputs go up in one
+ * copy from the batch's pinned staging, the results come back in one; nothing is allocated per call once the scratch has grown.
+ * GFS_E_ARG for a null batch or out, or n != the batch's items; GFS_E_UNSUPPORTED for a batch of layouts; GFS_E_STATE, naming the
+ * item, for an item that is not a set-up 1D context — all before any device call; GFS_E_UNSUPPORTED, naming the item, for an item
+ * of 2^53 bp or more (its length comes back with the results).  out is written only where the call succeeds.  An item without
+ * nodes or with fewer than two steps gives a row of zeros.  Synchronises; nothing but the output is written: positions, RNG
+ * streams and counters are untouched. */
+/* gfs_ctx_sort_quality of every item of a batch of 1D sorts, bit for bit; out[n], n = the batch's items. */
+int  gfs_batch_sort_quality(gfs_batch *b, gfs_sort_quality *out, uint64_t n, double *kernel_ms /*nullable*/, void *hip_stream);
 
 /* ---- context sets: the contexts of many small graphs built in one pass ----
  * gfs_ctx_create costs about the same however small the graph is: a score of allocations, six blocking uploads, three sorts, a scan
