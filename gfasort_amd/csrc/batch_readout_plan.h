@@ -107,7 +107,8 @@ inline uint64_t segment_launch_order(const uint64_t *n_nodes, uint64_t n, uint64
     return within;
 }
 // the row behind the last one of the launch that starts at row `first` (< within): the rows of one padded length
-inline uint64_t segment_launch_end(const uint64_t *n_nodes, const uint64_t *order, uint64_t first, uint64_t within, uint64_t cap) {
+// (kept out of line, as it has been: called once per launch, and the shared object's list of symbols stays what it was)
+__attribute__((noinline)) inline uint64_t segment_launch_end(const uint64_t *n_nodes, const uint64_t *order, uint64_t first, uint64_t within, uint64_t cap) {
     const uint64_t P = segment_group_of(n_nodes[order[first]], cap);
     uint64_t end = first;
     while (end < within && segment_group_of(n_nodes[order[end]], cap) == P) ++end;

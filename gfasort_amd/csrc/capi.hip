@@ -726,7 +726,7 @@ int gfs_ctx_sort_order(gfs_ctx *c, uint64_t *order, uint64_t n) {
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipDeviceSynchronize());
     gfs::Buffer d_tmp;
-    if (int rc = d_tmp.reserve(n * (2 * 8 + 2 * 4))) return rc;
+    if (int rc = d_tmp.reserve(gfs::sort_order_scratch_bytes(n))) return rc;
     uint32_t *d_order = nullptr;
     hipError_t e = gfs::sort_order_device(c->d_x, c->d_perm, n, 1, d_tmp.p, &d_order);
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("sort_order_device: ") + hipGetErrorString(e));
@@ -759,15 +759,27 @@ gfs_pair_error gfs::unpack_pair_error(uint64_t z, const uint64_t *w) {
     std::memcpy(&o.sum_abs, &w[3], 8); std::memcpy(&o.sum_sq, &w[4], 8);
     return o;
 }
+gfs_sort_quality gfs::unpack_sort_quality(const uint64_t *w) {
+    gfs_sort_quality o{w[0], w[1], w[2], 0.0};
+    std::memcpy(&o.sq_err_sum, &w[3], 8);
+    return o;
+}
+int gfs::check_sorted_length(uint64_t total_bp, int64_t batch_item) {
+    if (total_bp < (1ull << 53)) return GFS_OK;
+    return fail(GFS_E_UNSUPPORTED, (batch_item < 0 ? "" : "batch item " + std::to_string(batch_item) + ": ") + "a graph of 2^53 bp or more");
+}
 
 extern "C" {
 
+static uint64_t *scratch_words(const gfs_ctx *c, uint64_t part) { return gfs::Region::at<uint64_t>(c->d_quality.p, part); }   // a part of an entry's map
 // the duration of an entry's device work on stderr under GFS_TIMING: only then does the entry's event pair come into being
 static void start_if_timing(gfs::EventPair &timer, hipStream_t st) { if (std::getenv("GFS_TIMING")) (void)timer.start(st); }
-static void report_timing(const gfs::EventPair &timer, const char *what, uint64_t z, uint64_t n_steps) {   // after the stream was synchronised
+// after the stream was synchronised; `count` is a step distance, or (before = "", after = " step distances") how many there were
+static void report_timing(const gfs::EventPair &timer, const char *what, uint64_t count, uint64_t n_steps, const char *before = "z = ", const char *after = "") {
     float ms = 0.f;
     if (timer.elapsed(&ms))
-        std::fprintf(stderr, "[%s] z = %llu, %llu steps: kernels %.4f ms\n", what, (unsigned long long)z, (unsigned long long)n_steps, ms);
+        std::fprintf(stderr, "[%s] %s%llu%s, %llu steps: kernels %.4f ms\n", what, before, (unsigned long long)count, after,
+                     (unsigned long long)n_steps, ms);
 }
 
 int gfs_ctx_pair_errors(gfs_ctx *c, const uint64_t *zs, uint64_t n_z, gfs_pair_error *out, void *hip_stream) {
@@ -779,10 +791,10 @@ int gfs_ctx_pair_errors(gfs_ctx *c, const uint64_t *zs, uint64_t n_z, gfs_pair_e
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const uint64_t blocks = gfs::quality_blocks(c->n_steps);
-    // scratch: [zs | out words | partials]
-    rc = c->d_quality.reserve(8 * (n_z + 5 * n_z + 5 * n_z * blocks));
-    if (rc) return rc;
-    uint64_t *d_zs = c->d_quality.as<uint64_t>(), *d_out = d_zs + n_z, *d_partials = d_out + 5 * n_z;
+    gfs::Region map;                                                       // scratch: [zs | out words | partials]
+    const uint64_t zs_at = map.add(8 * n_z), out_at = map.add(8 * 5 * n_z), partials_at = map.add(8 * 5 * n_z * blocks);
+    if ((rc = c->d_quality.reserve(map.bytes()))) return rc;
+    uint64_t *d_zs = scratch_words(c, zs_at), *d_out = scratch_words(c, out_at), *d_partials = scratch_words(c, partials_at);
     HIPCHK(hipMemcpyAsync(d_zs, zs, n_z * 8, hipMemcpyHostToDevice, st));
     gfs::EventPair timer;
     start_if_timing(timer, st);
@@ -793,10 +805,7 @@ int gfs_ctx_pair_errors(gfs_ctx *c, const uint64_t *zs, uint64_t n_z, gfs_pair_e
     std::vector<uint64_t> w(5 * n_z);
     HIPCHK(hipMemcpyAsync(w.data(), d_out, w.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    float ms = 0.f;
-    if (timer.elapsed(&ms))
-        std::fprintf(stderr, "[gfs_ctx_pair_errors] %llu step distances, %llu steps: kernels %.4f ms\n", (unsigned long long)n_z,
-                     (unsigned long long)c->n_steps, ms);
+    report_timing(timer, "gfs_ctx_pair_errors", n_z, c->n_steps, "", " step distances");
     for (uint64_t k = 0; k < n_z; ++k) out[k] = gfs::unpack_pair_error(zs[k], &w[5 * k]);
     return GFS_OK;
 }
@@ -811,10 +820,11 @@ int gfs_ctx_stress_of_pairs(gfs_ctx *c, const uint64_t *step_a, const uint64_t *
     if (n == 0) return GFS_OK;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipDeviceSynchronize());
-    int rc = c->d_quality.reserve(8 * 3 * n);                              // [step_a | step_b | rel_sq]
-    if (rc) return rc;
-    uint64_t *d_a = c->d_quality.as<uint64_t>(), *d_b = d_a + n;
-    double *d_rel = reinterpret_cast<double *>(d_b + n);
+    gfs::Region map;                                                       // scratch: [step_a | step_b | rel_sq]
+    const uint64_t a_at = map.add(8 * n), b_at = map.add(8 * n), rel_at = map.add(8 * n);
+    if (int rc = c->d_quality.reserve(map.bytes())) return rc;
+    uint64_t *d_a = scratch_words(c, a_at), *d_b = scratch_words(c, b_at);
+    double *d_rel = map.at<double>(c->d_quality.p, rel_at);
     HIPCHK(hipMemcpy(d_a, step_a, n * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_b, step_b, n * 8, hipMemcpyHostToDevice));
     hipError_t e = gfs::pair_list_device(c->d_step_rec, c->n_steps, c->d_x, c->n_nodes, (uint32_t)c->dims, d_a, d_b, n, d_rel, nullptr);
@@ -838,24 +848,25 @@ int gfs_ctx_sort_quality(gfs_ctx *c, gfs_sort_quality *out) {
     HIPCHK(hipDeviceSynchronize());
     const uint64_t n = c->n_nodes, blocks = gfs::quality_blocks(c->n_steps);
     gfs::Buffer d_sort;
-    int rc = d_sort.reserve(n * (2 * 8 + 2 * 4));
+    int rc = d_sort.reserve(gfs::sort_order_scratch_bytes(n));
     if (rc) return rc;
     uint32_t *d_order = nullptr;
     hipError_t e = gfs::sort_order_device(c->d_x, c->d_perm, n, 1, d_sort.p, &d_order);
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("sort_order_device: ") + hipGetErrorString(e));
-    rc = c->d_quality.reserve(8 * ((n + 1) + n + 5 * blocks + 5));         // [prefix | sorted positions | partials | out]
-    if (rc) return rc;
-    uint64_t *d_prefix = c->d_quality.as<uint64_t>(), *d_spos = d_prefix + n + 1, *d_partials = d_spos + n, *d_out = d_partials + 5 * blocks;
+    gfs::Region map;                                                       // scratch: [prefix | sorted positions | partials | out]
+    const uint64_t prefix_at = map.add(8 * (n + 1)), spos_at = map.add(8 * n), partials_at = map.add(8 * 5 * blocks), out_at = map.add(8 * 5);
+    if ((rc = c->d_quality.reserve(map.bytes()))) return rc;
+    uint64_t *d_prefix = scratch_words(c, prefix_at), *d_spos = scratch_words(c, spos_at), *d_partials = scratch_words(c, partials_at);
+    uint64_t *d_out = scratch_words(c, out_at);
     uint64_t total_len = 0;
     e = gfs::sort_quality_device(c->d_step_rec, c->n_steps, d_order, c->d_node_len, c->d_perm, n, d_prefix, d_spos, d_partials, d_out,
                                  &total_len, nullptr);
     d_sort.reset();
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("sort_quality_device: ") + hipGetErrorString(e));
-    if (total_len >= (1ull << 53)) return fail(GFS_E_UNSUPPORTED, "a graph of 2^53 bp or more");
+    if ((rc = gfs::check_sorted_length(total_len))) return rc;
     uint64_t w[5];
     HIPCHK(hipMemcpy(w, d_out, sizeof w, hipMemcpyDeviceToHost));
-    out->steps = w[0]; out->abs_err_sum = w[1]; out->genomic_sum = w[2];
-    std::memcpy(&out->sq_err_sum, &w[3], 8);
+    *out = gfs::unpack_sort_quality(w);
     return GFS_OK;
 }
 
@@ -867,13 +878,13 @@ int gfs_ctx_path_errors(gfs_ctx *c, uint64_t z, double ratio, gfs_path_error *ou
     if (n_paths != c->n_paths) return fail(GFS_E_ARG, "n_paths does not match the context");
     if (!c->d_x) return fail(GFS_E_STATE, "the context has no positions (not set up)");
     if (n_paths == 0) return GFS_OK;
-    static_assert(sizeof(gfs_path_error) == 8 * 8, "K7d writes gfs_path_error as 8 words");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const uint64_t tiles = gfs::quality_tiles(c->n_steps);
-    rc = c->d_quality.reserve(8 * (8 * n_paths + 10 * tiles));             // [out | head partials | tail partials]
-    if (rc) return rc;
-    uint64_t *d_out = c->d_quality.as<uint64_t>(), *d_head = d_out + 8 * n_paths, *d_tail = d_head + 5 * tiles;
+    gfs::Region map;                                                       // scratch: [out | head partials | tail partials]
+    const uint64_t out_at = map.add(n_paths * sizeof(gfs_path_error)), head_at = map.add(8 * 5 * tiles), tail_at = map.add(8 * 5 * tiles);
+    if ((rc = c->d_quality.reserve(map.bytes()))) return rc;
+    uint64_t *d_out = scratch_words(c, out_at), *d_head = scratch_words(c, head_at), *d_tail = scratch_words(c, tail_at);
     gfs::EventPair timer;
     start_if_timing(timer, st);
     hipError_t e = gfs::path_errors_device(c->d_step_rec, c->n_steps, c->d_path_rec, n_paths, c->d_x, c->n_nodes, (uint32_t)c->dims, z, ratio,
@@ -893,13 +904,13 @@ int gfs_ctx_stretched_pairs(gfs_ctx *c, uint64_t z, double ratio, gfs_stretched_
     int rc = gfs::check_diagnosis(z, ratio);
     if (rc) return rc;
     if (!c->d_x) return fail(GFS_E_STATE, "the context has no positions (not set up)");
-    static_assert(sizeof(gfs_stretched_pair) == 5 * 8, "K7e writes gfs_stretched_pair as 5 words");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const uint64_t tiles = gfs::quality_tiles(c->n_steps), room = std::min(cap, c->n_steps);
-    rc = c->d_quality.reserve(8 * (2 * (tiles + 1) + 5 * room));           // [tile counts | offsets | list]
-    if (rc) return rc;
-    uint64_t *d_counts = c->d_quality.as<uint64_t>(), *d_offsets = d_counts + tiles + 1, *d_list = d_offsets + tiles + 1;
+    gfs::Region map;                                                       // scratch: [tile counts | offsets | list]
+    const uint64_t counts_at = map.add(8 * (tiles + 1)), offsets_at = map.add(8 * (tiles + 1)), list_at = map.add(room * sizeof(gfs_stretched_pair));
+    if ((rc = c->d_quality.reserve(map.bytes()))) return rc;
+    uint64_t *d_counts = scratch_words(c, counts_at), *d_offsets = scratch_words(c, offsets_at), *d_list = scratch_words(c, list_at);
     gfs::EventPair timer;
     start_if_timing(timer, st);
     hipError_t e = gfs::stretched_pairs_device(c->d_step_rec, c->n_steps, c->d_x, c->n_nodes, (uint32_t)c->dims, z, ratio, d_counts, d_offsets,
@@ -920,12 +931,12 @@ int gfs_ctx_node_errors(gfs_ctx *c, uint64_t z, double ratio, gfs_node_error *ou
     if (n_nodes != c->n_nodes) return fail(GFS_E_ARG, "n_nodes does not match the context");
     if (!c->d_x) return fail(GFS_E_STATE, "the context has no positions (not set up)");
     if (n_nodes == 0) return GFS_OK;
-    static_assert(sizeof(gfs_node_error) == 3 * 8, "K7f writes gfs_node_error as 3 words");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    rc = c->d_quality.reserve(8 * 6 * n_nodes);                            // [per slot: pairs | stretched | max] [out]
-    if (rc) return rc;
-    uint64_t *d_slots = c->d_quality.as<uint64_t>(), *d_out = d_slots + 3 * n_nodes;
+    gfs::Region map;                                                       // scratch: [per slot: pairs | stretched | max] [out]
+    const uint64_t slots_at = map.add(n_nodes * sizeof(gfs_node_error)), out_at = map.add(n_nodes * sizeof(gfs_node_error));
+    if ((rc = c->d_quality.reserve(map.bytes()))) return rc;
+    uint64_t *d_slots = scratch_words(c, slots_at), *d_out = scratch_words(c, out_at);
     gfs::EventPair timer;
     start_if_timing(timer, st);
     hipError_t e = gfs::node_errors_device(c->d_step_rec, c->n_steps, c->d_x, c->d_perm, n_nodes, (uint32_t)c->dims, z, ratio, d_slots, d_out, st);

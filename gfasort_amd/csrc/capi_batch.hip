@@ -2,6 +2,8 @@
 // capi_ctx.h) in one persistent launch (K1f / K2f, sgd_kernels_batch.hip), and their start positions, read-outs, coordinates and
 // pair errors in one launch each (K4b / K6b, K4c / K6c, K7g), and their diagnosis — errors per path, stretched pairs, errors per node —
 // and their sort quality in a constant number of launches (K7h, K7i, K7j; K7k).
+// A read-out maps its one allocation with a gfs::Region (readout_region.h) and makes one RoundTrip through it; its checks, its plan,
+// its table fill, its launch and its unpacking are its own.
 #include "capi_ctx.h"
 #include "sgd_batch.h"
 #include "batch_plan.h"
@@ -47,13 +49,83 @@ struct gfs_batch {
 };
 static_assert(GFS_SEGMENT_SORT_CAP == gfs::SEGMENT_SORT_CAP, "the header's cap is the network's");
 
-static void read_kernel_ms(const gfs::EventPair &timer, double *kernel_ms) {
-    float t = 0.f;
-    if (kernel_ms && timer.elapsed(&t)) *kernel_ms = t;
-}
 static bool batch_item_idle(const gfs_ctx *c) { return !c->valid_paths || c->n_nodes == 0; }
 static bool batch_eligible(const gfs_ctx *c) {
     return gfs::batch_eligible(c->shape, c->cfg.trace_per_stream != 0, c->d_its_all != nullptr, batch_item_idle(c));
+}
+
+// one count of every item (&gfs_ctx::n_nodes, n_steps, n_paths), as the plans of batch_readout_plan.h take them
+static std::vector<uint64_t> item_counts(const gfs_batch *b, uint64_t gfs_ctx::*count) {
+    std::vector<uint64_t> counts(b->ctxs.size());
+    for (size_t i = 0; i < counts.size(); ++i) counts[i] = b->ctxs[i]->*count;
+    return counts;
+}
+// where each item's rows start in an output packed by node (or by path); one entry more than items: the total
+static std::vector<uint64_t> batch_offsets(const gfs_batch *b, uint64_t gfs_ctx::*count = &gfs_ctx::n_nodes) {
+    const std::vector<uint64_t> counts = item_counts(b, count);
+    std::vector<uint64_t> offsets(counts.size() + 1);
+    gfs::row_offsets(counts.data(), counts.size(), offsets.data());
+    return offsets;
+}
+// the row of K4b / K6b / K7k for context c as it is now (positions may have been bound anew; it has fewer than 2^31 nodes)
+static gfs::ReadoutItem readout_row(const gfs_ctx *c, uint64_t offset, uint32_t padded) { return {c->d_x, c->d_perm, c->d_node_len, offset, (uint32_t)c->n_nodes, padded}; }
+
+// One read-out's round trip through one allocation mapped by a gfs::Region (readout_region.h): a device buffer of the batch and, for
+// the parts up to staged(), the batch's pinned staging at the same offsets.  An entry reserves, fills the tables in h, uploads them
+// (the timer starts), launches, and finishes: the launch's verdict, the timer's stop, the results back into h, the wait, kernel_ms.
+struct GFS_LOCAL RoundTrip {
+    gfs_batch *b; hipStream_t st;
+    unsigned char *h = nullptr, *d = nullptr;                              // the staging and the device buffer, once reserved
+    template <typename T> T *host(uint64_t part) const { return gfs::Region::at<T>(h, part); }
+    template <typename T> T *device(uint64_t part) const { return gfs::Region::at<T>(d, part); }
+    int reserve(const gfs::Region &map, gfs::Buffer *dev) {                // (dev null: the staging alone)
+        int rc = b->h_packed.reserve(map.staged());
+        if (!rc && dev) rc = dev->reserve(map.bytes());
+        h = b->h_packed.as<unsigned char>(); d = dev ? dev->as<unsigned char>() : nullptr;
+        return rc;
+    }
+    int start() { HIPCHK(b->readout_timer.start(st)); return GFS_OK; }
+    int upload(uint64_t from, uint64_t to) {                               // ... and the timer's start behind it
+        HIPCHK(hipMemcpyAsync(d + from, h + from, to - from, hipMemcpyHostToDevice, st));
+        return start();
+    }
+    int finish(hipError_t launched, const char *what, uint64_t from, uint64_t to, double *kernel_ms) {
+        if (launched != hipSuccess) return fail(GFS_E_HIP, std::string(what) + ": " + hipGetErrorString(launched));
+        HIPCHK(b->readout_timer.stop(st));
+        if (to > from) HIPCHK(hipMemcpyAsync(h + from, d + from, to - from, hipMemcpyDeviceToHost, st));
+        return wait(kernel_ms);
+    }
+    int wait(double *kernel_ms) {
+        HIPCHK(hipStreamSynchronize(st));
+        float t = 0.f;
+        if (kernel_ms && b->readout_timer.elapsed(&t)) *kernel_ms = t;
+        return GFS_OK;
+    }
+};
+
+// One launch per padded segment length (K6b, K7k): launch(first, end, padded) for the rows [first, end) of by_len, which share it.
+template <typename Launch>
+static int for_each_segment_launch(const std::vector<uint64_t> &nodes, const std::vector<uint64_t> &by_len, uint64_t within, uint64_t cap, Launch launch) {
+    for (uint64_t first = 0, end; first < within; first = end) {
+        end = gfs::segment_launch_end(nodes.data(), by_len.data(), first, within, cap);
+        if (int rc = launch(first, end, (uint32_t)gfs::segment_group_of(nodes[by_len[first]], cap))) return rc;
+    }
+    return GFS_OK;
+}
+// An item above the sort cap: K6 (rocPRIM radix sort) for it alone, in the batch's sort scratch with `extra` bytes of the caller's behind
+// K6's own, then then(c, d_sorted, those bytes) on st.  Two waits: K6 runs on the null stream, and the scratch is the next item's.
+template <typename Then>
+static int sort_item_above_cap(gfs_batch *b, uint64_t item, uint64_t extra, hipStream_t st, Then then) {
+    const gfs_ctx *c = b->ctxs[item];
+    const uint64_t sort_bytes = gfs::sort_order_scratch_bytes(c->n_nodes);
+    HIPCHK(hipStreamSynchronize(st));
+    if (int rc = b->d_sort_tmp.reserve(sort_bytes + extra)) return rc;
+    uint32_t *d_sorted = nullptr;
+    hipError_t e = gfs::sort_order_device(c->d_x, c->d_perm, c->n_nodes, 1, b->d_sort_tmp.p, &d_sorted);
+    if (e != hipSuccess) return fail(GFS_E_HIP, "batch item " + std::to_string(item) + ": sort_order_device: " + hipGetErrorString(e));
+    if (int rc = then(c, d_sorted, b->d_sort_tmp.as<unsigned char>() + sort_bytes)) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    return GFS_OK;
 }
 
 extern "C" {
@@ -256,17 +328,6 @@ int gfs_batch_get_stats(gfs_batch *b, gfs_batch_stats *out) {
 }
 
 // ---- K4b / K6b: every item's start positions, and every item's positions and rank order, in one launch ------------------------
-// where each item starts in the packed outputs (the nodes of the items before it); one entry more than items: the total
-static std::vector<uint64_t> batch_offsets(const gfs_batch *b) {
-    std::vector<uint64_t> offsets(b->ctxs.size() + 1, 0);
-    for (size_t i = 0; i < b->ctxs.size(); ++i) offsets[i + 1] = offsets[i] + b->ctxs[i]->n_nodes;
-    return offsets;
-}
-static std::vector<uint64_t> batch_nodes(const gfs_batch *b) {
-    std::vector<uint64_t> nodes(b->ctxs.size());
-    for (size_t i = 0; i < nodes.size(); ++i) nodes[i] = b->ctxs[i]->n_nodes;
-    return nodes;
-}
 // the checks gfs_ctx_init_positions and gfs_ctx_sort_order make, on every item; no device call
 static int batch_readout_check(const gfs_batch *b) {
     if (b->dims != 0) return fail(GFS_E_UNSUPPORTED, "a batch of layouts has no start positions or rank order (dims=" + std::to_string(b->dims) +
@@ -277,31 +338,29 @@ static int batch_readout_check(const gfs_batch *b) {
     }
     return GFS_OK;
 }
-// The item table from the contexts as they are now (positions may have been bound anew), in the order `order` lists them;
-// offsets are those of gfs_batch_result_offsets.  Uploaded on st.
+// The item table from the contexts as they are now, in the order `order` lists them; offsets are those of gfs_batch_result_offsets.
+// Uploaded on st.
 static int batch_readout_table(gfs_batch *b, const std::vector<uint64_t> &order, hipStream_t st) {
     if (int rc = b->d_readout.reserve(b->ctxs.size() * sizeof(gfs::ReadoutItem))) return rc;
     const std::vector<uint64_t> offset = batch_offsets(b);
     b->h_readout.resize(order.size());
     for (size_t r = 0; r < order.size(); ++r) {
         const gfs_ctx *c = b->ctxs[order[r]];
-        gfs::ReadoutItem &it = b->h_readout[r];
-        it.x = c->d_x; it.perm = c->d_perm; it.node_len = c->d_node_len;
-        it.offset = offset[order[r]];
-        it.n = (uint32_t)c->n_nodes;                                       // (a context has fewer than 2^31 nodes)
-        it.padded = c->n_nodes <= gfs::SEGMENT_SORT_CAP ? gfs::segment_padded(it.n) : 0;
+        b->h_readout[r] = readout_row(c, offset[order[r]], c->n_nodes <= gfs::SEGMENT_SORT_CAP ? gfs::segment_padded((uint32_t)c->n_nodes) : 0);
     }
     if (!order.empty())
         HIPCHK(hipMemcpyAsync(b->d_readout.p, b->h_readout.data(), order.size() * sizeof(gfs::ReadoutItem), hipMemcpyHostToDevice, st));
     return GFS_OK;
 }
+static int copy_offsets(const std::vector<uint64_t> &of, uint64_t *offsets, uint64_t n) {
+    if (n != of.size()) return fail(GFS_E_ARG, "offsets: need items + 1 entries");
+    std::copy(of.begin(), of.end(), offsets);
+    return GFS_OK;
+}
 
 int gfs_batch_result_offsets(const gfs_batch *b, uint64_t *offsets, uint64_t n) {
     if (!b || !offsets) return fail(GFS_E_ARG, "null argument");
-    if (n != b->ctxs.size() + 1) return fail(GFS_E_ARG, "offsets: need items + 1 entries");
-    const std::vector<uint64_t> of = batch_offsets(b);
-    std::copy(of.begin(), of.end(), offsets);
-    return GFS_OK;
+    return copy_offsets(batch_offsets(b), offsets, n);
 }
 
 int gfs_batch_debug_sort_cap(gfs_batch *b, uint64_t cap) {
@@ -320,8 +379,7 @@ int gfs_batch_init_positions(gfs_batch *b, void *hip_stream) {
     hipStream_t st = (hipStream_t)hip_stream;
     std::vector<uint64_t> all(b->ctxs.size());
     std::iota(all.begin(), all.end(), 0ull);
-    rc = batch_readout_table(b, all, st);
-    if (rc) return rc;
+    if ((rc = batch_readout_table(b, all, st))) return rc;
     hipError_t e = gfs::batch_init_positions_device(b->d_readout.as<gfs::ReadoutItem>(), (uint32_t)all.size(), st);
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch init_positions: ") + hipGetErrorString(e));
     HIPCHK(hipStreamSynchronize(st));
@@ -344,58 +402,46 @@ int gfs_batch_results(gfs_batch *b, double *positions, uint32_t *order, uint64_t
     double *const d_positions = b->d_positions.as<double>();
     uint32_t *const d_order = b->d_order.as<uint32_t>();
     // items within the cap by the length of their padded segment: one launch per length, its LDS and block sized by it; the others after them
-    const std::vector<uint64_t> nodes = batch_nodes(b);
+    const std::vector<uint64_t> nodes = item_counts(b, &gfs_ctx::n_nodes);
     std::vector<uint64_t> by_len(nodes.size());
     const uint64_t within = gfs::segment_launch_order(nodes.data(), nodes.size(), b->sort_cap, by_len.data());
-    rc = batch_readout_table(b, by_len, st);
-    if (rc) return rc;
-    HIPCHK(b->readout_timer.start(st));
-    for (uint64_t first = 0; first < within;) {
-        const uint64_t P = gfs::segment_group_of(nodes[by_len[first]], b->sort_cap);
-        const uint64_t end = gfs::segment_launch_end(nodes.data(), by_len.data(), first, within, b->sort_cap);
+    if ((rc = batch_readout_table(b, by_len, st))) return rc;
+    RoundTrip rt{b, st};
+    if ((rc = rt.start())) return rc;
+    rc = for_each_segment_launch(nodes, by_len, within, b->sort_cap, [&](uint64_t first, uint64_t end, uint32_t padded) -> int {
         for (uint64_t at = first; at < end; at += 0x7FFFFFFFull) {         // (a grid's x dimension)
             const uint32_t count = (uint32_t)std::min<uint64_t>(end - at, 0x7FFFFFFFull);
-            hipError_t e = gfs::sort_segments_device(b->d_readout.as<gfs::ReadoutItem>() + at, count, (uint32_t)P, positions ? d_positions : nullptr, d_order, st);
+            hipError_t e = gfs::sort_segments_device(b->d_readout.as<gfs::ReadoutItem>() + at, count, padded, positions ? d_positions : nullptr, d_order, st);
             if (e != hipSuccess) return fail(GFS_E_HIP, std::string("segment sort launch: ") + hipGetErrorString(e));
         }
-        first = end;
-    }
-    // above the cap: K6 (rocPRIM radix sort) once each, into the same packed arrays
-    for (size_t r = within; r < by_len.size(); ++r) {
-        const gfs_ctx *c = b->ctxs[by_len[r]];
-        const gfs::ReadoutItem &it = b->h_readout[r];
-        const uint64_t n = c->n_nodes, need = n * (2 * 8 + 2 * 4);
-        HIPCHK(hipStreamSynchronize(st));                                  // (K6 runs on the null stream)
-        rc = b->d_sort_tmp.reserve(need);
-        if (rc) return rc;
-        uint32_t *d_sorted = nullptr;
-        hipError_t e = gfs::sort_order_device(c->d_x, c->d_perm, n, 1, b->d_sort_tmp.p, &d_sorted);
-        if (e != hipSuccess) return fail(GFS_E_HIP, "batch item " + std::to_string(by_len[r]) + ": sort_order_device: " + hipGetErrorString(e));
-        HIPCHK(hipMemcpyAsync(d_order + it.offset, d_sorted, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-        if (positions) {
-            e = gfs::reorder_positions_device(c->d_x, d_positions + it.offset, c->d_perm, n, 0, 0, st);
-            if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch positions: ") + hipGetErrorString(e));
-        }
-        HIPCHK(hipStreamSynchronize(st));                                  // (the scratch is the next item's)
-    }
+        return GFS_OK;
+    });
+    // above the cap: K6 once each, into the same packed arrays
+    for (size_t r = within; r < by_len.size() && !rc; ++r)
+        rc = sort_item_above_cap(b, by_len[r], 0, st, [&](const gfs_ctx *c, const uint32_t *d_sorted, void *) -> int {
+            const uint64_t offset = b->h_readout[r].offset;
+            HIPCHK(hipMemcpyAsync(d_order + offset, d_sorted, c->n_nodes * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+            if (!positions) return GFS_OK;
+            hipError_t e = gfs::reorder_positions_device(c->d_x, d_positions + offset, c->d_perm, c->n_nodes, 0, 0, st);
+            return e == hipSuccess ? GFS_OK : fail(GFS_E_HIP, std::string("batch positions: ") + hipGetErrorString(e));
+        });
+    if (rc) return rc;
     HIPCHK(b->readout_timer.stop(st));
     // The two copies go through pinned memory of the batch: a copy of megabytes straight into the caller's pageable buffer has
     // the runtime pin those pages first, 20-30 ms where they are fresh (profiles/r10/batch_readout_probe_pageable.log).
-    rc = b->h_packed.reserve(total * (sizeof(double) + sizeof(uint32_t)));
-    if (rc) return rc;
-    double *h_positions = b->h_packed.as<double>();
-    uint32_t *h_order = reinterpret_cast<uint32_t *>(h_positions + total);
-    if (positions && total) HIPCHK(hipMemcpyAsync(h_positions, d_positions, total * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (order && total) HIPCHK(hipMemcpyAsync(h_order, d_order, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (positions && total) std::memcpy(positions, h_positions, total * sizeof(double));
-    if (order && total) std::memcpy(order, h_order, total * sizeof(uint32_t));
-    read_kernel_ms(b->readout_timer, kernel_ms);
+    gfs::Region map;                                                       // the staging alone: [positions | order]
+    const uint64_t positions_at = map.add(total * sizeof(double)), order_at = map.add(total * sizeof(uint32_t));   map.end_staging();
+    if ((rc = rt.reserve(map, nullptr))) return rc;
+    if (positions && total) HIPCHK(hipMemcpyAsync(rt.h + positions_at, d_positions, total * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (order && total) HIPCHK(hipMemcpyAsync(rt.h + order_at, d_order, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if ((rc = rt.wait(kernel_ms))) return rc;
+    if (positions && total) std::memcpy(positions, rt.h + positions_at, total * sizeof(double));
+    if (order && total) std::memcpy(order, rt.h + order_at, total * sizeof(uint32_t));
     return GFS_OK;
 }
 
 // ---- K4c / K6c: every item's layout coordinates, up or down, in one launch and one copy of coordinates -------------------------
-// The checks of both directions, on every item; no device call.  *total_out = the packed length in doubles.
+// The checks of both directions, on every item; no device call.
 static int batch_coords_check(const gfs_batch *b, const double *coords, uint64_t total) {
     if (!b) return fail(GFS_E_ARG, "batch is null");
     if (!coords) return fail(GFS_E_ARG, "coords is null");
@@ -411,57 +457,44 @@ static int batch_coords_check(const gfs_batch *b, const double *coords, uint64_t
     if (total != want) return fail(GFS_E_ARG, "total is not the batch's node count * 2 * dimensions (gfs_batch_result_offsets)");
     return GFS_OK;
 }
-// One call either way.  Device buffer and pinned staging: [packed coordinates | CoordItem table | block table]; up, the whole of it
-// goes in one copy; down, the two tables go up and the coordinates come back.
+// One call either way: up, the whole region goes in one copy; down, the two tables go up and the coordinates come back.
 static int batch_coords_move(gfs_batch *b, double *coords, uint64_t total, int to_device, double *kernel_ms, hipStream_t st) {
+    int rc = batch_coords_check(b, coords, total);
+    if (rc) return rc;
     if (kernel_ms) *kernel_ms = 0.0;
     const uint64_t n = b->ctxs.size();
-    std::vector<uint64_t> nodes(n), word_offset(n + 1), first_block(n + 1);
-    for (uint64_t i = 0; i < n; ++i) nodes[i] = b->ctxs[i]->n_nodes;
+    const std::vector<uint64_t> nodes = item_counts(b, &gfs_ctx::n_nodes);
+    std::vector<uint64_t> word_offset(n + 1), first_block(n + 1);
     const uint64_t blocks = gfs::coord_plan(nodes.data(), n, (uint32_t)b->dims, word_offset.data(), first_block.data());
     if (blocks > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, "the batch's coordinates exceed one launch");
     if (total == 0) return GFS_OK;
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipDeviceSynchronize());                                        // as gfs_ctx_download_positions: nothing of an item is in flight
-    const uint64_t tables_at = total * sizeof(double), blocks_at = tables_at + n * sizeof(gfs::CoordItem);
-    const uint64_t bytes = blocks_at + blocks * sizeof(uint32_t);
-    int rc = b->h_packed.reserve(bytes);
-    if (!rc) rc = b->d_coords.reserve(bytes);
-    if (rc) return rc;
-    unsigned char *h = b->h_packed.as<unsigned char>(), *d = b->d_coords.as<unsigned char>();
-    gfs::CoordItem *h_items = reinterpret_cast<gfs::CoordItem *>(h + tables_at);
+    gfs::Region map;                                                       // [packed coordinates | CoordItem table | block table]
+    const uint64_t coords_at = map.add(total * sizeof(double)), items_at = map.add(n * sizeof(gfs::CoordItem));
+    const uint64_t blocks_at = map.add(blocks * sizeof(uint32_t));   map.end_upload(); map.end_staging();
+    RoundTrip rt{b, st};
+    if ((rc = rt.reserve(map, &b->d_coords))) return rc;
+    gfs::CoordItem *h_items = rt.host<gfs::CoordItem>(items_at);
     for (uint64_t i = 0; i < n; ++i) {                                     // from the contexts as they are now (positions may have been bound anew)
         const gfs_ctx *c = b->ctxs[i];
         h_items[i] = gfs::CoordItem{c->d_x, c->d_perm, word_offset[i], (uint32_t)c->n_nodes, (uint32_t)first_block[i], (uint32_t)b->dims, 0u};
     }
-    gfs::block_item_table(first_block.data(), n, reinterpret_cast<uint32_t *>(h + blocks_at));
-    if (to_device) {
-        std::memcpy(h, coords, total * sizeof(double));
-        HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
-    } else {
-        HIPCHK(hipMemcpyAsync(d + tables_at, h + tables_at, bytes - tables_at, hipMemcpyHostToDevice, st));
-    }
-    HIPCHK(b->readout_timer.start(st));
-    hipError_t e = gfs::batch_coords_device(reinterpret_cast<const gfs::CoordItem *>(d + tables_at), reinterpret_cast<const uint32_t *>(d + blocks_at),
-                                            blocks, reinterpret_cast<double *>(d), to_device, st);
-    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch coordinates launch: ") + hipGetErrorString(e));
-    HIPCHK(b->readout_timer.stop(st));
-    if (!to_device) HIPCHK(hipMemcpyAsync(h, d, total * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (!to_device) std::memcpy(coords, h, total * sizeof(double));
-    read_kernel_ms(b->readout_timer, kernel_ms);
+    gfs::block_item_table(first_block.data(), n, rt.host<uint32_t>(blocks_at));
+    if (to_device) std::memcpy(rt.h + coords_at, coords, total * sizeof(double));
+    if ((rc = rt.upload(to_device ? coords_at : items_at, map.uploaded()))) return rc;
+    hipError_t e = gfs::batch_coords_device(rt.device<const gfs::CoordItem>(items_at), rt.device<const uint32_t>(blocks_at), blocks,
+                                            rt.device<double>(coords_at), to_device, st);
+    if ((rc = rt.finish(e, "batch coordinates launch", coords_at, coords_at + (to_device ? 0 : total * sizeof(double)), kernel_ms))) return rc;
+    if (!to_device) std::memcpy(coords, rt.h + coords_at, total * sizeof(double));
     return GFS_OK;
 }
 
 int gfs_batch_upload_coords(gfs_batch *b, const double *coords, uint64_t total, void *hip_stream) {
-    int rc = batch_coords_check(b, coords, total);
-    if (rc) return rc;
     return batch_coords_move(b, const_cast<double *>(coords), total, 1, nullptr, (hipStream_t)hip_stream);
 }
 
 int gfs_batch_coords(gfs_batch *b, double *coords, uint64_t total, double *kernel_ms, void *hip_stream) {
-    int rc = batch_coords_check(b, coords, total);
-    if (rc) return rc;
     return batch_coords_move(b, coords, total, 0, kernel_ms, (hipStream_t)hip_stream);
 }
 
@@ -476,45 +509,35 @@ int gfs_batch_pair_errors(gfs_batch *b, const uint64_t *zs, uint64_t n_z, gfs_pa
             return fail(GFS_E_STATE, "batch item " + std::to_string(i) + ": the context has no positions (not set up)");
     if (kernel_ms) *kernel_ms = 0.0;
     if (n_z == 0) return GFS_OK;
-    std::vector<uint64_t> steps(n), first_block(n + 1);
-    for (uint64_t i = 0; i < n; ++i) steps[i] = b->ctxs[i]->n_steps;
+    const std::vector<uint64_t> steps = item_counts(b, &gfs_ctx::n_steps);
+    std::vector<uint64_t> first_block(n + 1);
     const uint64_t row_blocks = gfs::quality_plan(steps.data(), n, first_block.data());
     if (row_blocks > 0x7FFFFFFFull || n > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, "the batch's step tables exceed one launch");
     HIPCHK(hipSetDevice(b->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    // device: [zs | QualityItem table | block table (whole words) | out words | partials]; the first three go up in one copy
-    const uint64_t items_at = n_z * 8, blocks_at = items_at + n * sizeof(gfs::QualityItem);
-    const uint64_t out_at = blocks_at + (row_blocks * sizeof(uint32_t) + 7) / 8 * 8, out_bytes = n * n_z * 5 * 8;
-    const uint64_t partials_at = out_at + out_bytes, bytes = partials_at + 5 * n_z * row_blocks * 8;
-    rc = b->h_packed.reserve(out_at + out_bytes);                          // (staging: the same offsets, less the partials)
-    if (!rc) rc = b->d_quality.reserve(bytes);
-    if (rc) return rc;
-    unsigned char *h = b->h_packed.as<unsigned char>(), *d = b->d_quality.as<unsigned char>();
-    std::memcpy(h, zs, n_z * 8);
-    gfs::QualityItem *h_items = reinterpret_cast<gfs::QualityItem *>(h + items_at);
+    gfs::Region map;                                                       // [zs | QualityItem table | block table] [out words] [partials]
+    const uint64_t zs_at = map.add(n_z * 8), items_at = map.add(n * sizeof(gfs::QualityItem)), blocks_at = map.add(row_blocks * sizeof(uint32_t));   map.end_upload();
+    const uint64_t out_at = map.add(n * n_z * 5 * 8);   map.end_staging();
+    const uint64_t partials_at = map.add(5 * n_z * row_blocks * 8);
+    RoundTrip rt{b, (hipStream_t)hip_stream};
+    if ((rc = rt.reserve(map, &b->d_quality))) return rc;
+    std::memcpy(rt.h + zs_at, zs, n_z * 8);
+    gfs::QualityItem *h_items = rt.host<gfs::QualityItem>(items_at);
     for (uint64_t i = 0; i < n; ++i) {
         const gfs_ctx *c = b->ctxs[i];
         h_items[i] = gfs::QualityItem{c->d_step_rec, c->d_x, c->n_steps, c->n_nodes, (uint32_t)first_block[i], (uint32_t)(first_block[i + 1] - first_block[i])};
     }
-    gfs::block_item_table(first_block.data(), n, reinterpret_cast<uint32_t *>(h + blocks_at));
-    HIPCHK(hipMemcpyAsync(d, h, blocks_at + row_blocks * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(b->readout_timer.start(st));
-    hipError_t e = gfs::batch_pair_errors_device(reinterpret_cast<const gfs::QualityItem *>(d + items_at), reinterpret_cast<const uint32_t *>(d + blocks_at),
-                                                 (uint32_t)n, row_blocks, (uint32_t)b->dims, reinterpret_cast<const uint64_t *>(d), (uint32_t)n_z,
-                                                 reinterpret_cast<uint64_t *>(d + partials_at), reinterpret_cast<uint64_t *>(d + out_at), st);
-    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch pair_errors launch: ") + hipGetErrorString(e));
-    HIPCHK(b->readout_timer.stop(st));
-    HIPCHK(hipMemcpyAsync(h + out_at, d + out_at, out_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const uint64_t *w = reinterpret_cast<const uint64_t *>(h + out_at);
+    gfs::block_item_table(first_block.data(), n, rt.host<uint32_t>(blocks_at));
+    if ((rc = rt.upload(zs_at, map.uploaded()))) return rc;
+    hipError_t e = gfs::batch_pair_errors_device(rt.device<const gfs::QualityItem>(items_at), rt.device<const uint32_t>(blocks_at), (uint32_t)n, row_blocks,
+                                                 (uint32_t)b->dims, rt.device<const uint64_t>(zs_at), (uint32_t)n_z, rt.device<uint64_t>(partials_at),
+                                                 rt.device<uint64_t>(out_at), rt.st);
+    if ((rc = rt.finish(e, "batch pair_errors launch", out_at, map.staged(), kernel_ms))) return rc;
+    const uint64_t *w = rt.host<const uint64_t>(out_at);
     for (uint64_t r = 0; r < n * n_z; ++r) out[r] = gfs::unpack_pair_error(zs[r % n_z], &w[5 * r]);
-    read_kernel_ms(b->readout_timer, kernel_ms);
     return GFS_OK;
 }
 
 // ---- K7k: gfs_ctx_sort_quality of every item of a batch of 1D sorts (batch_sort_quality_kernels.hip) ------------------------------
-static uint64_t words8(uint64_t bytes) { return (bytes + 7) / 8 * 8; }
-
 int gfs_batch_sort_quality(gfs_batch *b, gfs_sort_quality *out, uint64_t n, double *kernel_ms, void *hip_stream) {
     if (!b) return fail(GFS_E_ARG, "batch is null");
     if (!out) return fail(GFS_E_ARG, "out is null");
@@ -526,82 +549,55 @@ int gfs_batch_sort_quality(gfs_batch *b, gfs_sort_quality *out, uint64_t n, doub
         if (c->dims != 0 || (c->n_nodes && !c->d_x)) return fail(GFS_E_STATE, "batch item " + std::to_string(i) + ": needs a 1D context that has been set up");
     }
     if (n > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, "the batch's items exceed one table");
-    const std::vector<uint64_t> nodes = batch_nodes(b), first_node = batch_offsets(b);
-    std::vector<uint64_t> steps(n), first_block(n + 1), by_len(n);
-    for (uint64_t i = 0; i < n; ++i) steps[i] = b->ctxs[i]->n_steps;
-    const uint64_t row_blocks = gfs::quality_plan(steps.data(), n, first_block.data()), total_nodes = first_node.back();
+    const std::vector<uint64_t> nodes = item_counts(b, &gfs_ctx::n_nodes), steps = item_counts(b, &gfs_ctx::n_steps), first_node = batch_offsets(b);
+    std::vector<uint64_t> first_block(n + 1), by_len(n);
+    const uint64_t row_blocks = gfs::quality_plan(steps.data(), n, first_block.data());
     if (row_blocks > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, "the batch's step tables exceed one launch");
     const uint64_t within = gfs::segment_launch_order(nodes.data(), n, b->sort_cap, by_len.data());
     if (kernel_ms) *kernel_ms = 0.0;
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipDeviceSynchronize());                                        // as gfs_ctx_sort_quality: nothing of an item is in flight
     hipStream_t st = (hipStream_t)hip_stream;
-    // device: [ReadoutItem rows, in launch order | SortQualityItem table | block table (whole words) | out words | totals by row |
-    // sorted positions, packed by item | partials]; the first three go up in one copy, out and totals come back in one
-    const uint64_t items_at = n * sizeof(gfs::ReadoutItem), blocks_at = items_at + n * sizeof(gfs::SortQualityItem);
-    const uint64_t out_at = blocks_at + words8(row_blocks * sizeof(uint32_t)), totals_at = out_at + n * 5 * 8, spos_at = totals_at + n * 8;
-    const uint64_t partials_at = spos_at + total_nodes * 8, bytes = partials_at + 5 * row_blocks * 8;
-    int rc = b->h_packed.reserve(spos_at);                                 // (staging: the same offsets, less positions and partials)
-    if (!rc) rc = b->d_quality.reserve(bytes);
+    // [ReadoutItem rows, in launch order | SortQualityItem table | block table] [out words | totals by row] [sorted positions by item | partials]
+    gfs::Region map;
+    const uint64_t rows_at = map.add(n * sizeof(gfs::ReadoutItem)), items_at = map.add(n * sizeof(gfs::SortQualityItem));
+    const uint64_t blocks_at = map.add(row_blocks * sizeof(uint32_t));   map.end_upload();
+    const uint64_t out_at = map.add(n * 5 * 8), totals_at = map.add(n * 8);   map.end_staging();
+    const uint64_t spos_at = map.add(first_node.back() * 8), partials_at = map.add(5 * row_blocks * 8);
+    RoundTrip rt{b, st};
+    int rc = rt.reserve(map, &b->d_quality);
     if (rc) return rc;
-    unsigned char *h = b->h_packed.as<unsigned char>(), *d = b->d_quality.as<unsigned char>();
-    uint64_t *const d_spos = reinterpret_cast<uint64_t *>(d + spos_at), *const d_totals = reinterpret_cast<uint64_t *>(d + totals_at);
-    gfs::ReadoutItem *h_rows = reinterpret_cast<gfs::ReadoutItem *>(h);
-    gfs::SortQualityItem *h_items = reinterpret_cast<gfs::SortQualityItem *>(h + items_at);
-    for (uint64_t r = 0; r < n; ++r) {                                     // from the contexts as they are now (positions may have been bound anew)
-        const gfs_ctx *c = b->ctxs[by_len[r]];
-        gfs::ReadoutItem &it = h_rows[r];
-        it.x = c->d_x; it.perm = c->d_perm; it.node_len = c->d_node_len;
-        it.offset = first_node[by_len[r]];
-        it.n = (uint32_t)c->n_nodes;                                       // (a context has fewer than 2^31 nodes)
-        it.padded = r < within ? (uint32_t)gfs::segment_group_of(c->n_nodes, b->sort_cap) : 0;
-    }
+    uint64_t *const d_spos = rt.device<uint64_t>(spos_at), *const d_totals = rt.device<uint64_t>(totals_at);
+    gfs::ReadoutItem *h_rows = rt.host<gfs::ReadoutItem>(rows_at);
+    gfs::SortQualityItem *h_items = rt.host<gfs::SortQualityItem>(items_at);
+    for (uint64_t r = 0; r < n; ++r)
+        h_rows[r] = readout_row(b->ctxs[by_len[r]], first_node[by_len[r]], r < within ? (uint32_t)gfs::segment_group_of(nodes[by_len[r]], b->sort_cap) : 0);
     for (uint64_t i = 0; i < n; ++i) {
         const gfs_ctx *c = b->ctxs[i];
         h_items[i] = gfs::SortQualityItem{c->d_step_rec, d_spos + first_node[i], c->n_steps, (uint32_t)first_block[i], (uint32_t)(first_block[i + 1] - first_block[i])};
     }
-    gfs::block_item_table(first_block.data(), n, reinterpret_cast<uint32_t *>(h + blocks_at));
-    HIPCHK(hipMemcpyAsync(d, h, blocks_at + row_blocks * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(b->readout_timer.start(st));
-    for (uint64_t first = 0; first < within;) {
-        const uint64_t P = gfs::segment_group_of(nodes[by_len[first]], b->sort_cap);
-        const uint64_t end = gfs::segment_launch_end(nodes.data(), by_len.data(), first, within, b->sort_cap);
-        hipError_t e = gfs::batch_sorted_positions_device(reinterpret_cast<const gfs::ReadoutItem *>(d) + first, (uint32_t)(end - first), (uint32_t)P, d_spos,
-                                                          d_totals + first, st);
-        if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch sorted positions launch: ") + hipGetErrorString(e));
-        first = end;
-    }
-    // above the cap: K6 and K7c's own scan and scatter once each, into the same packed positions
+    gfs::block_item_table(first_block.data(), n, rt.host<uint32_t>(blocks_at));
+    if ((rc = rt.upload(rows_at, map.uploaded()))) return rc;
+    rc = for_each_segment_launch(nodes, by_len, within, b->sort_cap, [&](uint64_t first, uint64_t end, uint32_t padded) -> int {
+        hipError_t e = gfs::batch_sorted_positions_device(rt.device<const gfs::ReadoutItem>(rows_at) + first, (uint32_t)(end - first), padded, d_spos, d_totals + first, st);
+        return e == hipSuccess ? GFS_OK : fail(GFS_E_HIP, std::string("batch sorted positions launch: ") + hipGetErrorString(e));
+    });
+    // above the cap: K6 and K7c's own scan and scatter once each, into the same packed positions; behind K6's scratch, the prefix
     std::vector<uint64_t> long_total(n - within, 0);
-    for (uint64_t r = within; r < n; ++r) {
-        const gfs_ctx *c = b->ctxs[by_len[r]];
-        const uint64_t nn = c->n_nodes, sort_bytes = nn * (2 * 8 + 2 * 4);
-        HIPCHK(hipStreamSynchronize(st));                                  // (K6 runs on the null stream)
-        rc = b->d_sort_tmp.reserve(sort_bytes + (nn + 1) * 8);             // [K6's scratch | prefix]
-        if (rc) return rc;
-        uint32_t *d_sorted = nullptr;
-        hipError_t e = gfs::sort_order_device(c->d_x, c->d_perm, nn, 1, b->d_sort_tmp.p, &d_sorted);
-        if (e != hipSuccess) return fail(GFS_E_HIP, "batch item " + std::to_string(by_len[r]) + ": sort_order_device: " + hipGetErrorString(e));
-        e = gfs::sorted_positions_device(d_sorted, c->d_node_len, c->d_perm, nn, reinterpret_cast<uint64_t *>(b->d_sort_tmp.as<unsigned char>() + sort_bytes),
-                                         d_spos + first_node[by_len[r]], &long_total[r - within], st);
-        if (e != hipSuccess) return fail(GFS_E_HIP, "batch item " + std::to_string(by_len[r]) + ": sorted_positions_device: " + hipGetErrorString(e));
-        HIPCHK(hipStreamSynchronize(st));                                  // (the scratch is the next item's)
-    }
-    hipError_t e = gfs::batch_sort_quality_device(reinterpret_cast<const gfs::SortQualityItem *>(d + items_at), reinterpret_cast<const uint32_t *>(d + blocks_at),
-                                                  (uint32_t)n, row_blocks, reinterpret_cast<uint64_t *>(d + partials_at), reinterpret_cast<uint64_t *>(d + out_at), st);
-    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch sort_quality launch: ") + hipGetErrorString(e));
-    HIPCHK(b->readout_timer.stop(st));
-    HIPCHK(hipMemcpyAsync(h + out_at, d + out_at, spos_at - out_at, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    read_kernel_ms(b->readout_timer, kernel_ms);
-    const uint64_t *w = reinterpret_cast<const uint64_t *>(h + out_at), *totals = reinterpret_cast<const uint64_t *>(h + totals_at);
+    for (uint64_t r = within; r < n && !rc; ++r)
+        rc = sort_item_above_cap(b, by_len[r], (nodes[by_len[r]] + 1) * 8, st, [&](const gfs_ctx *c, const uint32_t *d_sorted, void *d_prefix) -> int {
+            hipError_t e = gfs::sorted_positions_device(d_sorted, c->d_node_len, c->d_perm, c->n_nodes, static_cast<uint64_t *>(d_prefix),
+                                                        d_spos + first_node[by_len[r]], &long_total[r - within], st);
+            return e == hipSuccess ? GFS_OK : fail(GFS_E_HIP, "batch item " + std::to_string(by_len[r]) + ": sorted_positions_device: " + hipGetErrorString(e));
+        });
+    if (rc) return rc;
+    hipError_t e = gfs::batch_sort_quality_device(rt.device<const gfs::SortQualityItem>(items_at), rt.device<const uint32_t>(blocks_at), (uint32_t)n, row_blocks,
+                                                  rt.device<uint64_t>(partials_at), rt.device<uint64_t>(out_at), st);
+    if ((rc = rt.finish(e, "batch sort_quality launch", out_at, map.staged(), kernel_ms))) return rc;
+    const uint64_t *w = rt.host<const uint64_t>(out_at), *totals = rt.host<const uint64_t>(totals_at);
     for (uint64_t r = 0; r < n; ++r)
-        if ((r < within ? totals[r] : long_total[r - within]) >= (1ull << 53))
-            return fail(GFS_E_UNSUPPORTED, "batch item " + std::to_string(by_len[r]) + ": a graph of 2^53 bp or more");
-    for (uint64_t i = 0; i < n; ++i) {
-        out[i].steps = w[5 * i]; out[i].abs_err_sum = w[5 * i + 1]; out[i].genomic_sum = w[5 * i + 2];
-        std::memcpy(&out[i].sq_err_sum, &w[5 * i + 3], 8);
-    }
+        if ((rc = gfs::check_sorted_length(r < within ? totals[r] : long_total[r - within], (int64_t)by_len[r]))) return rc;
+    for (uint64_t i = 0; i < n; ++i) out[i] = gfs::unpack_sort_quality(&w[5 * i]);
     return GFS_OK;
 }
 
@@ -615,23 +611,25 @@ struct DiagPlan {
 static DiagPlan diag_plan(const gfs_batch *b, uint64_t cap) {
     const uint64_t n = b->ctxs.size();
     DiagPlan p;
-    std::vector<uint64_t> paths(n), nodes(n);
-    p.steps.resize(n);
-    for (uint64_t i = 0; i < n; ++i) { p.steps[i] = b->ctxs[i]->n_steps; paths[i] = b->ctxs[i]->n_paths; nodes[i] = b->ctxs[i]->n_nodes; }
-    for (std::vector<uint64_t> *v : {&p.first_tile, &p.first_path, &p.first_node, &p.first_pair, &p.first_block}) v->resize(n + 1);
+    p.steps = item_counts(b, &gfs_ctx::n_steps);
+    p.first_path = batch_offsets(b, &gfs_ctx::n_paths); p.first_node = batch_offsets(b);
+    for (std::vector<uint64_t> *v : {&p.first_tile, &p.first_pair, &p.first_block}) v->resize(n + 1);
     p.tiles = gfs::tile_plan(p.steps.data(), n, p.first_tile.data());
-    p.paths = gfs::row_offsets(paths.data(), n, p.first_path.data());
-    p.nodes = gfs::row_offsets(nodes.data(), n, p.first_node.data());
+    p.paths = p.first_path.back(); p.nodes = p.first_node.back();
     p.pairs = gfs::stretched_list_plan(p.steps.data(), n, cap, p.first_pair.data());
     p.row_blocks = gfs::quality_plan(p.steps.data(), n, p.first_block.data());
     return p;
 }
-static void diag_items(const gfs_batch *b, const DiagPlan &p, gfs::DiagItem *items) {
-    for (uint64_t i = 0; i < b->ctxs.size(); ++i) {
-        const gfs_ctx *c = b->ctxs[i];
+// the two tables every diagnosis sends, filled in the staging and uploaded: the items, and (first_tile or first_block) whose a tile or a workgroup is
+static int diag_send(RoundTrip &rt, const gfs::Region &map, const DiagPlan &p, const std::vector<uint64_t> &first, uint64_t items_at, uint64_t table_at) {
+    gfs::DiagItem *items = rt.host<gfs::DiagItem>(items_at);
+    for (uint64_t i = 0; i < rt.b->ctxs.size(); ++i) {
+        const gfs_ctx *c = rt.b->ctxs[i];
         items[i] = gfs::DiagItem{c->d_step_rec, c->d_path_rec, c->d_x, c->d_perm, c->n_steps, c->n_nodes, c->n_paths, p.first_tile[i], p.first_path[i],
                                  p.first_node[i], p.first_pair[i], (uint32_t)p.first_block[i], (uint32_t)(p.first_block[i + 1] - p.first_block[i])};
     }
+    gfs::block_item_table(first.data(), rt.b->ctxs.size(), rt.host<uint32_t>(table_at));
+    return rt.upload(items_at, map.uploaded());
 }
 // gfs_ctx_*'s rules for z and ratio, then every item's state; no device call
 static int diag_check(const gfs_batch *b, uint64_t z, double ratio) {
@@ -646,10 +644,7 @@ static int diag_check(const gfs_batch *b, uint64_t z, double ratio) {
 
 int gfs_batch_path_offsets(const gfs_batch *b, uint64_t *offsets, uint64_t n) {
     if (!b || !offsets) return fail(GFS_E_ARG, "null argument");
-    if (n != b->ctxs.size() + 1) return fail(GFS_E_ARG, "offsets: need items + 1 entries");
-    offsets[0] = 0;
-    for (size_t i = 0; i < b->ctxs.size(); ++i) offsets[i + 1] = offsets[i] + b->ctxs[i]->n_paths;
-    return GFS_OK;
+    return copy_offsets(batch_offsets(b, &gfs_ctx::n_paths), offsets, n);
 }
 
 int gfs_batch_debug_tile_blocks(gfs_batch *b, uint64_t max_blocks) {
@@ -666,30 +661,19 @@ int gfs_batch_path_errors(gfs_batch *b, uint64_t z, double ratio, gfs_path_error
     if (total_paths != p.paths) return fail(GFS_E_ARG, "total_paths is not the batch's path count (gfs_batch_path_offsets)");
     if (kernel_ms) *kernel_ms = 0.0;
     if (p.paths == 0) return GFS_OK;
-    static_assert(sizeof(gfs_path_error) == 8 * 8, "K7h writes gfs_path_error as 8 words");
     const uint64_t n = b->ctxs.size();
     HIPCHK(hipSetDevice(b->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    // device: [DiagItem table | tile table (whole words) | out | head partials | tail partials]; the first two go up in one copy
-    const uint64_t tiles_at = n * sizeof(gfs::DiagItem), out_at = tiles_at + words8(p.tiles * sizeof(uint32_t)), out_bytes = p.paths * sizeof(gfs_path_error);
-    const uint64_t head_at = out_at + out_bytes, tail_at = head_at + 5 * p.tiles * 8, bytes = tail_at + 5 * p.tiles * 8;
-    rc = b->h_packed.reserve(out_at + out_bytes);                          // (staging: the same offsets, less the partials)
-    if (!rc) rc = b->d_quality.reserve(bytes);
-    if (rc) return rc;
-    unsigned char *h = b->h_packed.as<unsigned char>(), *d = b->d_quality.as<unsigned char>();
-    diag_items(b, p, reinterpret_cast<gfs::DiagItem *>(h));
-    gfs::tile_item_table(p.first_tile.data(), n, reinterpret_cast<uint32_t *>(h + tiles_at));
-    HIPCHK(hipMemcpyAsync(d, h, out_at, hipMemcpyHostToDevice, st));
-    HIPCHK(b->readout_timer.start(st));
-    hipError_t e = gfs::batch_path_errors_device(reinterpret_cast<const gfs::DiagItem *>(d), reinterpret_cast<const uint32_t *>(d + tiles_at), (uint32_t)n,
-                                                 p.tiles, p.paths, (uint32_t)b->dims, z, ratio, reinterpret_cast<uint64_t *>(d + head_at),
-                                                 reinterpret_cast<uint64_t *>(d + tail_at), reinterpret_cast<uint64_t *>(d + out_at), b->tile_blocks, st);
-    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch path_errors launch: ") + hipGetErrorString(e));
-    HIPCHK(b->readout_timer.stop(st));
-    HIPCHK(hipMemcpyAsync(h + out_at, d + out_at, out_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    std::memcpy(out, h + out_at, out_bytes);
-    read_kernel_ms(b->readout_timer, kernel_ms);
+    gfs::Region map;                                                       // [DiagItem table | tile table] [out] [head partials | tail partials]
+    const uint64_t items_at = map.add(n * sizeof(gfs::DiagItem)), tiles_at = map.add(p.tiles * sizeof(uint32_t));   map.end_upload();
+    const uint64_t out_at = map.add(p.paths * sizeof(gfs_path_error));   map.end_staging();
+    const uint64_t head_at = map.add(5 * p.tiles * 8), tail_at = map.add(5 * p.tiles * 8);
+    RoundTrip rt{b, (hipStream_t)hip_stream};
+    if ((rc = rt.reserve(map, &b->d_quality)) || (rc = diag_send(rt, map, p, p.first_tile, items_at, tiles_at))) return rc;
+    hipError_t e = gfs::batch_path_errors_device(rt.device<const gfs::DiagItem>(items_at), rt.device<const uint32_t>(tiles_at), (uint32_t)n, p.tiles, p.paths,
+                                                 (uint32_t)b->dims, z, ratio, rt.device<uint64_t>(head_at), rt.device<uint64_t>(tail_at),
+                                                 rt.device<uint64_t>(out_at), b->tile_blocks, rt.st);
+    if ((rc = rt.finish(e, "batch path_errors launch", out_at, map.staged(), kernel_ms))) return rc;
+    std::memcpy(out, rt.h + out_at, p.paths * sizeof(gfs_path_error));
     return GFS_OK;
 }
 
@@ -703,40 +687,27 @@ int gfs_batch_stretched_pairs(gfs_batch *b, uint64_t z, double ratio, gfs_stretc
     if (kernel_ms) *kernel_ms = 0.0;
     const DiagPlan p = diag_plan(b, cap);
     if (p.tiles == 0) return GFS_OK;
-    static_assert(sizeof(gfs_stretched_pair) == 5 * 8, "K7i writes gfs_stretched_pair as 5 words");
     HIPCHK(hipSetDevice(b->device));
-    hipStream_t st = (hipStream_t)hip_stream;
     size_t tmp_bytes = 0;
     hipError_t e = gfs::batch_stretched_scan_bytes(p.tiles, &tmp_bytes);
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch stretched_pairs scan: ") + hipGetErrorString(e));
-    // device: [DiagItem table | tile table (whole words) | tile counts | offsets | list | the scan's storage]; the first two go up in one
-    // copy, offsets and list come back in one
-    const uint64_t tiles_at = n * sizeof(gfs::DiagItem), counts_at = tiles_at + words8(p.tiles * sizeof(uint32_t));
-    const uint64_t offsets_at = counts_at + (p.tiles + 1) * 8, list_at = offsets_at + (p.tiles + 1) * 8;
-    const uint64_t tmp_at = list_at + p.pairs * sizeof(gfs_stretched_pair), bytes = tmp_at + (tmp_bytes ? tmp_bytes : 8);
-    rc = b->h_packed.reserve(tmp_at);                                      // (staging: the same offsets, less the scan's storage)
-    if (!rc) rc = b->d_quality.reserve(bytes);
-    if (rc) return rc;
-    unsigned char *h = b->h_packed.as<unsigned char>(), *d = b->d_quality.as<unsigned char>();
-    diag_items(b, p, reinterpret_cast<gfs::DiagItem *>(h));
-    gfs::tile_item_table(p.first_tile.data(), n, reinterpret_cast<uint32_t *>(h + tiles_at));
-    HIPCHK(hipMemcpyAsync(d, h, counts_at, hipMemcpyHostToDevice, st));
-    HIPCHK(b->readout_timer.start(st));
-    e = gfs::batch_stretched_pairs_device(reinterpret_cast<const gfs::DiagItem *>(d), reinterpret_cast<const uint32_t *>(d + tiles_at), p.tiles,
-                                          (uint32_t)b->dims, z, ratio, reinterpret_cast<uint64_t *>(d + counts_at), reinterpret_cast<uint64_t *>(d + offsets_at),
-                                          p.pairs ? d + list_at : nullptr, cap, d + tmp_at, tmp_bytes, b->tile_blocks, st);
-    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch stretched_pairs launch: ") + hipGetErrorString(e));
-    HIPCHK(b->readout_timer.stop(st));
-    HIPCHK(hipMemcpyAsync(h + offsets_at, d + offsets_at, tmp_at - offsets_at, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const uint64_t *offsets = reinterpret_cast<const uint64_t *>(h + offsets_at);
-    const gfs_stretched_pair *list = reinterpret_cast<const gfs_stretched_pair *>(h + list_at);
+    gfs::Region map;   // [DiagItem table | tile table] [tile counts | offsets | list], of which offsets and list come back, [the scan's storage, never empty]
+    const uint64_t items_at = map.add(n * sizeof(gfs::DiagItem)), tiles_at = map.add(p.tiles * sizeof(uint32_t));   map.end_upload();
+    const uint64_t counts_at = map.add((p.tiles + 1) * 8), offsets_at = map.add((p.tiles + 1) * 8), list_at = map.add(p.pairs * sizeof(gfs_stretched_pair));   map.end_staging();
+    const uint64_t tmp_at = map.add(tmp_bytes ? tmp_bytes : 8);
+    RoundTrip rt{b, (hipStream_t)hip_stream};
+    if ((rc = rt.reserve(map, &b->d_quality)) || (rc = diag_send(rt, map, p, p.first_tile, items_at, tiles_at))) return rc;
+    e = gfs::batch_stretched_pairs_device(rt.device<const gfs::DiagItem>(items_at), rt.device<const uint32_t>(tiles_at), p.tiles, (uint32_t)b->dims, z, ratio,
+                                          rt.device<uint64_t>(counts_at), rt.device<uint64_t>(offsets_at), p.pairs ? rt.d + list_at : nullptr, cap,
+                                          rt.d + tmp_at, tmp_bytes, b->tile_blocks, rt.st);
+    if ((rc = rt.finish(e, "batch stretched_pairs launch", offsets_at, map.staged(), kernel_ms))) return rc;
+    const uint64_t *offsets = rt.host<const uint64_t>(offsets_at);
+    const gfs_stretched_pair *list = rt.host<const gfs_stretched_pair>(list_at);
     for (uint64_t i = 0; i < n; ++i) {
         totals[i] = offsets[p.first_tile[i + 1]] - offsets[p.first_tile[i]];
         const uint64_t listed = std::min(std::min(cap, p.steps[i]), totals[i]);
         if (listed) std::memcpy(out + i * cap, list + p.first_pair[i], listed * sizeof(gfs_stretched_pair));
     }
-    read_kernel_ms(b->readout_timer, kernel_ms);
     return GFS_OK;
 }
 
@@ -749,31 +720,20 @@ int gfs_batch_node_errors(gfs_batch *b, uint64_t z, double ratio, gfs_node_error
     if (p.row_blocks > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, "the batch's step tables exceed one launch");
     if (kernel_ms) *kernel_ms = 0.0;
     if (p.nodes == 0) return GFS_OK;
-    static_assert(sizeof(gfs_node_error) == 3 * 8, "K7j writes gfs_node_error as 3 words");
     const uint64_t n = b->ctxs.size();
     HIPCHK(hipSetDevice(b->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    // device: [DiagItem table | block table (whole words) | out | per slot: pairs, stretched, max]; the first two go up in one copy
-    const uint64_t blocks_at = n * sizeof(gfs::DiagItem), out_at = blocks_at + words8(p.row_blocks * sizeof(uint32_t));
-    const uint64_t out_bytes = p.nodes * sizeof(gfs_node_error), slots_at = out_at + out_bytes, bytes = slots_at + out_bytes;
-    rc = b->h_packed.reserve(out_at + out_bytes);                          // (staging: the same offsets, less the slots)
-    if (!rc) rc = b->d_quality.reserve(bytes);
-    if (rc) return rc;
-    unsigned char *h = b->h_packed.as<unsigned char>(), *d = b->d_quality.as<unsigned char>();
-    diag_items(b, p, reinterpret_cast<gfs::DiagItem *>(h));
-    gfs::block_item_table(p.first_block.data(), n, reinterpret_cast<uint32_t *>(h + blocks_at));
-    HIPCHK(hipMemcpyAsync(d, h, out_at, hipMemcpyHostToDevice, st));
-    HIPCHK(b->readout_timer.start(st));
-    hipError_t e = gfs::batch_node_errors_device(reinterpret_cast<const gfs::DiagItem *>(d), reinterpret_cast<const uint32_t *>(d + blocks_at), (uint32_t)n,
-                                                 p.row_blocks, p.nodes, (uint32_t)b->dims, z, ratio, reinterpret_cast<uint64_t *>(d + slots_at),
-                                                 reinterpret_cast<uint64_t *>(d + out_at), st);
-    if (e != hipSuccess) return fail(GFS_E_HIP, std::string("batch node_errors launch: ") + hipGetErrorString(e));
-    HIPCHK(b->readout_timer.stop(st));
-    HIPCHK(hipMemcpyAsync(h + out_at, d + out_at, out_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    std::memcpy(out, h + out_at, out_bytes);
-    read_kernel_ms(b->readout_timer, kernel_ms);
+    gfs::Region map;                                                       // [DiagItem table | block table] [out] [per slot: pairs, stretched, max]
+    const uint64_t items_at = map.add(n * sizeof(gfs::DiagItem)), blocks_at = map.add(p.row_blocks * sizeof(uint32_t));   map.end_upload();
+    const uint64_t out_at = map.add(p.nodes * sizeof(gfs_node_error));   map.end_staging();
+    const uint64_t slots_at = map.add(p.nodes * sizeof(gfs_node_error));
+    RoundTrip rt{b, (hipStream_t)hip_stream};
+    if ((rc = rt.reserve(map, &b->d_quality)) || (rc = diag_send(rt, map, p, p.first_block, items_at, blocks_at))) return rc;
+    hipError_t e = gfs::batch_node_errors_device(rt.device<const gfs::DiagItem>(items_at), rt.device<const uint32_t>(blocks_at), (uint32_t)n, p.row_blocks, p.nodes,
+                                                 (uint32_t)b->dims, z, ratio, rt.device<uint64_t>(slots_at), rt.device<uint64_t>(out_at), rt.st);
+    if ((rc = rt.finish(e, "batch node_errors launch", out_at, map.staged(), kernel_ms))) return rc;
+    std::memcpy(out, rt.h + out_at, p.nodes * sizeof(gfs_node_error));
     return GFS_OK;
 }
 
 }  // extern "C"
+

@@ -7,11 +7,17 @@
 #include "sgd_kernel_common.h"
 #include "launch_policy.h"
 #include "sgd_host.h"
+#include "readout_region.h"
 
 #include <string>
 #include <vector>
 
 static inline int fail(int code, const std::string &msg) { return gfs_set_error(code, msg); }   // (the error slot: host_tables.hip)
+
+// the records the diagnosis kernels write as words, and the read-outs' maps (readout_region.h) size by
+static_assert(sizeof(gfs_path_error) == 8 * 8, "K7d / K7h write gfs_path_error as 8 words");
+static_assert(sizeof(gfs_stretched_pair) == 5 * 8, "K7e / K7i write gfs_stretched_pair as 5 words");
+static_assert(sizeof(gfs_node_error) == 3 * 8, "K7f / K7j write gfs_node_error as 3 words");
 
 static constexpr size_t kCounterBytes = gfs::COUNTER_SLOTS * 8 * sizeof(unsigned long long);   // lines of 64 B
 
@@ -121,4 +127,8 @@ GFS_LOCAL int check_step_distances(const uint64_t *zs, uint64_t n_z, const gfs_p
 GFS_LOCAL int check_diagnosis(uint64_t z, double ratio);   // K7d-f and K7h-j: z >= 1, ratio a number >= 0
 // five words of K7a / K7g { pairs, sum_rel_sq, max_rel_sq, sum_abs, sum_sq (f64 bits) } as the ABI's record for step distance z
 GFS_LOCAL gfs_pair_error unpack_pair_error(uint64_t z, const uint64_t *w);
+// five words of K7c / K7k { steps, abs_err_sum, genomic_sum, sq_err_sum (f64 bits), 0 } as the ABI's record; and the refusal of a
+// graph whose length in bp a double no longer holds exactly, "batch item <i>: " in front of its text where batch_item >= 0
+GFS_LOCAL gfs_sort_quality unpack_sort_quality(const uint64_t *w);
+GFS_LOCAL int check_sorted_length(uint64_t total_bp, int64_t batch_item = -1);
 }  // namespace gfs

@@ -61,6 +61,8 @@ hipError_t build_path_index_device(const uint32_t *d_step_node, const uint8_t *d
                                    uint64_t n_steps, uint64_t n_nodes, uint64_t *d_tmp, uint4 *d_rec, uint64_t *d_path_len);
 hipError_t sort_order_device(const double *d_x_layout, const uint32_t *d_perm, uint64_t n, uint64_t stride_doubles,
                              void *d_tmp, uint32_t **d_order_out);
+// what d_tmp must hold for n nodes: two buffers of keys and two of values
+inline uint64_t sort_order_scratch_bytes(uint64_t n) { return n * (2 * 8 + 2 * 4); }
 
 // batch_readout_kernels.hip (K4b, K6b): one workgroup per item of a table on the device.  x, perm and node_len are the item's
 // context's; offset is where its segment starts in the packed outputs; padded = segment_padded(n) (segment_sort.h; K6b only).
@@ -70,6 +72,7 @@ struct ReadoutItem {
     uint64_t offset;
     uint32_t n, padded;
 };
+static_assert(sizeof(ReadoutItem) == 40, "a multiple of 8 bytes: the next part of a read-out's region starts where the table ends (readout_region.h)");
 // K4b: every item's initial positions (what init_positions_device writes).  Asynchronous.
 hipError_t batch_init_positions_device(const ReadoutItem *d_items, uint32_t count, hipStream_t st);
 // K6b: count items of one padded length <= SEGMENT_SORT_CAP: d_positions (nullable) [offset + k] = x[perm[k]], d_order[offset + r] =
@@ -87,6 +90,7 @@ struct CoordItem {
     uint64_t offset;
     uint32_t n, first_block, dims, _pad;
 };
+static_assert(sizeof(CoordItem) == 40, "a multiple of 8 bytes: the next part of a read-out's region starts where the table ends (readout_region.h)");
 // to_device = 1: packed -> the items' planes (what reorder_positions_device writes per item), else planes -> packed.  Asynchronous.
 hipError_t batch_coords_device(const CoordItem *d_items, const uint32_t *d_block_item, uint64_t blocks, double *d_packed, int to_device,
                                hipStream_t st);
@@ -97,6 +101,7 @@ struct QualityItem {
     uint64_t n_steps, n_nodes;
     uint32_t first_block, blocks;
 };
+static_assert(sizeof(QualityItem) == 40, "a multiple of 8 bytes: the next part of a read-out's region starts where the table ends (readout_region.h)");
 // All pairs (s, s + z) of every item for n_z step distances.  row_blocks: the sum of the items' blocks; d_partials: 5 * n_z *
 // row_blocks words; d_out: 5 words per (item, distance), [item][z], as pair_errors_device writes them for one.  Asynchronous.
 hipError_t batch_pair_errors_device(const QualityItem *d_items, const uint32_t *d_block_item, uint32_t n_items, uint64_t row_blocks,
@@ -114,6 +119,7 @@ struct DiagItem {
     uint64_t first_tile, first_path, first_node, first_pair;
     uint32_t first_block, blocks;
 };
+static_assert(sizeof(DiagItem) == 96, "a multiple of 8 bytes: the next part of a read-out's region starts where the table ends (readout_region.h)");
 // max_blocks (K7h, K7i): a cap on the grids over flat tiles and paths below Q_TILE_MAX_BLOCKS, 0 = none (a test hook: a tile's
 // yield does not depend on the grid).
 // K7h: d_tile_item: n_tiles entries; d_head, d_tail: 5 words per flat tile; d_out: 8 words per path of the union, item i's rows at
@@ -147,6 +153,7 @@ struct SortQualityItem {
     uint64_t n_steps;
     uint32_t first_block, blocks;
 };
+static_assert(sizeof(SortQualityItem) == 32, "a multiple of 8 bytes: the next part of a read-out's region starts where the table ends (readout_region.h)");
 // d_block_item: row_blocks entries; d_partials: 5 * row_blocks words; d_out: 5 words per item, as sort_quality_steps_device writes
 // them for one.  Two launches.  Asynchronous.
 hipError_t batch_sort_quality_device(const SortQualityItem *d_items, const uint32_t *d_block_item, uint32_t n_items, uint64_t row_blocks,

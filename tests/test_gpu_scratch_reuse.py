@@ -142,6 +142,46 @@ def _check_pair_errors(b, ctxs, zs):
         assert rows[i].tobytes() == c.pair_errors(zs).tobytes(), (i, zs)
 
 
+def _check_readouts_interleaved(b, ctxs, sorts):
+    """Every batch read-out in the order small map, large map, small map, each bit for bit the per-context call: the diagnosis and
+    the sort quality share the batch's quality buffer and pinned staging with pair_errors, and the staging with results."""
+    above = max(c.graph.n_steps for c in ctxs) + 10                      # a cap above every total
+
+    def path_errors():
+        for i, rows in enumerate(b.path_errors(2, RATIO)):
+            assert _bytes(rows) == _bytes(ctxs[i].path_errors(2, RATIO)), i
+
+    def stretched_pairs(cap):
+        lists, totals = b.stretched_pairs(2, RATIO, cap=cap)
+        for i, c in enumerate(ctxs):
+            rows, total = c.stretched_pairs(2, RATIO, cap=cap)
+            assert int(totals[i]) == int(total) and _bytes(lists[i]) == _bytes(rows), (i, cap)
+
+    def node_errors():
+        for i, rows in enumerate(b.node_errors(2, RATIO)):
+            assert _bytes(rows) == _bytes(ctxs[i].node_errors(2, RATIO)), i
+
+    def sort_quality():
+        for i, q in enumerate(b.sort_quality()):
+            assert _bytes(q) == _bytes(ctxs[i].sort_quality()), i
+
+    def results():
+        xs, orders, _ = b.results()
+        for i, c in enumerate(ctxs):
+            assert np.array_equal(orders[i], c.sort_order()) and xs[i].tobytes() == c.download().tobytes(), i
+
+    calls = [path_errors, lambda: stretched_pairs(1), lambda: stretched_pairs(above), node_errors] + ([sort_quality] if sorts else []) + \
+            [lambda: _check_pair_errors(b, ctxs, [1, 2, 3, 10, 100])] + ([results] if sorts else [])
+    small, large = lambda: _check_pair_errors(b, ctxs, [1]), lambda: stretched_pairs(above)
+    for call in calls:
+        small()
+        large()
+        call()
+        small()
+    totals = b.stretched_pairs(2, RATIO, cap=0)[1]
+    assert max(int(t) for t in totals) > 1 and all(int(t) < above for t in totals)   # cap 1 cuts a list short, the other none
+
+
 def test_batch_of_sorts_reuses_its_buffers():
     ctxs, b = _batch(0)
 
@@ -161,6 +201,10 @@ def test_batch_of_sorts_reuses_its_buffers():
         check_results(True)
         _check_pair_errors(b, ctxs, [1, 2, 3, 10, 100])
         assert not any(np.array_equal(c.download(), hip.init_positions(c.graph)) for c in ctxs)   # (the run moved every item)
+        b.debug_sort_cap(0)                                            # the default sort cap, then every item above it again
+        _check_readouts_interleaved(b, ctxs, True)
+        b.debug_sort_cap(ctxs[0].graph.n_nodes - 1)
+        _check_readouts_interleaved(b, ctxs, True)
     finally:
         b.close()
         for c in ctxs:
@@ -180,6 +224,7 @@ def test_batch_of_layouts_reuses_its_buffers():
             assert x.tobytes() == up[i].tobytes(), i
         for i, c in enumerate(ctxs):
             assert c.download().tobytes() == up[i].tobytes(), i         # (what the batch uploaded is what the item holds)
+        _check_readouts_interleaved(b, ctxs, False)
     finally:
         b.close()
         for c in ctxs:
