@@ -15,23 +15,6 @@
 #include <new>
 #include <numeric>
 
-namespace {
-// GFS_TIMING: the phase times of an entry on stderr, each since the lap before it or (cumulative) since the start
-struct Laps {
-    const char *tag;
-    bool cumulative;
-    bool on = std::getenv("GFS_TIMING") != nullptr;
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void lap(const char *what) {
-        if (!on) return;
-        const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, cumulative ? "[%s] %-10s %8.2f ms\n" : "[%s] %-12s %8.2f ms\n", tag, what,
-                     std::chrono::duration<double, std::milli>(now - t).count());
-        if (!cumulative) t = now;
-    }
-};
-}  // namespace
-
 extern "C" {
 
 const char *gfs_version(void) { return "gfasort_hip 0.1.0 (gfx950)"; }
@@ -44,7 +27,7 @@ int gfs_device_count(void) {
 int gfs_warmup(int device) {
     // Creates the HIP context (the first HIP call of a process costs ~0.1-0.3 s); callers run this
     // on a side thread while they are still parsing their input.
-    Laps laps{"gfs_warmup", false};
+    gfs::Laps laps{"gfs_warmup", false};
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return fail(GFS_E_HIP, "no HIP device available (libgfasort_hip has no CPU fallback)");
     if (device < 0 || device >= n) return fail(GFS_E_ARG, "bad device index");
@@ -287,7 +270,7 @@ int gfs_ctx_create_with_layout(const gfs_graph_view *g, int device, const uint32
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(GFS_E_HIP, "no HIP device available (libgfasort_hip has no CPU fallback)");
     if (device < 0 || device >= ndev) return fail(GFS_E_ARG, "bad device index");
-    Laps laps{"gfs_ctx_create", false};
+    gfs::Laps laps{"gfs_ctx_create", false};
     laps.lap("validate");
     // (every error return below relies on scope: the temporaries go first, then the context)
     std::unique_ptr<gfs_ctx, decltype(&gfs_ctx_destroy)> owner(new (std::nothrow) gfs_ctx(), gfs_ctx_destroy);
@@ -301,7 +284,7 @@ int gfs_ctx_create_with_layout(const gfs_graph_view *g, int device, const uint32
     c->cu_count = prop.multiProcessorCount;
 
     // Internal node layout.  The position vector is stored in FIRST-VISIT PATH ORDER (nodes in the
-    // order the paths first step on them, unvisited nodes last; derived on the device, index_kernels.hip)
+    // order the paths first step on them, unvisited nodes last; derived on the device, index_set_kernels.hip)
     // unless the caller supplies a layout: consecutive steps of a path then touch neighbouring position words whatever the
     // order of the input's S lines was, which is what lets a run's loads and atomics coalesce
     // (C3 with randomly ordered nodes: 63 G updates/s in path order, 11 G/s in input order).
@@ -313,67 +296,13 @@ int gfs_ctx_create_with_layout(const gfs_graph_view *g, int device, const uint32
             seen[node_perm[k]] = 1; c->perm[k] = node_perm[k];
         }
     }
-    // The facts the launch logic needs, with the refusals of over-long paths (capi_ctx.h), and the path records (host, P entries)
+    // The facts the launch logic needs, with the refusals of over-long paths (capi_ctx.h)
     if (int bad = gfs::path_facts(g, c, "")) return bad;
-    std::vector<uint4> prec(std::max<uint64_t>(g->n_paths, 1));
-    for (uint64_t p = 0; p < g->n_paths; ++p) {
-        const uint64_t b = g->path_first_step[p];
-        const uint32_t cnt = c->path_counts[p];
-        prec[p].x = (uint32_t)b; prec[p].y = cnt;
-        prec[p].z = cnt ? (uint32_t)(0u - cnt) % cnt : 0u; prec[p].w = (uint32_t)(b >> 32);
-    }
-    // K3 on the device: PathIndex::from_graph (sgd.rs:34-71) — the per-path exclusive prefix sum of
-    // node lengths over the steps — written straight into the 16-byte step records
-    // (index_kernels.hip).  Uploads 5 B per step instead of 16.
-    int rc = GFS_OK;
-    auto ok = [&rc](const char *what, hipError_t e) {                      // false: rc holds the reported error
-        if (e != hipSuccess) rc = fail(GFS_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-        return e == hipSuccess;
-    };
-    const uint64_t S = g->n_steps, N = g->n_nodes, P = g->n_paths;
-    gfs::Array<uint64_t> d_tmp, d_first; gfs::Array<uint8_t> d_rev; gfs::Array<uint32_t> d_step_node;   // (scope frees them last to first)
-    // (one record of padding, zeroed: the layout team kernels read the record AFTER a step for its node's length and use it
-    // only where that step is not its path's last — so the graph's very last step needs no clamp, sgd_kernels_nd_team.hip)
-    if ((rc = c->d_step_rec.reserve((S + 1) * sizeof(uint4), "hipMalloc step_rec"))) return rc;
-    if (!ok("hipMemset step_rec", hipMemset(c->d_step_rec + S, 0, sizeof(uint4)))) return rc;
-    if ((rc = c->d_path_rec.reserve(prec.size() * sizeof(uint4), "hipMalloc path_rec"))) return rc;
-    if ((rc = c->d_path_len.reserve(std::max<uint64_t>(P, 1) * 8, "hipMalloc path_len"))) return rc;
-    if ((rc = c->d_perm.reserve(std::max<uint64_t>(N, 1) * 4, "hipMalloc perm"))) return rc;
-    if ((rc = c->d_node_len.reserve(std::max<uint64_t>(N, 1) * 4, "hipMalloc node_len"))) return rc;
-    if (N && !ok("hipMemcpy node_len", hipMemcpy(c->d_node_len, g->node_len, N * 4, hipMemcpyHostToDevice))) return rc;
-    if (!ok("hipMemcpy path_rec", hipMemcpy(c->d_path_rec, prec.data(), prec.size() * sizeof(uint4), hipMemcpyHostToDevice))) return rc;
-    if (S) {
-        if ((rc = d_step_node.reserve(S * 4, "hipMalloc step_node"))) return rc;
-        if (!ok("hipMemcpy step_node", hipMemcpy(d_step_node, g->step_node, S * 4, hipMemcpyHostToDevice))) return rc;
-        if ((rc = d_first.reserve((P + 1) * 8, "hipMalloc path_first"))) return rc;
-        if (!ok("hipMemcpy path_first", hipMemcpy(d_first, g->path_first_step, (P + 1) * 8, hipMemcpyHostToDevice))) return rc;
-    }
-    laps.lap("step upload");
-    {
-        // range check of step_node, and (unless the caller brought a layout) the first-visit order
-        int bad = 0;
-        gfs::Array<uint32_t> d_scratch_perm;
-        if (node_perm && N && (rc = d_scratch_perm.reserve(N * 4, "hipMalloc scratch"))) return rc;
-        const hipError_t e = gfs::first_visit_layout_device(d_step_node, S, N, d_first, (uint32_t)P,
-                                                            node_perm && N ? d_scratch_perm : c->d_perm, &bad);
-        d_scratch_perm.reset();
-        if (!ok("first_visit_layout", e)) return rc;
-        if (bad) return fail(GFS_E_ARG, "step_node out of range");
-        if (N && node_perm && !ok("hipMemcpy perm", hipMemcpy(c->d_perm, c->perm.data(), N * 4, hipMemcpyHostToDevice))) return rc;
-        if (N && !node_perm && !ok("hipMemcpy perm", hipMemcpy(c->perm.data(), c->d_perm, N * 4, hipMemcpyDeviceToHost))) return rc;
-    }
-    laps.lap("node layout");
-    if (S) {
-        if ((rc = d_rev.reserve(S, "hipMalloc step_is_rev"))) return rc;
-        if ((rc = d_tmp.reserve((S + 1) * 8, "hipMalloc scan"))) return rc;
-        laps.lap("alloc tmp");
-        if (!ok("hipMemcpy step_is_rev", hipMemcpy(d_rev, g->step_is_rev, S, hipMemcpyHostToDevice))) return rc;
-        laps.lap("upload");
-        if (!ok("build_path_index", gfs::build_path_index_device(d_step_node, d_rev, c->d_node_len, c->d_perm, d_first, (uint32_t)P, S, N, d_tmp,
-                                                                 c->d_step_rec, c->d_path_len))) return rc;
-    }
-    laps.lap("K3");
-    d_step_node.reset(); d_rev.reset(); d_first.reset(); d_tmp.reset();
+    // The index on the device (K3b, index_set_kernels.hip), as a union of one item in an arena of the context's own: the range
+    // check of step_node, the layout unless given, and K3 — PathIndex::from_graph (sgd.rs:34-71), the per-path exclusive prefix
+    // sum of node lengths over the steps, written straight into the 16-byte step records.  Uploads 5 B per step instead of 16.
+    gfs_ctx_set_info info{};
+    if (int bad = gfs::build_contexts(&g, &c, 1, c->arena, node_perm, false, &laps, &info)) return bad;
     laps.lap("free tmp");
     *out = owner.release();
     return GFS_OK;
@@ -972,7 +901,7 @@ static int one_shot(const gfs_graph_view *g, const gfs_sgd_params *p, int dims, 
     if (!g || !p) return fail(GFS_E_ARG, "null argument");
     if (g->n_nodes == 0) return GFS_NOTHING_TO_DO;                         // sgd.rs:242-244,780-782
     if (!x) return fail(GFS_E_ARG, "positions buffer is null");
-    Laps laps{"gfasort_hip", true};                                        // phase times of the one-shot call on stderr
+    gfs::Laps laps{"gfasort_hip", true};                                        // phase times of the one-shot call on stderr
     gfs_ctx *c = nullptr;
     int rc = gfs_ctx_create(g, 0, &c);
     if (rc) return rc;

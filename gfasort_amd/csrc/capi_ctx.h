@@ -9,6 +9,9 @@
 #include "sgd_host.h"
 #include "readout_region.h"
 
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -38,7 +41,9 @@ struct gfs_ctx {
     bool set_item = false;             // owned by a gfs_ctx_set (capi_set.hip): its index arrays are borrowed from the set's arena, gfs_ctx_destroy leaves it alone
     std::vector<uint32_t> path_counts;
     std::vector<uint32_t> perm;        // dense node index (ABI order) -> internal index (device layout of positions)
-    // device mirror of PathIndex
+    // device mirror of PathIndex: the five arrays lie in one arena — the context's own (gfs_ctx_create: a union of one item), or
+    // its set's, and then this one stays empty — and borrow from it
+    gfs::Buffer arena;                 // (declared before them: it outlives them)
     gfs::Array<uint4> d_step_rec;
     gfs::Array<uint4> d_path_rec;
     gfs::Array<uint64_t> d_path_len;
@@ -117,6 +122,34 @@ static inline int path_facts(const gfs_graph_view *g, gfs_ctx *c, const std::str
     }
     return GFS_OK;
 }
+}  // namespace gfs
+
+namespace gfs {
+// GFS_TIMING: the phase times of an entry on stderr, each since the lap before it or (cumulative) since the start
+struct Laps {
+    const char *tag;
+    bool cumulative;
+    bool on = std::getenv("GFS_TIMING") != nullptr;
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void lap(const char *what) {
+        if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        std::fprintf(stderr, cumulative ? "[%s] %-10s %8.2f ms\n" : "[%s] %-12s %8.2f ms\n", tag, what,
+                     std::chrono::duration<double, std::milli>(now - t).count());
+        if (!cumulative) t = now;
+    }
+};
+
+// capi_set.hip, for capi.hip: the ONE driver of the index build (K3b, index_set_kernels.hip), for a set's items and for a single
+// context, which is a set of one.  ctxs[i] holds graphs[i]'s counts and path_facts; on GFS_OK its perm and its five index arrays
+// are in place, the arrays borrowed from `arena`.  What tells a single context from a set's items, and nothing else:
+//   arena      whose it is — the set's, or the single context's own (gfs_ctx::arena)
+//   node_perm  a caller's layout (n == 1 only; checked to be a permutation by the caller, already in ctxs[0]->perm), or null
+//   staged     a set: the inputs are gathered in ONE pinned staging copy, and the error texts say "set" and name the item;
+//              else a single graph, which may be tens of GB: its arrays go up straight from the caller's, each with a blocking copy
+// laps (nullable): GFS_TIMING of the caller's entry; the stream is drained before a lap where it is on.
+GFS_LOCAL int build_contexts(const gfs_graph_view *const *graphs, gfs_ctx *const *ctxs, uint64_t n, Buffer &arena, const uint32_t *node_perm,
+                             bool staged, Laps *laps, gfs_ctx_set_info *info);
 }  // namespace gfs
 
 // capi.hip, for capi_batch.hip

@@ -2,6 +2,7 @@
 // treated as one disjoint graph — their nodes, steps and paths concatenated (the UNION) — and an item table says where each item
 // begins in the union and where its five index arrays lie in the set's arena.  Nothing here is exported from the shared object.
 #pragma once
+#include "index_set_plan.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -12,6 +13,7 @@ struct SetItem {
     uint64_t node_off, step_off, path_off;       // first union node / step / path of the item
     uint64_t rec, prec, plen, perm, nlen;        // byte offsets into the arena: step records (n_steps + 1), path records, path
 };                                               // lengths, node layout, node lengths (gfs_ctx_set_plan)
+static_assert(sizeof(SetItem) == SET_ITEM_BYTES, "the item table of the input head (index_set_plan.h)");
 
 // The union as the kernels see it; every pointer is a device pointer.  step_node keeps each item's OWN dense indices (a kernel
 // adds the item's node_off); path_first is in union steps, [n_paths + 1], its last entry n_steps.
@@ -28,13 +30,17 @@ struct SetUnion {
 constexpr uint32_t SET_NO_BAD_ITEM = 0xFFFFFFFFu;
 constexpr unsigned SET_STEP_BLOCKS = 2048, SET_NODE_BLOCKS = 1024, SET_PATH_BLOCKS = 64, SET_BLOCK = 256;   // the grids of the kernels over steps / over nodes / over paths and items
 
-// Bytes of scratch build_index_set_device needs for a union of these totals (rocPRIM's temporary storage included).
+// Bytes of scratch the build needs for a union of these totals (rocPRIM's temporary storage included).
 hipError_t index_set_work_bytes(uint64_t n_nodes, uint64_t n_steps, uint64_t *bytes);
-// Fills every item's step records (padding record included), path records, path lengths and node layout in the arena.
-// *bad_item = lowest item with a step naming a node out of its range (nothing past the range check has run then), else
-// SET_NO_BAD_ITEM.  *launches += kernel launches and memsets, each rocPRIM call counted as one.  On the null stream; the arena is
-// complete once the stream has drained (the last call in here is a blocking copy only where a fixpoint ran).
-hipError_t build_index_set_device(const SetUnion &u, void *d_work, uint32_t *bad_item, uint64_t *launches);
+// The build, in its two halves; both on the null stream, over the same d_work.  *launches += kernel launches and memsets, each
+// rocPRIM call counted as one.
+// Layout half: the range check of step_node — *bad_item = lowest item with a step naming a node out of its range (nothing that
+// indexes by step_node has run then), else SET_NO_BAD_ITEM — and then every item's node layout into its perm range of the arena.
+// layout_given: the perm ranges already hold the caller's layout; only the range check runs.
+hipError_t index_set_layout_device(const SetUnion &u, void *d_work, bool layout_given, uint32_t *bad_item, uint64_t *launches);
+// K3 half, after the layouts are in place: every item's step records (padding record included), path records and path lengths.
+// The arena is complete once the stream has drained.
+hipError_t index_set_records_device(const SetUnion &u, void *d_work, uint64_t *launches);
 hipError_t warm_module_index_set();
 
 }  // namespace gfs

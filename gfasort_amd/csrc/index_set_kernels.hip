@@ -1,9 +1,28 @@
-// index_set_kernels.hip — K3b: the index build of index_kernels.hip (node layout, K3) for MANY graphs in one pass.  The items of a
-// set are one disjoint graph, the UNION (index_set.h): one scan over all steps, two radix sorts over all nodes, the pointer-jumping
-// fixpoints once over all nodes.  The kernels around them are the item-aware twins of index_kernels.hip's: they look an element's
-// item up in the item table (a binary search: the table is small and stays in cache) and REBASE on the way out — slot = union
-// rank - the item's first node, path id = union path - the item's first path, positions from scan differences — so that every
-// item's arrays in the arena hold the bits a context of that graph alone holds.  Integer arithmetic throughout.
+// index_set_kernels.hip — K3b: THE index build — the internal node layout, and K3, PathIndex::from_graph (src/sgd.rs:34-71): step
+// positions = per-path exclusive prefix sum of node lengths over the steps, written straight into the 16-byte step records — of
+// one graph or of MANY in one pass.  The items of a set are one disjoint graph, the UNION (index_set.h): one scan over all steps,
+// two radix sorts over all nodes, the pointer-jumping fixpoints once over all nodes (rocPRIM for the scan and the sorts; the kernels
+// around them are hand-written).  The kernels look an element's item up in the item table (a binary search: the table is small and
+// stays in cache) and REBASE on the way out — slot = union rank - the item's first node, path id = union path - the item's first
+// path, positions from scan differences — so that every item's arrays in the arena hold the bits a context of that graph alone
+// holds.  gfs_ctx_create builds its context here too, as a union of one item: the look-up runs no iteration, every rebase
+// subtracts 0.  Integer arithmetic throughout.
+//
+// ---- internal node layout (first-visit path order with branches placed where they branch off) -----------------------
+// Base rule: nodes in the order the paths first step on them, nodes no path visits last in index order (min-reduction over
+// the steps + stable sort, so that a 4.5e9-step graph takes 0.3 s instead of 25 s on one host core).  The same pass
+// validates step_node (dense index < n_nodes, or NO_NODE).
+// Refinement: the first visits of a path come in RUNS of consecutive steps.  A run that starts its path is a ROOT run and
+// keeps its place.  Any other run BRANCHES OFF the node its path stepped on just before it (its anchor) — an alternative
+// allele of a bubble, first seen by the 7th haplotype, branches off the node before the bubble — and is placed right after
+// the root-run node its chain of anchors leads to, instead of where the 7th haplotype happens to come in step order.
+// sort key of node v = 4*(first[v] + 1) for a root-run node, 4*(first[root(v)] + 1) + 1 otherwise (any keys of that order do:
+// 2*first and 2*first + 1 for one graph); ties (branches of one root node) in first-visit order.  Why: a run of 64 consecutive
+// path steps then touches neighbouring position words on a bubble graph too, not 8 lines of main chain plus a scattered line per
+// alternative allele (bubble graphs of 0.5M / 2M nodes: 63.9 -> 77.6 and 68.2 -> 79.7 G updates/s,
+// profiles/r02/relayout_probe.log; chains and window graphs are unchanged — they have no branches).  gfs_shared_node_layout
+// (multi.hip) is the same rule on the host.
+//
 // Where the union differs from one graph:
 //   * a node no path visits goes last WITHIN ITS ITEM: the sort keys are 4*(first + 1) (+ 1 for a branch) for a visited node and
 //     4*(the item's last step + 1) + 2 for an unvisited one — above every key of its item, below every key of the next; first
@@ -17,6 +36,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>
+#include <type_traits>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -135,7 +155,8 @@ __global__ void set_scatter_rank_kernel(SetUnion u, const uint32_t *sorted_node)
 }
 
 // ---- K3 over the union ---------------------------------------------------------------------------------------------------------
-// len(s) = sequence length of the step's node (0 for an absent node); len(n_steps) = 0.  Fed to the scan through a transform iterator.
+// len(s) = sequence length of the step's node (0 for an absent node, sgd.rs:52-54); len(n_steps) = 0.  Fed to the scan through a
+// transform iterator, so the lengths are never materialised (8 B per step less scratch).
 struct SetStepLen {
     SetUnion u;
     __host__ __device__ uint64_t operator()(uint64_t s) const {
@@ -146,7 +167,9 @@ struct SetStepLen {
         return (uint64_t)reinterpret_cast<const uint32_t *>(u.arena + it.nlen)[n];
     }
 };
-// cnt / rep of index_kernels.hip's node_stats_kernel, by union node; the window stops at the start of the step's path
+// Crowding statistics of the nodes (sgd_device.h crowd_shift), by union node: cnt[v] = steps on node v; rep[v] = the most visits
+// to v within any 64 consecutive steps of one path (a step counts its node's earlier visits among the 63 steps before it, not
+// looking across the start of its path).
 __global__ void set_node_stats_kernel(SetUnion u, uint32_t *cnt, uint32_t *rep) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < u.n_steps; s += stride) {
@@ -160,7 +183,8 @@ __global__ void set_node_stats_kernel(SetUnion u, uint32_t *cnt, uint32_t *rep) 
         if (c > 1 && rep[v] < c) atomicMax(&rep[v], c);
     }
 }
-// the step record of index_kernels.hip's fill_records_kernel, with the item's own slot and path id, into the item's array
+// rec[s] = { internal node slot | NO_NODE, path | rev<<31, pos lo, pos hi (23 bits) | a<<23 | b<<29 } with pos = scan[s] -
+// scan[first(path)], the slot and the path id the item's own, into the item's array
 __global__ void set_fill_records_kernel(SetUnion u, const uint64_t *scan, const uint32_t *cnt, const uint32_t *rep) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < u.n_steps; s += stride) {
@@ -200,12 +224,17 @@ __global__ void set_paths_kernel(SetUnion u, const uint64_t *scan) {
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 namespace {
-constexpr uint64_t round256(uint64_t b) { return (b + 255ull) & ~255ull; }
-// where the pieces of the scratch lie (bytes from its start); every piece 256-byte aligned
+// the pieces of the scratch, every piece 256-byte aligned; `bytes` is their sum
 struct Work {
-    uint64_t first, key_a, key_b, ids_a, ids_b, a, b, cnt, rep, scan, flags, tmp, tmp_bytes, total;
+    unsigned long long *first, *key_a, *key_b;
+    uint32_t *ids_a, *ids_b, *a, *b, *cnt, *rep;
+    uint64_t *scan;
+    uint32_t *flags;                                                       // [0]: lowest bad item; [1 + round]: a fixpoint round changed something
+    void *tmp;
+    size_t tmp_bytes;
+    uint64_t cnt_rep_bytes, bytes;                                         // (cnt and rep are adjacent: one memset zeroes both)
 };
-hipError_t plan_work(uint64_t N, uint64_t S, Work &w) {
+hipError_t plan_work(uint64_t N, uint64_t S, void *d_work, Work &w) {
     size_t sort_tmp = 0, scan_tmp = 0;
     hipError_t e = hipSuccess;
     if (N) e = rocprim::radix_sort_pairs(nullptr, sort_tmp, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
@@ -216,109 +245,111 @@ hipError_t plan_work(uint64_t N, uint64_t S, Work &w) {
         e = rocprim::exclusive_scan(nullptr, scan_tmp, lens, (uint64_t *)nullptr, (uint64_t)0, (size_t)(S + 1), rocprim::plus<uint64_t>(), 0);
         if (e != hipSuccess) return e;
     }
+    const uintptr_t base = reinterpret_cast<uintptr_t>(d_work);            // (null where only the size is asked for)
     uint64_t at = 0;
-    auto take = [&at](uint64_t bytes) { const uint64_t here = at; at += round256(bytes ? bytes : 1); return here; };
-    w.first = take(N * 8); w.key_a = take(N * 8); w.key_b = take(N * 8);
-    w.ids_a = take(N * 4); w.ids_b = take(N * 4); w.a = take(N * 4); w.b = take(N * 4);
-    w.cnt = take(N * 4); w.rep = take(N * 4);                              // (adjacent: one memset zeroes both)
-    w.scan = take(S ? (S + 1) * 8 : 0);
-    w.flags = take((1 + 2 * JUMP_ROUNDS) * sizeof(uint32_t));
-    w.tmp_bytes = std::max<uint64_t>(sort_tmp, scan_tmp);
-    w.tmp = take(w.tmp_bytes);
-    w.total = at;
+    auto take = [&at, base](auto *&piece, uint64_t bytes) {
+        piece = reinterpret_cast<std::remove_reference_t<decltype(piece)>>(base + at);
+        at += round256(bytes ? bytes : 1);
+    };
+    take(w.first, N * 8); take(w.key_a, N * 8); take(w.key_b, N * 8);
+    take(w.ids_a, N * 4); take(w.ids_b, N * 4); take(w.a, N * 4); take(w.b, N * 4);
+    take(w.cnt, N * 4); take(w.rep, N * 4);
+    w.cnt_rep_bytes = round256(N ? N * 4 : 1) + N * 4;
+    take(w.scan, S ? (S + 1) * 8 : 0);
+    take(w.flags, (1 + 2 * JUMP_ROUNDS) * sizeof(uint32_t));
+    w.tmp_bytes = std::max(sort_tmp, scan_tmp);
+    take(w.tmp, w.tmp_bytes);
+    w.bytes = at;
     return hipSuccess;
 }
+const dim3 over_steps(SET_STEP_BLOCKS), over_nodes(SET_NODE_BLOCKS), block(SET_BLOCK);
 }  // namespace
 
 hipError_t index_set_work_bytes(uint64_t n_nodes, uint64_t n_steps, uint64_t *bytes) {
     Work w{};
-    const hipError_t e = plan_work(n_nodes, n_steps, w);
-    *bytes = w.total;
+    const hipError_t e = plan_work(n_nodes, n_steps, nullptr, w);
+    *bytes = w.bytes;
     return e;
 }
 
-hipError_t build_index_set_device(const SetUnion &u, void *d_work, uint32_t *bad_item, uint64_t *launches) {
+hipError_t index_set_layout_device(const SetUnion &u, void *d_work, bool layout_given, uint32_t *bad_item, uint64_t *launches) {
     *bad_item = SET_NO_BAD_ITEM;
     const uint64_t N = u.n_nodes, S = u.n_steps;
     Work w{};
-    hipError_t e = plan_work(N, S, w);
+    hipError_t e = plan_work(N, S, d_work, w);
     if (e != hipSuccess) return e;
-    unsigned char *base = static_cast<unsigned char *>(d_work);
-    auto *d_first = reinterpret_cast<unsigned long long *>(base + w.first);
-    auto *d_key_a = reinterpret_cast<unsigned long long *>(base + w.key_a), *d_key_b = reinterpret_cast<unsigned long long *>(base + w.key_b);
-    auto *d_ids_a = reinterpret_cast<uint32_t *>(base + w.ids_a), *d_ids_b = reinterpret_cast<uint32_t *>(base + w.ids_b);
-    auto *d_a = reinterpret_cast<uint32_t *>(base + w.a), *d_b = reinterpret_cast<uint32_t *>(base + w.b);
-    auto *d_cnt = reinterpret_cast<uint32_t *>(base + w.cnt), *d_rep = reinterpret_cast<uint32_t *>(base + w.rep);
-    auto *d_scan = reinterpret_cast<uint64_t *>(base + w.scan);
-    auto *d_flags = reinterpret_cast<uint32_t *>(base + w.flags);          // [0]: lowest bad item; [1 + round]: a fixpoint round changed something
-    void *d_tmp = base + w.tmp;
-    size_t tmp_bytes = w.tmp_bytes;
-    const dim3 over_steps(SET_STEP_BLOCKS), over_nodes(SET_NODE_BLOCKS), block(SET_BLOCK);
-
-    if ((e = hipMemsetAsync(d_flags, 0xFF, sizeof(uint32_t), 0)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(d_flags + 1, 0, 2 * JUMP_ROUNDS * sizeof(uint32_t), 0)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.flags, 0xFF, sizeof(uint32_t), 0)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.flags + 1, 0, 2 * JUMP_ROUNDS * sizeof(uint32_t), 0)) != hipSuccess) return e;
     *launches += 2;
     if (N) {
-        if ((e = hipMemsetAsync(d_first, 0xFF, N * 8, 0)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(w.first, 0xFF, N * 8, 0)) != hipSuccess) return e;
         ++*launches;
     }
     if (S) {
-        hipLaunchKernelGGL(set_first_visit_kernel, over_steps, block, 0, 0, u, d_first, d_flags);
+        hipLaunchKernelGGL(set_first_visit_kernel, over_steps, block, 0, 0, u, w.first, w.flags);
         ++*launches;
-        // the one read-back the build cannot do without: the kernels below index by step_node
-        if ((e = hipMemcpy(bad_item, d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess) return e;
+        // the one read-back the build cannot do without: the kernels below, and K3, index by step_node
+        if ((e = hipMemcpy(bad_item, w.flags, sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess) return e;
         if (*bad_item != SET_NO_BAD_ITEM) return hipSuccess;
     }
-    if (N) {
-        hipLaunchKernelGGL(set_first_key_kernel, over_nodes, block, 0, 0, u, d_first, d_key_a, d_ids_a);
-        e = rocprim::radix_sort_pairs(d_tmp, tmp_bytes, (uint64_t *)d_key_a, (uint64_t *)d_key_b, d_ids_a, d_ids_b, (size_t)N, 0, KEY_BITS, 0);
+    if (!N || layout_given) return hipGetLastError();
+    hipLaunchKernelGGL(set_first_key_kernel, over_nodes, block, 0, 0, u, w.first, w.key_a, w.ids_a);
+    e = rocprim::radix_sort_pairs(w.tmp, w.tmp_bytes, (uint64_t *)w.key_a, (uint64_t *)w.key_b, w.ids_a, w.ids_b, (size_t)N, 0, KEY_BITS, 0);
+    *launches += 2;
+    if (e != hipSuccess) return e;
+    uint32_t *d_ids = w.ids_b, *d_ids_other = w.ids_a;                     // ids in first-visit order (stable: unvisited nodes in index order)
+    if (S) {
+        // branches: run heads by pointer jumping along the runs, anchors, roots by pointer jumping along the anchors.  A round past
+        // the fixpoint changes nothing, so the rounds go out JUMP_CHUNK at a time and their flags come back in one copy.
+        uint32_t *d_a = w.a, *d_b = w.b;
+        auto jump_to_fixpoint = [&](uint32_t *&cur, uint32_t *&other, uint32_t *flags) -> hipError_t {
+            for (int round = 0; round < JUMP_ROUNDS; round += JUMP_CHUNK) {
+                for (int k = 0; k < JUMP_CHUNK; ++k) {
+                    hipLaunchKernelGGL(set_jump_kernel, over_nodes, block, 0, 0, cur, other, N, flags + round + k);
+                    std::swap(cur, other);
+                }
+                *launches += JUMP_CHUNK;
+                uint32_t changed[JUMP_CHUNK];
+                const hipError_t err = hipMemcpy(changed, flags + round, sizeof changed, hipMemcpyDeviceToHost);
+                if (err != hipSuccess) return err;
+                if (std::find(changed, changed + JUMP_CHUNK, 0u) != changed + JUMP_CHUNK) break;
+            }
+            return hipSuccess;
+        };
+        hipLaunchKernelGGL(set_run_up_kernel, over_nodes, block, 0, 0, u, w.first, d_a);
+        ++*launches;
+        if ((e = jump_to_fixpoint(d_a, d_b, w.flags + 1)) != hipSuccess) return e;                  // d_a = run head of every node
+        hipLaunchKernelGGL(set_anchor_kernel, over_nodes, block, 0, 0, u, w.first, d_a, d_b);
+        std::swap(d_a, d_b);
+        ++*launches;
+        if ((e = jump_to_fixpoint(d_a, d_b, w.flags + 1 + JUMP_ROUNDS)) != hipSuccess) return e;    // d_a = root of every node
+        hipLaunchKernelGGL(set_branch_key_kernel, over_nodes, block, 0, 0, u, w.first, d_a, d_ids, w.key_a);
+        // stable sort by key of the ids already in first-visit order: (key, first visit)
+        e = rocprim::radix_sort_pairs(w.tmp, w.tmp_bytes, (uint64_t *)w.key_a, (uint64_t *)w.key_b, d_ids, d_ids_other, (size_t)N, 0, KEY_BITS, 0);
         *launches += 2;
         if (e != hipSuccess) return e;
-        uint32_t *d_ids = d_ids_b, *d_ids_other = d_ids_a;                 // ids in first-visit order (stable: unvisited nodes in index order)
-        if (S) {
-            // branches: run heads by pointer jumping along the runs, anchors, roots by pointer jumping along the anchors.  A round past
-            // the fixpoint changes nothing, so the rounds go out JUMP_CHUNK at a time and their flags come back in one copy.
-            auto jump_to_fixpoint = [&](uint32_t *&cur, uint32_t *&other, uint32_t *flags) -> hipError_t {
-                for (int round = 0; round < JUMP_ROUNDS; round += JUMP_CHUNK) {
-                    for (int k = 0; k < JUMP_CHUNK; ++k) {
-                        hipLaunchKernelGGL(set_jump_kernel, over_nodes, block, 0, 0, cur, other, N, flags + round + k);
-                        std::swap(cur, other);
-                    }
-                    *launches += JUMP_CHUNK;
-                    uint32_t changed[JUMP_CHUNK];
-                    const hipError_t err = hipMemcpy(changed, flags + round, sizeof changed, hipMemcpyDeviceToHost);
-                    if (err != hipSuccess) return err;
-                    if (std::find(changed, changed + JUMP_CHUNK, 0u) != changed + JUMP_CHUNK) break;
-                }
-                return hipSuccess;
-            };
-            hipLaunchKernelGGL(set_run_up_kernel, over_nodes, block, 0, 0, u, d_first, d_a);
-            ++*launches;
-            if ((e = jump_to_fixpoint(d_a, d_b, d_flags + 1)) != hipSuccess) return e;                  // d_a = run head of every node
-            hipLaunchKernelGGL(set_anchor_kernel, over_nodes, block, 0, 0, u, d_first, d_a, d_b);
-            std::swap(d_a, d_b);
-            ++*launches;
-            if ((e = jump_to_fixpoint(d_a, d_b, d_flags + 1 + JUMP_ROUNDS)) != hipSuccess) return e;    // d_a = root of every node
-            hipLaunchKernelGGL(set_branch_key_kernel, over_nodes, block, 0, 0, u, d_first, d_a, d_ids, d_key_a);
-            // stable sort by key of the ids already in first-visit order: (key, first visit)
-            e = rocprim::radix_sort_pairs(d_tmp, tmp_bytes, (uint64_t *)d_key_a, (uint64_t *)d_key_b, d_ids, d_ids_other, (size_t)N, 0, KEY_BITS, 0);
-            *launches += 2;
-            if (e != hipSuccess) return e;
-            std::swap(d_ids, d_ids_other);
-        }
-        hipLaunchKernelGGL(set_scatter_rank_kernel, over_nodes, block, 0, 0, u, d_ids);
-        ++*launches;
+        std::swap(d_ids, d_ids_other);
     }
+    hipLaunchKernelGGL(set_scatter_rank_kernel, over_nodes, block, 0, 0, u, d_ids);
+    ++*launches;
+    return hipGetLastError();
+}
+
+hipError_t index_set_records_device(const SetUnion &u, void *d_work, uint64_t *launches) {
+    const uint64_t N = u.n_nodes, S = u.n_steps;
+    Work w{};
+    hipError_t e = plan_work(N, S, d_work, w);
+    if (e != hipSuccess) return e;
     if (S) {
         auto lens = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), SetStepLen{u});
-        e = rocprim::exclusive_scan(d_tmp, tmp_bytes, lens, d_scan, (uint64_t)0, (size_t)(S + 1), rocprim::plus<uint64_t>(), 0);
+        e = rocprim::exclusive_scan(w.tmp, w.tmp_bytes, lens, w.scan, (uint64_t)0, (size_t)(S + 1), rocprim::plus<uint64_t>(), 0);
         if (e != hipSuccess) return e;
-        if ((e = hipMemsetAsync(d_cnt, 0, (w.rep - w.cnt) + N * 4, 0)) != hipSuccess) return e;          // cnt and rep
-        hipLaunchKernelGGL(set_node_stats_kernel, over_steps, block, 0, 0, u, d_cnt, d_rep);
-        hipLaunchKernelGGL(set_fill_records_kernel, over_steps, block, 0, 0, u, d_scan, d_cnt, d_rep);
+        if ((e = hipMemsetAsync(w.cnt, 0, w.cnt_rep_bytes, 0)) != hipSuccess) return e;
+        hipLaunchKernelGGL(set_node_stats_kernel, over_steps, block, 0, 0, u, w.cnt, w.rep);
+        hipLaunchKernelGGL(set_fill_records_kernel, over_steps, block, 0, 0, u, w.scan, w.cnt, w.rep);
         *launches += 4;
     }
-    hipLaunchKernelGGL(set_paths_kernel, dim3(SET_PATH_BLOCKS), block, 0, 0, u, S ? d_scan : (const uint64_t *)nullptr);
+    hipLaunchKernelGGL(set_paths_kernel, dim3(SET_PATH_BLOCKS), block, 0, 0, u, S ? w.scan : (const uint64_t *)nullptr);
     ++*launches;
     return hipGetLastError();
 }

@@ -164,7 +164,7 @@ int gfs_shard_quotas(uint64_t updates, const uint64_t *rank_steps, uint32_t worl
     return GFS_OK;
 }
 
-// perm[k] = slot of dense node k — the rule gfs_ctx_create applies to ITS graph (index_kernels.hip, which explains it), here
+// perm[k] = slot of dense node k — the rule gfs_ctx_create applies to ITS graph (index_set_kernels.hip, which explains it), here
 // on the whole graph and on the host, so that all ranks store their replicas alike: nodes in the order the paths first step
 // on them, except that a run of first visits which does not start its path is placed right after the root-run node it
 // branches off (through its chain of anchors); unvisited nodes last, in index order.

@@ -13,7 +13,7 @@ namespace gfs {
 static constexpr uint32_t Q_NO_NODE = 0xFFFFFFFFu;
 
 // ---- the one per-pair function (sgd.rs:1252-1275) ---------------------------------------------------------------------
-// step record: { slot | NO_NODE, path | rev << 31, pos lo, pos hi (23 bits) | crowding exponents } (index_kernels.hip)
+// step record: { slot | NO_NODE, path | rev << 31, pos lo, pos hi (23 bits) | crowding exponents } (index_set_kernels.hip)
 __device__ __forceinline__ uint64_t rec_pos(const uint4 r) { return (uint64_t)r.z | ((uint64_t)(r.w & 0x7FFFFFu) << 32); }
 __device__ __forceinline__ uint32_t rec_path(const uint4 r) { return r.y & 0x7FFFFFFFu; }
 

@@ -126,7 +126,7 @@ __device__ __forceinline__ uint32_t rec_path(const uint4 &r) { return r.y & PATH
 // with many lanes of the SAME trip), receives dozens of full corrections of the same error at once and the positions
 // blow up (measured: NaN on graphs with 40-fold self-loops, profiles/r01/repeat_probe.log).  Every step record
 // therefore carries two small exponents of its node (in the spare top bits of its position's high word: bp positions
-// stay below 2^55), computed when the index is built (index_kernels.hip):
+// stay below 2^55), computed when the index is built (index_set_kernels.hip):
 //   a = ceil(log2(steps on the node)),  b = ceil(log2(most visits within any 64 consecutive steps of a path)),
 // and a term's mu is scaled by 2^-k, k = max over its two nodes of max(b, a - kshift): c concurrent corrections of
 // 1/c-th size add up to about one.  kshift = floor(log2(n_steps / (2 n_streams))) + 2 puts the onset at four times

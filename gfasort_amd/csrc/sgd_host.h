@@ -54,11 +54,6 @@ hipError_t warm_module_quality();
 hipError_t init_positions_device(const uint32_t *d_node_len, const uint32_t *d_perm, double *d_x, uint64_t n);
 hipError_t reorder_positions_device(const double *d_src, double *d_dst, const uint32_t *d_perm, uint64_t N, uint32_t D,
                                     int to_device, hipStream_t st);
-hipError_t first_visit_layout_device(const uint32_t *d_step_node, uint64_t n_steps, uint64_t n_nodes, const uint64_t *d_path_first,
-                                     uint32_t n_paths, uint32_t *d_perm, int *bad_out);
-hipError_t build_path_index_device(const uint32_t *d_step_node, const uint8_t *d_step_is_rev, const uint32_t *d_node_len,
-                                   const uint32_t *d_perm, const uint64_t *d_path_first, uint32_t n_paths,
-                                   uint64_t n_steps, uint64_t n_nodes, uint64_t *d_tmp, uint4 *d_rec, uint64_t *d_path_len);
 hipError_t sort_order_device(const double *d_x_layout, const uint32_t *d_perm, uint64_t n, uint64_t stride_doubles,
                              void *d_tmp, uint32_t **d_order_out);
 // what d_tmp must hold for n nodes: two buffers of keys and two of values

@@ -1,6 +1,9 @@
 """Context sets (gfs_ctx_set_*, csrc/capi_set.hip) on the host: the arena plan, and every refusal gfs_ctx_set_create makes before
 it touches a device.  No GPU needed; the build itself is held to gfs_ctx_create bit for bit in tests/test_gpu_ctx_set.py."""
 import ctypes as C
+import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -146,3 +149,65 @@ def test_valid_list_without_a_gpu_is_a_hip_error():
     with pytest.raises(hip.GfsError) as ei:
         hip.ContextSet([load("simple.gfa")])
     assert ei.value.code == E_HIP
+
+
+# ---- the planning arithmetic of the one driver (csrc/index_set_plan.h), in a program of its own -------------------------------------
+SANITIZED_MAIN = r"""
+#include "index_set_plan.h"
+#include <cstdio>
+#include <vector>
+
+static int failures = 0;
+static void expect(bool ok, const char *what, uint64_t a, uint64_t b, uint64_t c) {
+    if (!ok) { std::printf("%s at N=%llu S=%llu P=%llu\n", what, (unsigned long long)a, (unsigned long long)b, (unsigned long long)c); ++failures; }
+}
+static uint64_t up(uint64_t b) { return (b + 255) / 256 * 256; }
+
+int main() {
+    const uint64_t Ns[] = {0, 1, 63, 64, 65, 70001, 0x7FFFFFFFull}, Ss[] = {0, 1, 15, 16, 17, 255, 256, 257, 123457, 1ull << 40},
+                   Ps[] = {0, 1, 31, 32, 33, 0x7FFFFFFFull};
+    for (uint64_t N : Ns) for (uint64_t S : Ss) for (uint64_t P : Ps) {
+        // the arena of a single context: a set of one item — exactly five offsets are written
+        std::vector<uint64_t> off(gfs::SET_KINDS);
+        const uint64_t arena = gfs::set_arena_plan(&N, &S, &P, 1, off.data());
+        const uint64_t rec = up((S + 1) * 16), prec = up((P ? P : 1) * 16), plen = up((P ? P : 1) * 8), perm = up((N ? N : 1) * 4);
+        expect(off[0] == 0 && off[1] == rec && off[2] == rec + prec && off[3] == rec + prec + plen && off[4] == rec + prec + plen + perm,
+               "one-item offsets", N, S, P);
+        expect(arena == rec + prec + plen + 2 * perm, "one-item arena", N, S, P);
+        // the input head of one item and of seven: [step_node | path_first | item table | step_is_rev]
+        for (uint64_t n : {1ull, 7ull}) {
+            const gfs::SetInputHead h = gfs::set_input_head(S, P, n);
+            expect(h.at_first == up(4 * S) && h.at_items == up(4 * S) + up(8 * (P + 1)) &&
+                   h.at_rev == up(4 * S) + up(8 * (P + 1)) + up(64 * (n + 1)) && h.bytes == h.at_rev + up(S), "input head", N, S, P);
+            expect(h.at_first % 256 == 0 && h.at_items % 256 == 0 && h.at_rev % 256 == 0 && h.bytes % 256 == 0, "input head alignment", N, S, P);
+            expect(h.at_first >= 4 * S && h.at_items - h.at_first >= 8 * (P + 1) && h.at_rev - h.at_items >= 64 * (n + 1) && h.bytes - h.at_rev >= S,
+                   "input head room", N, S, P);
+        }
+    }
+    // two items: by kind, then by item, in arrays that hold exactly ten offsets
+    const uint64_t nn[2] = {5, 0}, ns[2] = {0, 37}, np[2] = {0, 3};
+    std::vector<uint64_t> off(2 * gfs::SET_KINDS);
+    const uint64_t arena = gfs::set_arena_plan(nn, ns, np, 2, off.data());
+    const uint64_t want[10] = {0, 1024, 1536, 2048, 2560, 256, 1280, 1792, 2304, 2816};
+    for (int k = 0; k < 10; ++k) expect(off[k] == want[k], "two items", k, off[k], want[k]);
+    expect(arena == 3072, "two items arena", arena, 0, 0);
+    std::printf("%d failures\n", failures);
+    return failures ? 1 : 0;
+}
+"""
+
+
+def test_plan_arithmetic_under_sanitizers(tmp_path):
+    """index_set_plan.h in a program of its own, built with -fsanitize=address,undefined (it is not loaded into Python): the arena
+    of a single context — a set of one — and the input head in front of the build's scratch, against the formulas written out, at
+    counts either side of the 256-byte alignment and at the limits of a context; the offset arrays hold exactly what is written."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cxx = os.environ.get("CXX") or shutil.which("g++")
+    assert cxx, "no C++ compiler"
+    src = tmp_path / "plan_main.cpp"
+    src.write_text(SANITIZED_MAIN)
+    exe = tmp_path / "plan_main"
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(root, "gfasort_amd", "csrc"), "-o", str(exe), str(src)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and "0 failures" in r.stdout, (r.stdout, r.stderr)

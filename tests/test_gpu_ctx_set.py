@@ -1,14 +1,12 @@
 """Context sets on the device (gfs_ctx_set_*, csrc/capi_set.hip, K3b in csrc/index_set_kernels.hip): every item of a set built
 in one pass over the disjoint union of its graphs holds, bit for bit, what gfs_ctx_create gives for that graph alone — the index
 build is integer arithmetic, so there is no tolerance anywhere in this file."""
-import ctypes as C
-import gc
-
 import numpy as np
 import pytest
 
 from util import G, P, load, graph_from_paths, gaussian_init, absent_node_graph, self_loop_graph, reverse_short_paths_graph, \
     crowding_edge_graph, NO_NODE
+from index_ref import HostIndex, free_device_bytes as _free_bytes
 from gfasort_amd import hip
 from gfasort_amd import sgd as S
 
@@ -55,21 +53,6 @@ def mix():
     cset.close()
 
 
-def _free_bytes():
-    """Free device memory as hipMemGetInfo of the library's own runtime reports it (a symbol lookup on the library's handle
-    searches its dependencies), with the device idle.  The figure is the whole device's, so whatever else this process still
-    holds must not change between two samples: garbage of earlier tests (contexts in reference cycles free their device memory
-    when the collector gets to them) is collected first."""
-    gc.collect()
-    L = hip.lib()
-    L.hipMemGetInfo.argtypes = [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-    L.hipDeviceSynchronize.argtypes = []
-    free, total = C.c_size_t(0), C.c_size_t(0)
-    assert L.hipDeviceSynchronize() == 0
-    assert L.hipMemGetInfo(C.byref(free), C.byref(total)) == 0
-    return int(free.value)
-
-
 def _outcome(fn):
     """What a call gives, comparable: its bytes, or the library's error code."""
     try:
@@ -86,10 +69,15 @@ def _setup_1d(ctx, g):
 
 
 def _same_index(item, solo, where):
+    """Item and solo context hold the same bits — and, now that both are built by the same kernels, each is ALSO held to the
+    host's restatement of their graph (index_ref.py: gfs_shared_node_layout and the numpy records), which shares no code with them."""
     assert np.array_equal(item.node_layout(), solo.node_layout()), where
     got, want = item.step_records(), solo.step_records()
     assert got.shape == want.shape and got.tobytes() == want.tobytes(), where
     assert not got[-1].any(), where                                    # the padding record
+    host = HostIndex(solo.graph)
+    host.check(item, f"{where}: item")
+    host.check(solo, f"{where}: solo")
 
 
 # ---- 1: a hostile mix -------------------------------------------------------------------------------------------------------------
@@ -146,6 +134,9 @@ def test_union_past_every_grid():
         graphs.append(drb1); kind.append(3)
     solos = [hip.Context(g) for g in tiny + [drb1]]
     want = [(c.node_layout(), c.step_records().tobytes()) for c in solos]
+    hosts = [HostIndex(g) for g in tiny + [drb1]]                       # the host's restatement, once per distinct graph
+    for k, (host, solo) in enumerate(zip(hosts, solos)):
+        host.check(solo, f"solo {k}")
     cset = hip.ContextSet(graphs)
     try:
         info = cset.info()
@@ -153,6 +144,8 @@ def test_union_past_every_grid():
         for i, (item, k) in enumerate(zip(cset.contexts, kind)):
             assert np.array_equal(item.node_layout(), want[k][0]), (i, k)
             assert item.step_records().tobytes() == want[k][1], (i, k)
+            assert np.array_equal(item.node_layout(), hosts[k].layout), (i, k)
+            assert item.step_records().tobytes() == hosts[k].records.tobytes(), (i, k)
     finally:
         cset.close()
         for c in solos:

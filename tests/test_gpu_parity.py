@@ -489,7 +489,7 @@ def test_bundled_nd_quality_matches_reference_streams():
 
 
 def test_internal_node_layout_is_path_order_and_invisible():
-    """The device stores positions in first-visit path order with branches placed where they branch off (index_kernels.hip);
+    """The device stores positions in first-visit path order with branches placed where they branch off (index_set_kernels.hip);
     upload/download/trace speak dense indices."""
     from gfasort_amd.distributed import path_order_layout
     g = load("DRB1-3123.gfa")
@@ -1023,7 +1023,7 @@ def test_one_rank_rccl_group_runs_the_merge_path():
 
 
 def test_device_node_layout_with_unvisited_nodes_absent_steps_and_bad_indices():
-    """The first-visit layout and the range check of step_node run on the device (index_kernels.hip)."""
+    """The first-visit layout and the range check of step_node run on the device (index_set_kernels.hip)."""
     from gfasort_amd.distributed import path_order_layout
     rng = np.random.default_rng(11)
     n, S = 5000, 40000

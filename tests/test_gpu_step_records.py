@@ -1,7 +1,8 @@
-"""The 16-byte step records (index_kernels.hip K3, format sgd_device.h) and the crowding rule that reads them, exactly.
+"""The 16-byte step records (index_set_kernels.hip K3, format sgd_device.h) and the crowding rule that reads them, exactly.
 
-G1  every record field by field against a numpy restatement of K3: node slot, path id and reverse bit, the 55-bit position,
-    the crowding exponents a (steps on the node) and b (visits within 64 consecutive steps of a path), the zeroed padding record.
+G1  every record field by field against a numpy restatement of K3 (index_ref.py): node slot, path id and reverse bit, the 55-bit
+    position, the crowding exponents a (steps on the node) and b (visits within 64 consecutive steps of a path), the zeroed padding
+    record; and the shapes at which a single context, built as a union of one item, can still go wrong.
 G2  the crowding onset kshift the kernels are handed, and its per-context override.
 G3  reference streams with kshift = 0 (the `a` rule) on one stream, 1D and nD, fused and per-iteration, == the oracle bit for bit.
 G4  one team wave with kshift = 0 and 1 (the `a` rule in every trip form) == the oracle's mirror bit for bit.
@@ -13,11 +14,10 @@ import pytest
 
 from util import (O, G, P, load, oracle_graph, oracle_params, gaussian_init, crowding_edge_graph, hub_graph, np_crowding,
                   graph_from_paths, NO_NODE)
+from index_ref import POS_HI, HostIndex, np_records, same_records, free_device_bytes
 from gfasort_amd import hip
 
 pytestmark = pytest.mark.gpu
-
-POS_HI = 0x7FFFFF
 
 
 def _ygs(g, iter_max, mtu=None):
@@ -40,26 +40,6 @@ def _node_slots(g):
     return path_order_layout(g)
 
 
-def np_records(g, perm, crowd=None):
-    """K3 restated: rec[s] = {perm[n] | NO_NODE, path | rev << 31, pos lo, pos hi (23 bits) | a << 23 | b << 29}, padding zero."""
-    S = g.n_steps
-    sn = g.step_node.astype(np.int64)
-    present = sn != NO_NODE
-    pos, _ = g.step_positions()
-    pos = pos.astype(np.uint64)
-    _, _, a, b = crowd if crowd is not None else np_crowding(g)
-    first = g.path_first_step.astype(np.int64)
-    path = np.repeat(np.arange(g.n_paths, dtype=np.int64), np.diff(first))
-    rec = np.zeros((S + 1, 4), dtype=np.uint32)
-    safe = np.where(present, sn, 0)
-    rec[:S, 0] = np.where(present, np.asarray(perm, dtype=np.int64)[safe], NO_NODE)
-    rec[:S, 1] = (path | (g.step_is_rev.astype(np.int64) << 31)).astype(np.uint32)
-    rec[:S, 2] = (pos & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-    crowd_w = np.where(present, (a[safe] << 23) | (b[safe] << 29), 0)
-    rec[:S, 3] = (((pos >> np.uint64(32)).astype(np.int64) & POS_HI) | crowd_w).astype(np.uint32)
-    return rec
-
-
 def _check_records(g, node_perm=None):
     crowd = np_crowding(g)
     ctx = hip.Context(g, node_perm=node_perm)
@@ -70,10 +50,7 @@ def _check_records(g, node_perm=None):
         assert np.array_equal(perm, node_perm)
     want = np_records(g, perm, crowd)
     assert rec.shape == (g.n_steps + 1, 4)
-    assert not rec[-1].any(), "padding record not zero"
-    for f, name in enumerate(("node slot", "path | rev", "pos lo", "pos hi | a | b")):
-        bad = np.nonzero(rec[:, f] != want[:, f])[0]
-        assert bad.size == 0, f"{name}: {bad.size} records differ, first at step {bad[:5]}: {rec[bad[:5], f]} != {want[bad[:5], f]}"
+    same_records(rec, want)
     return rec, crowd
 
 
@@ -148,6 +125,102 @@ def test_step_records_past_2_to_the_53():
     pos, plen = g.step_positions()
     assert int(pos.max()) >= 1 << 53 and int(plen.max()) > 1 << 53
     assert ((rec[:-1, 3] & POS_HI) > 0).mean() > 0.9                   # the high word is in use nearly everywhere
+
+
+# ---- G1b: a single context is a union of one item ---------------------------------------------------------------------
+E_ARG = -1
+_LONG_RUN = 40                                                         # nodes of one run of first visits
+
+
+def _edge_case(name):
+    """(graph, node_perm or None, refused).  Small graphs at the seams of the one-item union."""
+    perm = None
+    if name == "no_steps":
+        g = graph_from_paths([[], []], [3, 1, 4])
+    elif name == "no_paths":
+        g = graph_from_paths([], [2, 3, 5])
+        assert g.path_first_step.tolist() == [0]
+    elif name == "empty_first_and_last_path":                           # the item's first step must still start a path
+        g = graph_from_paths([[], [2, 0, 1, 0, 3], []], [3, 1, 4, 1])
+    elif name == "absent_first_step":                                   # the anchor look-up at p == NO_NODE
+        g = graph_from_paths([[NO_NODE, 1, 2, 0], [2, 3, 4, 0]], [3, 1, 4, 1, 5], rev=[0, 1, 0, 0, 1, 0, 0, 1])
+    elif name == "branch_off_a_long_run":                               # head of the run: log2(40) > 4 rounds, a second chunk
+        g = graph_from_paths([list(range(_LONG_RUN)), [_LONG_RUN // 2, _LONG_RUN, _LONG_RUN + 1, _LONG_RUN // 2 + 1]],
+                             np.arange(1, _LONG_RUN + 3))
+    elif name == "odd_nodes_unvisited":                                 # they go last, in index order
+        g = graph_from_paths([[0, 2, 4, 6, 8], [8, 4, 10, 0]], np.arange(1, 13))
+    elif name in ("given_layout", "given_layout_bad_step"):
+        g = graph_from_paths([[NO_NODE, 1, 2, 0], [2, 3, 4, 0], [5, 5]], [3, 1, 4, 1, 5, 9, 2])
+        perm = np.array([4, 0, 6, 2, 5, 1, 3], dtype=np.uint32)
+        if name == "given_layout_bad_step":
+            bad = g.step_node.copy()
+            bad[5] = g.n_nodes
+            g = G.FlatGraph(node_len=g.node_len, step_node=bad, step_is_rev=g.step_is_rev, path_first_step=g.path_first_step,
+                            node_ids=g.node_ids, path_names=g.path_names)
+    elif name == "no_nodes_no_steps":
+        g = graph_from_paths([[]], [])
+    elif name == "no_nodes_absent_steps":
+        g = graph_from_paths([[NO_NODE, NO_NODE, NO_NODE]], [])
+    elif name == "no_nodes_one_real_step":                              # refused before anything is indexed by the step's node
+        g = graph_from_paths([[NO_NODE, 0]], [])
+    return g, perm, name in ("given_layout_bad_step", "no_nodes_one_real_step")
+
+
+EDGE_CASES = ["no_steps", "no_paths", "empty_first_and_last_path", "absent_first_step", "branch_off_a_long_run", "odd_nodes_unvisited",
+              "given_layout", "given_layout_bad_step", "no_nodes_no_steps", "no_nodes_absent_steps", "no_nodes_one_real_step"]
+
+
+@pytest.mark.parametrize("name", EDGE_CASES)
+def test_single_context_edge_cases(name):
+    """gfs_ctx_create builds its context as a union of ONE item through the set's kernels.  For each graph that builds: the layout
+    is the host's (gfs_shared_node_layout) or the given one, the records are the numpy restatement's field by field, and — where a
+    path has two steps or more — one reference stream, which finds its steps through the path records the DEVICE now writes,
+    ends where the oracle's ends, bit for bit.  A refused graph is refused with "step_node out of range" and leaves no device
+    memory behind."""
+    g, node_perm, refused = _edge_case(name)
+    if refused:
+        hip.Context(graph_from_paths([[0, 1]], [1, 1])).close()         # (modules loaded, the runtime's pools warm)
+        free = [free_device_bytes()]
+        for _ in range(2):
+            with pytest.raises(hip.GfsError) as ei:
+                hip.Context(g, node_perm=node_perm)
+            assert ei.value.code == E_ARG and "step_node out of range" in str(ei.value) and "set item" not in str(ei.value)
+            del ei                                                      # (the traceback holds the frame of the failed create)
+            free.append(free_device_bytes())
+        print("free device memory before, after one and after two refused creates:", free)
+        assert free[1] == free[0] and free[2] == free[0]
+        return
+    host = HostIndex(g)
+    ctx = hip.Context(g, node_perm=node_perm)
+    try:
+        if node_perm is None:
+            host.check(ctx, name)
+        else:
+            assert np.array_equal(ctx.node_layout(), node_perm)
+            assert not np.array_equal(node_perm, host.layout)           # (the given layout is not the one the device would derive)
+            same_records(ctx.step_records(), np_records(g, node_perm, host.crowd), name)
+        if name == "odd_nodes_unvisited":
+            odd = np.arange(1, g.n_nodes, 2)
+            assert ctx.node_layout()[odd].tolist() == list(range(g.n_nodes - odd.size, g.n_nodes))
+        if name == "branch_off_a_long_run":                             # the branch sits right after the node it branches off
+            lay = ctx.node_layout()
+            assert lay[_LONG_RUN] == lay[_LONG_RUN // 2] + 1 and lay[_LONG_RUN + 1] == lay[_LONG_RUN // 2] + 2
+        if g.n_nodes == 0 or np.diff(g.path_first_step.astype(np.int64)).max(initial=0) < 2:
+            return
+        p = _ygs(g, 1, 300)
+        og = oracle_graph(g)
+        x_ref = O.init_positions(og)
+        rc, st, _ = O.sgd_1d(og, oracle_params(p), x_ref, n_streams=1)
+        ctx.setup_1d(p, hip.make_config(n_streams=1, flags=hip.F_BUNDLE(1)))
+        ctx.init_positions()
+        ctx.run()
+        hst = ctx.stats()
+        x = ctx.download()
+        assert rc == 0 and hst.term_updates == st.term_updates == 2 * 300 and hst.attempts == st.attempts
+        assert np.array_equal(x.view(np.uint64), x_ref.view(np.uint64))
+        assert not np.array_equal(x, hip.init_positions(g))             # (the stream moved something)
+    finally:
+        ctx.close()
 
 
 # ---- G2 ----------------------------------------------------------------------------------------------------------

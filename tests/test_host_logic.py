@@ -248,7 +248,7 @@ def test_subgraph_keeps_nodes_and_selected_paths():
 
 
 def _layout_reference(g):
-    """The node layout rule, restated with plain loops (gfs_shared_node_layout / index_kernels.hip): first-visit path order,
+    """The node layout rule, restated with plain loops (gfs_shared_node_layout / index_set_kernels.hip): first-visit path order,
     except that a run of first visits which does not start its path goes right after the root-run node it branches off."""
     N, S = g.n_nodes, g.n_steps
     node = g.step_node
