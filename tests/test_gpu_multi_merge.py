@@ -4,7 +4,7 @@ logic of gfs_rank_*) against the numpy restatement of tests/multi_restatement.py
 An in-process cluster: W hip.Rank objects on device 0, one process, one thread, one reference stream per rank; the test is
 the collective.  Per window every rank's exchange buffer, the sum and every rank's replica after the apply are compared;
 at the finish every rank's masked vector in device order and the final positions.  The buffers bound into the ranks are
-the caller's, allocated through the HIP runtime the library itself is linked to (`Dev` below) and summed on the host in
+the caller's, allocated through the HIP runtime the library itself is linked to (`Dev`, tests/device_raw.py) and summed on the host in
 the payload type: the suite's process cannot also start torch's own copy of the runtime once the library's is in use, so
 the tensors of RankDriver are left to the tests that run it in processes of their own (tests/test_gpu_parity.py).
 
@@ -20,66 +20,13 @@ import numpy as np
 import pytest
 
 import multi_cases as MC
+from device_raw import Dev, download as _download, rt as _rt, sync as _sync, upload as _upload
 from multi_restatement import bits, hexval
 from util import O, oracle_graph, oracle_params
 from gfasort_amd import hip
 from gfasort_amd.distributed import SHARDING, subgraph
 
 pytestmark = pytest.mark.gpu
-
-H2D, D2H = 1, 2
-
-
-def _rt():
-    """The HIP runtime the library is linked to, through the library's own handle (a symbol lookup on it searches its
-    dependencies): the copies below go through the same runtime as the kernels."""
-    L = hip.lib()
-    if not getattr(L, "_merge_test_rt", False):
-        L.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        L.hipFree.argtypes = [C.c_void_p]
-        L.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        L.hipStreamSynchronize.argtypes = [C.c_void_p]
-        L.hipDeviceSynchronize.argtypes = []
-        L._merge_test_rt = True
-    return L
-
-
-def _sync():
-    assert _rt().hipDeviceSynchronize() == 0
-
-
-def _download(ptr, count, dtype):
-    host = np.empty(int(count), dtype=dtype)
-    assert _rt().hipMemcpy(host.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), host.nbytes, D2H) == 0
-    return host
-
-
-def _upload(ptr, host):
-    host = np.ascontiguousarray(host)
-    assert _rt().hipMemcpy(C.c_void_p(ptr), host.ctypes.data_as(C.c_void_p), host.nbytes, H2D) == 0
-
-
-class Dev:
-    """`count` elements of `dtype` in device memory, zeroed; the caller's buffer a rank is bound to."""
-
-    def __init__(self, count, dtype):
-        self.count, self.dtype = int(count), np.dtype(dtype)
-        p = C.c_void_p()
-        assert self.count > 0 and _rt().hipMalloc(C.byref(p), self.count * self.dtype.itemsize) == 0
-        self.ptr = p.value
-        _upload(self.ptr, np.zeros(self.count, dtype=self.dtype))
-
-    def host(self):
-        return _download(self.ptr, self.count, self.dtype)
-
-    def set(self, host):
-        assert host.dtype == self.dtype and host.shape == (self.count,)
-        _upload(self.ptr, host)
-
-    def free(self):
-        if self.ptr:
-            assert _rt().hipFree(C.c_void_p(self.ptr)) == 0
-            self.ptr = None
 
 
 def _same(cl, got, want, where, space):
