@@ -14,9 +14,9 @@ LIB     := $(LIBDIR)/libgfasort_hip.so
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -munsafe-fp-atomics -Wall -Wno-unused-function
 CXXFLAGS := -O2 -std=c++17 -Wall -ffp-contract=off
 
-KERNELS := sgd_kernels_1d sgd_kernels_1d_phased sgd_kernels_nd sgd_kernels_nd_team sgd_kernels_nd_team_wide sgd_kernels_batch batch_readout_kernels batch_quality_kernels batch_diagnosis_kernels batch_sort_quality_kernels index_kernels index_set_kernels quality_kernels capi capi_batch capi_set host_tables multi
+KERNELS := sgd_kernels_1d sgd_kernels_1d_phased sgd_kernels_nd sgd_kernels_nd_team sgd_kernels_nd_team_wide sgd_kernels_batch batch_readout_kernels batch_quality_kernels batch_diagnosis_kernels batch_sort_quality_kernels index_kernels index_set_kernels set_setup_kernels quality_kernels capi capi_batch capi_set host_tables multi
 OBJS    := $(KERNELS:%=$(OBJDIR)/%.o)
-HDRS    := $(CSRC)/sgd_device.h $(CSRC)/sgd_kernel_common.h $(CSRC)/sgd_1d.h $(CSRC)/sgd_nd.h $(CSRC)/sgd_nd_team.h $(CSRC)/sgd_batch.h $(CSRC)/batch_plan.h $(CSRC)/batch_readout_plan.h $(CSRC)/readout_region.h $(CSRC)/quality_device.h $(CSRC)/segment_sort.h $(CSRC)/segment_device.h $(CSRC)/sort_key.h $(CSRC)/sgd_limits.h $(CSRC)/launch_policy.h $(CSRC)/capi_error.h $(CSRC)/device_memory.h $(CSRC)/sgd_host.h $(CSRC)/capi_ctx.h $(CSRC)/index_set.h $(CSRC)/index_set_plan.h include/gfasort_hip.h
+HDRS    := $(CSRC)/sgd_device.h $(CSRC)/sgd_kernel_common.h $(CSRC)/sgd_1d.h $(CSRC)/sgd_nd.h $(CSRC)/sgd_nd_team.h $(CSRC)/sgd_batch.h $(CSRC)/batch_plan.h $(CSRC)/batch_readout_plan.h $(CSRC)/readout_region.h $(CSRC)/quality_device.h $(CSRC)/segment_sort.h $(CSRC)/segment_device.h $(CSRC)/sort_key.h $(CSRC)/sgd_limits.h $(CSRC)/launch_policy.h $(CSRC)/capi_error.h $(CSRC)/device_memory.h $(CSRC)/sgd_host.h $(CSRC)/capi_ctx.h $(CSRC)/index_set.h $(CSRC)/index_set_plan.h $(CSRC)/set_seed.h $(CSRC)/set_state_plan.h include/gfasort_hip.h
 HOSTSRC := $(HOST)/graph.cpp $(HOST)/sgd.cpp
 HOSTHDR := $(HOST)/graph.hpp $(HOST)/sgd.hpp
 

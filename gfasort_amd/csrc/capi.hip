@@ -4,6 +4,8 @@
 // launch_policy.h; the host tables are host_tables.hip's; batches of contexts are capi_batch.hip's (capi_ctx.h is what the two share).
 #include "capi_ctx.h"
 #include "index_set.h"
+#include "set_seed.h"
+#include "set_state_plan.h"
 
 #include <algorithm>
 #include <chrono>
@@ -40,6 +42,7 @@ int gfs_warmup(int device) {
     laps.lap("module 1d");
     HIPCHK(gfs::warm_module_index());
     HIPCHK(gfs::warm_module_index_set());
+    HIPCHK(gfs::warm_module_set_setup());
     HIPCHK(gfs::warm_module_quality());
     laps.lap("module index");
     HIPCHK(gfs::warm_module_nd());
@@ -71,7 +74,7 @@ int gfs_warmup(int device) {
 // resident context
 // ---------------------------------------------------------------------------------------------
 // what a setup allocates, let go before the next one (the index of gfs_ctx_create and the read-outs' scratch stay)
-static void free_sgd_state(gfs_ctx *c) {
+void gfs::free_sgd_state(gfs_ctx *c) {
     c->d_zetas.reset();
     c->d_x.reset();                                                       // (a bound pointer is the caller's: only dropped)
     c->d_rng.reset();
@@ -109,10 +112,8 @@ static int upload_zeta_table(gfs_ctx *c, const gfs_sgd_params *p, const double *
     const uint64_t zlen_full = c->shape.zlen_full;
     std::vector<double> ztab;
     if (!zetas) {
-        const uint64_t m = c->shape.zlen_staged - 1;                // last staged index
-        const uint64_t need_i = m <= p->space_max ? m : p->space_max + (m - p->space_max - 1) * p->space_quantization_step;
         gfs_sgd_params q = *p;
-        q.space = std::min<uint64_t>(p->space, std::max<uint64_t>(need_i, 1));
+        q.space = gfs::zeta_clamped_space(*p, c->shape.zlen_staged);
         std::vector<double> part(gfs_zeta_table_len(&q));
         gfs_zeta_table(&q, part.data());
         ztab.assign(zlen_full, 0.0);
@@ -127,9 +128,12 @@ static int upload_zeta_table(gfs_ctx *c, const gfs_sgd_params *p, const double *
 gfs::IterConsts gfs::iter_consts(const gfs_ctx *c, uint64_t k) { return gfs::iter_consts(c->params, c->etas, c->shape, k); }
 
 // The resident table of the whole schedule's constants (d_its_all); again whenever the phase window moves, whose marks it carries.
+void gfs::schedule_table(const gfs_sgd_params &p, const std::vector<double> &etas, const gfs::LaunchShape &s, gfs::IterConsts *out) {
+    for (uint64_t k = 0; k <= p.iter_max; ++k) out[k] = gfs::iter_consts(p, etas, s, k);
+}
 static int upload_schedule(gfs_ctx *c) {
     std::vector<gfs::IterConsts> all(c->params.iter_max + 1);
-    for (uint64_t k = 0; k <= c->params.iter_max; ++k) all[k] = gfs::iter_consts(c, k);
+    gfs::schedule_table(c->params, c->etas, c->shape, all.data());
     HIPCHK(hipMemcpy(c->d_its_all, all.data(), all.size() * sizeof(gfs::IterConsts), hipMemcpyHostToDevice));
     return GFS_OK;
 }
@@ -149,10 +153,12 @@ static const void *fused_kernel(const gfs::KernelShape &s, bool pooled) {
 // Workgroups of `fn` one CU holds at once with this context's block size and LDS table (registers, waves per SIMD and the table
 // all count).  Also: the first launch of a kernel function costs the host ~0.1 ms (the runtime materialises the function
 // lazily), and a caller that brackets its launch with events pays that inside the bracket; this resolves the function at setup.
-static int resident_blocks_per_cu(const gfs_ctx *c, const void *fn, int *per_cu) {
+static int resident_blocks_per_cu(const gfs::LaunchShape &s, const void *fn, int *per_cu, std::string *err) {
     hipFuncAttributes attr;
-    HIPCHK(hipFuncGetAttributes(&attr, fn));
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, fn, (int)c->shape.block, c->shape.lds_bytes));
+    hipError_t e = hipFuncGetAttributes(&attr, fn);
+    if (e != hipSuccess) { *err = std::string("hipFuncGetAttributes(&attr, fn): ") + hipGetErrorString(e); return GFS_E_HIP; }
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, fn, (int)s.block, s.lds_bytes);
+    if (e != hipSuccess) { *err = std::string("hipOccupancyMaxActiveBlocksPerMultiprocessor: ") + hipGetErrorString(e); return GFS_E_HIP; }
     return GFS_OK;
 }
 
@@ -165,11 +171,9 @@ static hipError_t launch(const gfs_ctx *c, const void *fn, gfs::KArgs &a, const 
     return hipLaunchKernel(fn, grid, block, args, s.lds_bytes, st);
 }
 
-// Resolves c->plan for c->shape as shape_before_residency left it, asks the runtime for the fused team kernel's residency and
+// Resolves the plan for the shape as shape_before_residency left it, asks the runtime for the fused team kernel's residency and
 // lets shape_after_residency finish the shape (which may lower n_streams).
-static int plan_launches(gfs_ctx *c) {
-    gfs::LaunchShape &s = c->shape;
-    LaunchPlan &pl = c->plan;
+static int plan_launches(int cu_count, gfs::LaunchShape &s, LaunchPlan &pl, std::string *err) {
     pl = LaunchPlan{};
     const gfs::KernelShape shape{s.dims, s.bundle, s.lds_tables, s.atomic_loads, s.trace};
     const bool team = s.team, ref = s.bundle == 1;
@@ -179,18 +183,59 @@ static int plan_launches(gfs_ctx *c) {
     const void *pooled_kernel = s.phased ? gfs::phased_fused_kernel(s.lds_tables) : (team || ref) ? fused_kernel(shape, true) : nullptr;
     const void *free_kernel = team && !s.phased && free_running ? fused_kernel(shape, false) : nullptr;   // (K1e, K1d, K2d: pools only)
     if (!pl.iteration || (s.phased && !pl.window_iteration) || ((team || ref) && !pooled_kernel) ||
-        (team && !s.phased && free_running && !free_kernel))
-        return fail(GFS_E_UNSUPPORTED, "no kernel is built for dims=" + std::to_string(s.dims) + " bundle=" + std::to_string(s.bundle) +
-                                           " lds_tables=" + std::to_string(s.lds_tables) + " atomic_loads=" + std::to_string(s.atomic_loads) +
-                                           " trace=" + std::to_string(s.trace) + " phased=" + std::to_string(s.phased));
+        (team && !s.phased && free_running && !free_kernel)) {
+        *err = "no kernel is built for dims=" + std::to_string(s.dims) + " bundle=" + std::to_string(s.bundle) +
+               " lds_tables=" + std::to_string(s.lds_tables) + " atomic_loads=" + std::to_string(s.atomic_loads) +
+               " trace=" + std::to_string(s.trace) + " phased=" + std::to_string(s.phased);
+        return GFS_E_UNSUPPORTED;
+    }
     int per_cu = 0;
     if (team) {                                                            // (the measurement behind it: shape_after_residency)
-        int rc = resident_blocks_per_cu(c, pooled_kernel, &per_cu);
+        int rc = resident_blocks_per_cu(s, pooled_kernel, &per_cu, err);
         if (rc) return rc;
     }
-    gfs::shape_after_residency(per_cu, gfs::DeviceFacts{c->cu_count}, &s);
+    gfs::shape_after_residency(per_cu, gfs::DeviceFacts{cu_count}, &s);
     if (s.fused) pl.fused = s.pooled ? pooled_kernel : free_kernel;
     return GFS_OK;
+}
+
+// ---- a setup's host half (capi_ctx.h: shared with gfs_ctx_set_setup_*, capi_set.hip) -------------------------------------------
+int gfs::plan_setup(const gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs_launch_config *cfg, const double *etas,
+                    gfs::SetupPlan *out, std::string *err) {
+    gfs::SetupPlan &sp = *out;
+    sp = gfs::SetupPlan{};
+    sp.params = *p;
+    sp.cfg = cfg ? *cfg : gfs_launch_config{};
+    sp.dims = dims;
+    sp.rc = GFS_NOTHING_TO_DO;
+    if (c->n_nodes == 0) return sp.rc;
+    // positions.  A context with nothing to do (no path of more than one step: sgd.rs:250-261 returns before any
+    // update) still owns a full-length position replica: a multi-GPU rank whose shard holds no such path must be able to
+    // upload, bind, merge and download like its peers — its contribution to every merge is a zero delta of the same size.
+    sp.x_len = dims ? c->n_nodes * 2 * (uint64_t)dims : c->n_nodes;
+    if (!c->valid_paths) return sp.rc;
+
+    // launch shape (launch_policy.h): decided before anything of the run's state is allocated
+    const gfs::GraphFacts graph{c->n_nodes, c->n_steps, c->n_paths, c->max_path_steps, c->valid_paths, c->path_counts.data()};
+    int rc = gfs::shape_before_residency(graph, gfs::DeviceFacts{c->cu_count}, p, dims, cfg, &sp.shape, err);
+    if (rc) return rc;
+    rc = plan_launches(c->cu_count, sp.shape, sp.plan, err);              // (may lower n_streams)
+    if (rc) return rc;
+    // eta schedule (host, bit-exact) unless supplied
+    sp.etas.resize(p->iter_max + 1);
+    if (etas) std::copy(etas, etas + p->iter_max + 1, sp.etas.begin());
+    else gfs_sgd_schedule(p, sp.etas.data());
+    return sp.rc = GFS_OK;
+}
+
+void gfs::commit_setup(gfs_ctx *c, gfs::SetupPlan &&sp) {
+    const bool has_work = sp.rc == GFS_OK;
+    c->params = sp.params; c->cfg = sp.cfg; c->dims = sp.dims; c->x_len = sp.x_len;
+    c->shape = has_work ? sp.shape : gfs::LaunchShape{};
+    c->plan = has_work ? sp.plan : LaunchPlan{};
+    if (!has_work) return;
+    c->etas = std::move(sp.etas);
+    c->events_used = 0; c->kernel_ms_harvested = 0.0; c->iterations = 0; c->total_ms = 0.0;
 }
 
 static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs_launch_config *cfg,
@@ -200,54 +245,37 @@ static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs
     int rc = gfs::check_setup_args(p, dims, cfg, &err);                    // (refused before the context is touched)
     if (rc) return fail(rc, err);
     HIPCHK(hipSetDevice(c->device));
-    free_sgd_state(c);
-    c->shape = gfs::LaunchShape{};
-    c->plan = LaunchPlan{};
-    c->params = *p;
-    c->cfg = cfg ? *cfg : gfs_launch_config{};
-    c->dims = dims;
-    c->x_len = 0;
-    if (c->n_nodes == 0) { c->configured = true; return GFS_NOTHING_TO_DO; }
+    gfs::free_sgd_state(c);
+    gfs::SetupPlan sp;
+    const int planned = gfs::plan_setup(c, p, dims, cfg, etas, &sp, &err);
+    uint64_t bytes[GFS_STATE_KINDS];
+    for (uint32_t k = 0; k < GFS_STATE_KINDS; ++k) bytes[k] = gfs::state_bytes(sp, k);
+    gfs::commit_setup(c, std::move(sp));                                   // (a refused shape leaves no shape, plan or schedule behind)
+    if (c->x_len) {                                                        // (before the policy's verdict: a refused shape keeps its replica)
+        HIPCHK(c->d_x.grow(bytes[GFS_STATE_POSITIONS]));
+        HIPCHK(hipMemset(c->d_x, 0, bytes[GFS_STATE_POSITIONS]));
+    }
+    if (planned < 0) return fail(planned, err);
+    if (planned == GFS_NOTHING_TO_DO) { c->configured = true; return GFS_NOTHING_TO_DO; }
 
-    // positions.  A context with nothing to do (no path of more than one step: sgd.rs:250-261 returns before any
-    // update) still owns a full-length position replica: a multi-GPU rank whose shard holds no such path must be able to
-    // upload, bind, merge and download like its peers — its contribution to every merge is a zero delta of the same size.
-    c->x_len = dims ? c->n_nodes * 2 * (uint64_t)dims : c->n_nodes;
-    HIPCHK(c->d_x.grow(c->x_len * 8));
-    HIPCHK(hipMemset(c->d_x, 0, c->x_len * 8));
-    if (!c->valid_paths) { c->configured = true; return GFS_NOTHING_TO_DO; }
-
-    // launch shape (launch_policy.h): decided before anything of the run's state is allocated
-    const gfs::GraphFacts graph{c->n_nodes, c->n_steps, c->n_paths, c->max_path_steps, c->valid_paths, c->path_counts.data()};
-    rc = gfs::shape_before_residency(graph, gfs::DeviceFacts{c->cu_count}, p, dims, cfg, &c->shape, &err);
-    if (rc) return fail(rc, err);
-    rc = plan_launches(c);                                               // (may lower n_streams)
-    if (rc) return rc;
-    const uint64_t n_streams = c->shape.n_streams;
-
-    // eta schedule and zeta table (host, bit-exact) unless supplied
-    c->etas.resize(p->iter_max + 1);
-    if (etas) std::copy(etas, etas + p->iter_max + 1, c->etas.begin());
-    else gfs_sgd_schedule(p, c->etas.data());
+    // zeta table (host, bit-exact) unless supplied
     rc = upload_zeta_table(c, p, zetas);
     if (rc) return rc;
-
-    HIPCHK(c->d_rng.grow(4 * n_streams * 8));
-    if (c->shape.bundle > 1) {                                           // team kernels, sort and layout
-        HIPCHK(c->d_lead.grow(8 * n_streams * sizeof(uint32_t)));
-        HIPCHK(hipMemset(c->d_lead, 0, 8 * n_streams * sizeof(uint32_t)));      // trips left = 0: no pass yet
+    HIPCHK(c->d_rng.grow(bytes[GFS_STATE_RNG]));
+    if (bytes[GFS_STATE_LEAD]) {
+        HIPCHK(c->d_lead.grow(bytes[GFS_STATE_LEAD]));
+        HIPCHK(hipMemset(c->d_lead, 0, bytes[GFS_STATE_LEAD]));             // trips left = 0: no pass yet
     }
-    HIPCHK(c->d_counters.grow(kCounterBytes));
-    if (c->cfg.trace_per_stream) {
-        HIPCHK(c->d_trace.grow(n_streams * c->cfg.trace_per_stream * sizeof(gfs_term)));
-        HIPCHK(hipMemset(c->d_trace, 0, n_streams * c->cfg.trace_per_stream * sizeof(gfs_term)));
-        HIPCHK(c->d_trace_cnt.grow(n_streams * sizeof(uint32_t)));
+    HIPCHK(c->d_counters.grow(bytes[GFS_STATE_COUNTERS]));
+    if (bytes[GFS_STATE_TRACE]) {
+        HIPCHK(c->d_trace.grow(bytes[GFS_STATE_TRACE]));
+        HIPCHK(hipMemset(c->d_trace, 0, bytes[GFS_STATE_TRACE]));
+        HIPCHK(c->d_trace_cnt.grow(bytes[GFS_STATE_TRACE_COUNTS]));
     }
     rc = seed_streams(c);
     if (rc) return rc;
-    if ((c->shape.team || c->shape.bundle == 1) && c->params.iter_max < (1u << 20)) {
-        // the whole schedule's per-iteration constants, for fused launches over consecutive iterations
-        HIPCHK(c->d_its_all.grow((c->params.iter_max + 1) * sizeof(gfs::IterConsts)));
+    if (bytes[GFS_STATE_SCHEDULE]) {
+        HIPCHK(c->d_its_all.grow(bytes[GFS_STATE_SCHEDULE]));
         rc = upload_schedule(c);
         if (rc) return rc;
     }
@@ -613,6 +641,26 @@ int gfs_ctx_debug_step_records(const gfs_ctx *c, uint32_t *out, uint64_t n_words
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, c->d_step_rec, (c->n_steps + 1) * sizeof(uint4), hipMemcpyDeviceToHost));
+    return GFS_OK;
+}
+int gfs_ctx_debug_sgd_state(gfs_ctx *c, uint32_t which, void *out, uint64_t bytes) {
+    if (!c) return fail(GFS_E_ARG, "ctx is null");
+    const uint32_t kind = which & ~GFS_STATE_SIZE_OF;
+    if (kind >= GFS_STATE_KINDS) return fail(GFS_E_ARG, "no such state array");
+    if (!c->configured) return fail(GFS_E_STATE, "context not set up");
+    const void *arrays[GFS_STATE_KINDS] = {c->d_x.p, c->d_counters.p, c->d_lead.p, c->d_trace.p, c->d_trace_cnt.p, c->d_rng.p, c->d_zetas.p, c->d_its_all.p};
+    const uint64_t size = arrays[kind] ? gfs::state_bytes(kind, c->d_rng.p != nullptr, c->x_len, c->shape, c->params, c->cfg) : 0;
+    if (which & GFS_STATE_SIZE_OF) {
+        if (!out || bytes != sizeof(uint64_t)) return fail(GFS_E_ARG, "the size of a state array is one uint64_t");
+        *static_cast<uint64_t *>(out) = size;
+        return GFS_OK;
+    }
+    if (bytes != size) return fail(GFS_E_ARG, "state array length mismatch: it has " + std::to_string(size) + " bytes");
+    if (!size) return GFS_OK;
+    if (!out) return fail(GFS_E_ARG, "null argument");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, arrays[kind], size, hipMemcpyDeviceToHost));
     return GFS_OK;
 }
 int gfs_ctx_debug_kshift(gfs_ctx *c, int32_t set, int32_t *kshift_out) {

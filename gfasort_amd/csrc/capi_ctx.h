@@ -152,6 +152,53 @@ GFS_LOCAL int build_contexts(const gfs_graph_view *const *graphs, gfs_ctx *const
                              bool staged, Laps *laps, gfs_ctx_set_info *info);
 }  // namespace gfs
 
+// capi.hip, for capi_set.hip: the ONE text of a setup's host half, which gfs_ctx_setup_* and gfs_ctx_set_setup_* share.
+namespace gfs {
+// What a setup decides on the host before it touches its context: the launch shape and the kernels (launch_policy.h, the
+// residency query in the middle), the eta schedule, the length of the position vector.  rc: GFS_OK, or GFS_NOTHING_TO_DO for a
+// graph of 0 nodes (x_len 0) or without a path of more than one step (x_len set: it still gets its zeroed replica), and then
+// shape, plan and etas are untouched.
+struct SetupPlan {
+    int rc = GFS_OK;
+    int dims = 0;
+    uint64_t x_len = 0;
+    gfs_sgd_params params{};
+    gfs_launch_config cfg{};
+    LaunchShape shape;
+    LaunchPlan plan;
+    std::vector<double> etas;
+};
+// Reads c's facts, writes nothing of c.  p, dims and cfg have passed check_setup_args.  A refusal returns its code with its text
+// in *err; out->x_len is set by then (the single call allocates its positions before the policy runs).
+GFS_LOCAL int plan_setup(const gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs_launch_config *cfg, const double *etas,
+                         SetupPlan *out, std::string *err);
+// Bytes of state array `kind` (GFS_STATE_*) that a setup of this shape makes, 0 for one it does not: the sizes gfs_ctx_setup_*
+// allocates, a set's arena is planned with and gfs_ctx_debug_sgd_state reads.  has_work: the setup returned GFS_OK.
+inline uint64_t state_bytes(uint32_t kind, bool has_work, uint64_t x_len, const LaunchShape &s, const gfs_sgd_params &p, const gfs_launch_config &cfg) {
+    if (kind == GFS_STATE_POSITIONS) return x_len * 8;
+    if (!has_work) return 0;
+    const uint64_t T = s.n_streams;
+    switch (kind) {
+    case GFS_STATE_COUNTERS: return kCounterBytes;
+    case GFS_STATE_LEAD: return s.bundle > 1 ? 8 * T * sizeof(uint32_t) : 0;          // team kernels, sort and layout
+    case GFS_STATE_TRACE: return T * cfg.trace_per_stream * sizeof(gfs_term);
+    case GFS_STATE_TRACE_COUNTS: return cfg.trace_per_stream ? T * sizeof(uint32_t) : 0;
+    case GFS_STATE_RNG: return 4 * T * 8;
+    case GFS_STATE_ZETAS: return s.zlen_full * 8;
+    // the whole schedule's per-iteration constants, for fused launches over consecutive iterations
+    case GFS_STATE_SCHEDULE: return (s.team || s.bundle == 1) && p.iter_max < (1u << 20) ? (p.iter_max + 1) * sizeof(IterConsts) : 0;
+    default: return 0;
+    }
+}
+inline uint64_t state_bytes(const SetupPlan &sp, uint32_t kind) { return state_bytes(kind, sp.rc == GFS_OK, sp.x_len, sp.shape, sp.params, sp.cfg); }
+// the table of the whole schedule's constants (d_its_all), iterations 0..=iter_max, into out
+GFS_LOCAL void schedule_table(const gfs_sgd_params &p, const std::vector<double> &etas, const LaunchShape &s, IterConsts *out);
+// what a setup allocates or borrows, let go; the context is not set up afterwards
+GFS_LOCAL void free_sgd_state(gfs_ctx *c);
+// c's host fields from the plan, and the run's statistics back to zero; the state arrays are the caller's to put in place
+GFS_LOCAL void commit_setup(gfs_ctx *c, SetupPlan &&sp);
+}  // namespace gfs
+
 // capi.hip, for capi_batch.hip
 namespace gfs {
 GFS_LOCAL void fill_kargs(const gfs_ctx *c, KArgs &a);

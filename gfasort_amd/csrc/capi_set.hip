@@ -1,9 +1,12 @@
 // capi_set.hip — the context sets of the C ABI (include/gfasort_hip.h, gfs_ctx_set_*): many gfs_ctx (capi.hip, capi_ctx.h) built
 // from many graph views in ONE pass over their disjoint union (K3b, index_set_kernels.hip), and the driver of that build, which
 // gfs_ctx_create shares: a single context is a set of one.  The items' index arrays live in one arena the set owns, the items
-// borrow them; what a setup allocates stays each item's own.
+// borrow them.  What gfs_ctx_setup_* allocates stays each item's own; gfs_ctx_set_setup_* sets every item up in one pass (K3c,
+// set_setup_kernels.hip), their state arrays in a second arena of the set's.
 #include "capi_ctx.h"
 #include "index_set.h"
+#include "set_seed.h"
+#include "set_state_plan.h"
 
 #include <algorithm>
 #include <chrono>
@@ -14,8 +17,11 @@
 struct gfs_ctx_set {
     int device = 0;
     gfs::Buffer arena;                              // every item's step records, path records, path lengths, node layout, node lengths
-    std::vector<std::unique_ptr<gfs_ctx>> items;    // (declared after the arena: they go first)
+    gfs::Buffer state_arena;                        // gfs_ctx_set_setup_*: every item's state arrays, the seeding kernel's tables behind them
+    gfs::Buffer h_stage{true};                      // ... and the pinned staging of what a set setup sends up; both kept between setups
+    std::vector<std::unique_ptr<gfs_ctx>> items;    // (declared after the arenas: they go first)
     gfs_ctx_set_info info{};
+    gfs_ctx_set_setup_info setup_info{};
 };
 
 namespace {
@@ -140,7 +146,168 @@ int gfs::build_contexts(const gfs_graph_view *const *graphs, gfs_ctx *const *ctx
     return GFS_OK;
 }
 
+// ---- set setup (K3c) -------------------------------------------------------------------------------------------------------------
+// Every item set up as gfs_ctx_setup_1d / _nd would (dims[i] = 0 / 1..8), in one pass: the host half of each (capi.hip plan_setup,
+// the single call's own text) before anything is touched; then one arena, one memset, one copy, one launch.
+static int set_setup(gfs_ctx_set *s, const std::vector<const gfs_sgd_params *> &params, const std::vector<int> &dims,
+                     const gfs_launch_config *cfgs, int32_t *item_rc) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t n = s->items.size();
+    std::string err;
+    for (uint64_t i = 0; i < n; ++i) {                                     // (no item is touched, no device call is made, before all pass)
+        if (dims[i] < 0) return fail(GFS_E_UNSUPPORTED, item_prefix(i) + "dimensions must be 1..8");   // as gfs_ctx_setup_nd: before its other arguments
+        if (int rc = gfs::check_setup_args(params[i], dims[i], cfgs ? &cfgs[i] : nullptr, &err)) return fail(rc, item_prefix(i) + err);
+    }
+    HIPCHK(hipSetDevice(s->device));
+
+    // 1. host: every item's launch shape, kernels and schedule; then where its state arrays lie
+    std::vector<gfs::SetupPlan> plans(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        const int rc = gfs::plan_setup(s->items[i].get(), params[i], dims[i], cfgs ? &cfgs[i] : nullptr, nullptr, &plans[i], &err);
+        if (rc < 0) return fail(rc, item_prefix(i) + err);
+    }
+    constexpr int K = gfs::SET_STATE_KINDS;
+    std::vector<uint64_t> bytes(K * n), offsets(K * n);
+    gfs_ctx_set_setup_info info{};
+    info.items = n;
+    std::vector<gfs::SeedItem> seeds;                                      // the items with streams (rng: filled in once the arena is there)
+    std::vector<uint64_t> seed_of;                                         // ... and which items they are
+    uint64_t total_blocks = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const gfs::SetupPlan &sp = plans[i];
+        for (int k = 0; k < K; ++k) bytes[K * i + k] = gfs::state_bytes(sp, (uint32_t)k);
+        if (sp.rc != GFS_OK) { ++info.nothing_to_do; continue; }
+        ++info.configured;
+        info.total_streams += sp.shape.n_streams;
+        seeds.push_back(gfs::SeedItem{nullptr, sp.params.seed + sp.cfg.stream_base, (uint32_t)sp.shape.n_streams, (uint32_t)total_blocks});
+        seed_of.push_back(i);
+        total_blocks += (sp.shape.n_streams + gfs::SEED_BLOCK - 1) / gfs::SEED_BLOCK;
+        if (total_blocks > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, "set items 0.." + std::to_string(i) + " have more streams together than one seeding launch holds");
+    }
+    // the arena: [positions, counters, team state, traces, trace counts | RNG words | zeta tables, schedule tables, seeding tables]
+    const uint64_t arrays_end = gfs::set_state_plan(bytes.data(), n, offsets.data());
+    const uint64_t zero_end = gfs::set_state_kind_begin(offsets.data(), GFS_STATE_RNG);
+    const uint64_t upload_begin = gfs::set_state_kind_begin(offsets.data(), GFS_STATE_ZETAS);
+    const uint64_t seeds_at = arrays_end, blocks_at = seeds_at + gfs::round256(seeds.size() * sizeof(gfs::SeedItem));
+    const uint64_t arena_bytes = blocks_at + gfs::round256(total_blocks * sizeof(uint32_t)), stage_bytes = arena_bytes - upload_begin;
+    info.state_bytes = arena_bytes;
+
+    // ---- from here on the items are touched: a failure leaves every one of them not set up and the arena released ----
+    HIPCHK(hipDeviceSynchronize());                                        // (nothing of an earlier run in flight on what goes or is written over)
+    for (auto &c : s->items) gfs::free_sgd_state(c.get());                 // borrows dropped, arrays of an item's own setup freed
+    int rc = GFS_OK;
+    auto ok = [&rc, s](const char *what, hipError_t e) {                   // false: rc holds the reported error, the arena is gone
+        if (e == hipSuccess) return true;
+        (void)hipDeviceSynchronize();
+        s->state_arena.reset();
+        rc = fail(GFS_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+        return false;
+    };
+    if (s->state_arena.bytes < arena_bytes) {
+        ++info.device_allocations;
+        if ((rc = s->state_arena.reserve(arena_bytes, "hipMalloc set state arena"))) return rc;
+    }
+    if (s->h_stage.bytes < stage_bytes) {
+        ++info.device_allocations;
+        if ((rc = s->h_stage.reserve(stage_bytes, "hipHostMalloc set state staging"))) { s->state_arena.reset(); return rc; }
+    }
+    unsigned char *d_arena = s->state_arena.as<unsigned char>(), *h = s->h_stage.as<unsigned char>();
+    auto staged = [h, upload_begin](uint64_t arena_offset) { return h + (arena_offset - upload_begin); };
+
+    // 2. zeta tables: items that share (theta, space_max, step) get slices of one running sum;  3. staging: the tables, the schedule
+    // tables and the seeding kernel's two tables, where the arena has them
+    if (stage_bytes) std::memset(h, 0, stage_bytes);                       // (the zero padding of every zeta table up to zlen_full)
+    {
+        std::vector<gfs_sgd_params> clamped(n);
+        std::vector<uint8_t> needed(n, 0);
+        for (uint64_t i = 0; i < n; ++i) {
+            if (plans[i].rc != GFS_OK) continue;
+            clamped[i] = plans[i].params;
+            clamped[i].space = gfs::zeta_clamped_space(plans[i].params, plans[i].shape.zlen_staged);
+            needed[i] = 1;
+        }
+        const gfs::SharedZetaTables shared = gfs::shared_zeta_tables(clamped.data(), needed.data(), n);
+        for (uint64_t i = 0; i < n; ++i) {
+            if (!needed[i]) continue;
+            const gfs::SetupPlan &sp = plans[i];
+            gfs::zeta_slice(shared.tables[shared.table_of[i]], clamped[i], sp.shape.zlen_full, reinterpret_cast<double *>(staged(offsets[K * i + GFS_STATE_ZETAS])));
+            if (bytes[K * i + GFS_STATE_SCHEDULE])
+                gfs::schedule_table(sp.params, sp.etas, sp.shape, reinterpret_cast<gfs::IterConsts *>(staged(offsets[K * i + GFS_STATE_SCHEDULE])));
+        }
+    }
+    uint32_t *h_block_item = reinterpret_cast<uint32_t *>(staged(blocks_at));
+    for (size_t k = 0; k < seeds.size(); ++k) {
+        seeds[k].rng = reinterpret_cast<uint64_t *>(d_arena + offsets[K * seed_of[k] + GFS_STATE_RNG]);
+        const uint64_t nb = (seeds[k].n_streams + gfs::SEED_BLOCK - 1) / gfs::SEED_BLOCK;
+        for (uint64_t b = 0; b < nb; ++b) h_block_item[seeds[k].first_block + b] = (uint32_t)k;
+    }
+    if (!seeds.empty()) std::memcpy(staged(seeds_at), seeds.data(), seeds.size() * sizeof(gfs::SeedItem));
+
+    // 4. one memset over everything a setup zeroes; one copy; 5. one launch over the concatenated streams
+    if (zero_end) {
+        if (!ok("hipMemset set state", hipMemsetAsync(d_arena, 0, zero_end, 0))) return rc;
+        ++info.launches;
+    }
+    if (stage_bytes) {
+        if (!ok("hipMemcpy set state", hipMemcpyAsync(d_arena + upload_begin, h, stage_bytes, hipMemcpyHostToDevice, 0))) return rc;
+        ++info.copies;
+    }
+    if (total_blocks) {
+        if (!ok("set_seed_streams_kernel", gfs::seed_streams_device(reinterpret_cast<const gfs::SeedItem *>(d_arena + seeds_at),
+                                                                    reinterpret_cast<const uint32_t *>(d_arena + blocks_at), (uint32_t)total_blocks, 0))) return rc;
+        ++info.launches;
+    }
+    if (!ok("hipDeviceSynchronize", hipDeviceSynchronize())) return rc;     // (the staging is free again; a fault shows here)
+
+    for (uint64_t i = 0; i < n; ++i) {
+        gfs_ctx *c = s->items[i].get();
+        const uint64_t *at = &offsets[K * i], *size = &bytes[K * i];
+        auto lend = [d_arena, at, size](gfs::Buffer &b, uint32_t kind) { if (size[kind]) (void)b.borrow(d_arena + at[kind]); };
+        if (item_rc) item_rc[i] = plans[i].rc;
+        gfs::commit_setup(c, std::move(plans[i]));
+        lend(c->d_x, GFS_STATE_POSITIONS); lend(c->d_counters, GFS_STATE_COUNTERS); lend(c->d_lead, GFS_STATE_LEAD);
+        lend(c->d_trace, GFS_STATE_TRACE); lend(c->d_trace_cnt, GFS_STATE_TRACE_COUNTS); lend(c->d_rng, GFS_STATE_RNG);
+        lend(c->d_zetas, GFS_STATE_ZETAS); lend(c->d_its_all, GFS_STATE_SCHEDULE);
+        c->configured = true;
+    }
+    info.setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    s->setup_info = info;
+    return GFS_OK;
+}
+
 extern "C" {
+
+int gfs_ctx_set_state_plan(const uint64_t *bytes, uint64_t n, uint64_t *offsets, uint64_t *arena_bytes) {
+    if (!arena_bytes || (n && (!bytes || !offsets))) return fail(GFS_E_ARG, "null argument");
+    *arena_bytes = gfs::set_state_plan(bytes, n, offsets);
+    return GFS_OK;
+}
+
+int gfs_ctx_set_setup_1d(gfs_ctx_set *s, const gfs_sgd_params *params, const gfs_launch_config *cfgs, int32_t *item_rc) {
+    if (!s) return fail(GFS_E_ARG, "set is null");
+    if (!params) return fail(GFS_E_ARG, "params is null");
+    const uint64_t n = s->items.size();
+    std::vector<const gfs_sgd_params *> p(n);
+    for (uint64_t i = 0; i < n; ++i) p[i] = &params[i];
+    return set_setup(s, p, std::vector<int>(n, 0), cfgs, item_rc);
+}
+int gfs_ctx_set_setup_nd(gfs_ctx_set *s, const gfs_layout_params *params, const gfs_launch_config *cfgs, int32_t *item_rc) {
+    if (!s) return fail(GFS_E_ARG, "set is null");
+    if (!params) return fail(GFS_E_ARG, "params is null");
+    const uint64_t n = s->items.size();
+    std::vector<const gfs_sgd_params *> p(n);
+    std::vector<int> dims(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        p[i] = &params[i].sgd;
+        dims[i] = params[i].dimensions >= 1 && params[i].dimensions <= GFS_MAX_DIMS ? (int)params[i].dimensions : -1;   // (-1: refused by set_setup, in item order)
+    }
+    return set_setup(s, p, dims, cfgs, item_rc);
+}
+int gfs_ctx_set_get_setup_info(const gfs_ctx_set *s, gfs_ctx_set_setup_info *out) {
+    if (!s || !out) return fail(GFS_E_ARG, "null argument");
+    *out = s->setup_info;
+    return GFS_OK;
+}
 
 int gfs_ctx_set_plan(const uint64_t *n_nodes, const uint64_t *n_steps, const uint64_t *n_paths, uint64_t n, uint64_t *offsets,
                      uint64_t *arena_bytes) {

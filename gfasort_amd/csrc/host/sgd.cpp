@@ -261,16 +261,19 @@ using BatchHandle = std::unique_ptr<gfs_batch, Destroy>;     // borrows its cont
 // set: gfs_ctx_destroy leaves an item alone (it goes with its set), so the handle of an item owns nothing, and ctx.reset() on
 // an item only lets go of it — its index arrays and what its setup allocated stay on the device until the set is destroyed at the
 // end of the driver (graphs of fewer than SET_MAX_NODES nodes: a few hundred KB each), where a context of its own is freed at once.
-struct Slot { CtxHandle ctx; FlatGraph f; };
+// set_up: the item was set up with its set (gfs_ctx_set_setup_*), and rc is what its setup returned.
+struct Slot { CtxHandle ctx; FlatGraph f; bool set_up = false; int rc = GFS_OK; };
 using SetHandle = std::unique_ptr<gfs_ctx_set, Destroy>;     // owns its items: declared before the slots and the batch, so that it goes last
 constexpr size_t SET_MAX_NODES = 16384;                       // graphs of fewer nodes are a batch's candidates under the default policy
 }  // namespace
 
 // The contexts of the graphs a batch can take — wanted(i), fewer than SET_MAX_NODES nodes, flags that ask for bundle 0 (auto) or
-// 1 — built in ONE gfs_ctx_set instead of one gfs_ctx_create each (K3b).  Their slots are flattened and hold their item; every
-// other slot is left for open_slot.  Empty when no graph qualifies.
-template <class Items, class Wanted>
-static SetHandle open_set(std::vector<Slot> &slots, const Items &items, const HipOptions &opt, uint8_t verbose, Wanted wanted) {
+// 1 — built in ONE gfs_ctx_set instead of one gfs_ctx_create each (K3b), and set up in ONE pass instead of one gfs_ctx_setup_* each
+// (K3c): setup_all(set, idx, item_rc) calls gfs_ctx_set_setup_1d / _nd with the parameters of the graphs idx, in item order.  Their
+// slots are flattened, hold their item and what its setup returned; every other slot is left for open_slot.  Empty when no graph
+// qualifies.
+template <class Items, class Wanted, class SetupAll>
+static SetHandle open_set(std::vector<Slot> &slots, const Items &items, const HipOptions &opt, uint8_t verbose, Wanted wanted, SetupAll setup_all) {
     const uint32_t bundle = (opt.cfg.flags >> 16) & 0xFFu;
     std::vector<size_t> idx;
     std::vector<gfs_graph_view> views;
@@ -295,12 +298,23 @@ static SetHandle open_set(std::vector<Slot> &slots, const Items &items, const Hi
         std::cerr << "[gfasort_hip] batch: contexts of " << info.items << " graphs built together, " << info.build_ms << " ms, "
                   << info.launches << " launches\n";
     }
+    std::vector<int32_t> rcs(idx.size(), GFS_OK);
+    check(setup_all(s, idx, rcs.data()));
+    if (verbose >= 2) {
+        gfs_ctx_set_setup_info info{};
+        check(gfs_ctx_set_get_setup_info(s, &info));
+        std::cerr << "[gfasort_hip] batch: " << info.items << " graphs set up together, " << info.setup_ms << " ms, " << info.device_allocations
+                  << " allocations, " << info.copies << " copies, " << info.launches << " launches\n";
+    }
     // (last, after everything that can throw: a slot must never hold an item of a set that has already gone)
-    for (size_t k = 0; k < idx.size(); ++k) slots[idx[k]].ctx.reset(gfs_ctx_set_item(s, k));
+    for (size_t k = 0; k < idx.size(); ++k) {
+        slots[idx[k]].ctx.reset(gfs_ctx_set_item(s, k));
+        slots[idx[k]].set_up = true; slots[idx[k]].rc = rcs[k];
+    }
     return set;
 }
 
-// Flatten g and create its context, unless open_set has done both, and set the context up with setup(ctx).  Returns what setup
+// Flatten g, create its context and set it up with setup(ctx), unless open_set has done all three.  Returns what the setup
 // returned: on GFS_NOTHING_TO_DO the slot has let go of its context (a context of its own is destroyed, an item stays with its
 // set), otherwise it is resident and `stats` says what it will run.
 template <class Setup>
@@ -312,7 +326,7 @@ static int open_slot(Slot &s, const BidirectedGraph &g, gfs_stats &stats, Setup 
         check(gfs_ctx_create(&v, 0, &c));
         s.ctx.reset(c);
     }
-    const int rc = setup(c);
+    const int rc = s.set_up ? s.rc : setup(c);                           // (a graph that runs alone keeps the single call)
     check(rc);
     if (rc == GFS_NOTHING_TO_DO) s.ctx.reset();
     else check(gfs_ctx_stats(c, &stats));
@@ -392,7 +406,12 @@ gfs_batch_stats sgd_sort_batch(std::vector<BatchSortItem> &items, uint8_t verbos
                                double diagnose_ratio, bool keep_sort_quality) {
     SetHandle set;                                                                    // (outlives the slots and the batch)
     std::vector<Slot> slots(items.size());
-    set = open_set(slots, items, opt, verbose, [](size_t) { return true; });
+    set = open_set(slots, items, opt, verbose, [](size_t) { return true; }, [&](gfs_ctx_set *s, const std::vector<size_t> &idx, int32_t *rcs) {
+        std::vector<gfs_sgd_params> ps;
+        for (size_t i : idx) ps.push_back(items[i].params.to_c());
+        const std::vector<gfs_launch_config> cfgs(idx.size(), opt.cfg);
+        return gfs_ctx_set_setup_1d(s, ps.data(), cfgs.data(), rcs);
+    });
     gfs_batch_stats bs{};
     // reorder the graph by its rank order, keep what was asked for, free the context
     auto apply = [&](size_t i, std::vector<double> &&x, const auto *order, size_t n) {
@@ -488,7 +507,13 @@ Layout path_linear_sgd_layout(const BidirectedGraph &g, const LayoutSGDParams &p
 gfs_batch_stats sgd_layout_batch(std::vector<BatchLayoutItem> &items, uint8_t verbose, const HipOptions &opt, bool keep_profile, double diagnose_ratio) {
     SetHandle set;                                                                    // (outlives the slots and the batch)
     std::vector<Slot> slots(items.size());
-    set = open_set(slots, items, opt, verbose, [&](size_t i) { return items[i].params.dimensions == 2 || items[i].params.dimensions == 3; });
+    set = open_set(slots, items, opt, verbose, [&](size_t i) { return items[i].params.dimensions == 2 || items[i].params.dimensions == 3; },
+                   [&](gfs_ctx_set *s, const std::vector<size_t> &idx, int32_t *rcs) {
+        std::vector<gfs_layout_params> ps;
+        for (size_t i : idx) ps.push_back(items[i].params.to_c());
+        const std::vector<gfs_launch_config> cfgs(idx.size(), opt.cfg);
+        return gfs_ctx_set_setup_nd(s, ps.data(), cfgs.data(), rcs);
+    });
     gfs_batch_stats bs{};
     // a graph that runs alone: the single call, after the slot has let go of its context (an item of the set stays resident beside it)
     auto finish_alone = [&](size_t i) {

@@ -33,8 +33,8 @@ inline int32_t h_sat_i32(double v) {
 }
 
 // rand_core's seed_from_u64: how every Xoshiro256+ state is seeded, the kernels' streams (capi.hip seed_streams, sgd.rs:431-432)
-// and the host's generators (host_tables.hip) alike.
-inline uint64_t splitmix64(uint64_t &s) {
+// and the host's generators (host_tables.hip) alike; on the device for a set's streams (set_setup_kernels.hip).
+GFS_HOST_DEVICE uint64_t splitmix64(uint64_t &s) {
     uint64_t z = (s += 0x9E3779B97F4A7C15ull);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;

@@ -108,6 +108,19 @@ class ContextSetInfo(C.Structure):
                 ("launches", C.c_uint64), ("device_allocations", C.c_uint64), ("arena_bytes", C.c_uint64), ("build_ms", C.c_double)]
 
 
+class ContextSetSetupInfo(C.Structure):
+    """gfs_ctx_set_setup_info: the last gfs_ctx_set_setup_* of a set, counted as ContextSetInfo counts."""
+    _fields_ = [("items", C.c_uint64), ("configured", C.c_uint64), ("nothing_to_do", C.c_uint64), ("total_streams", C.c_uint64),
+                ("state_bytes", C.c_uint64), ("device_allocations", C.c_uint64), ("copies", C.c_uint64), ("launches", C.c_uint64),
+                ("setup_ms", C.c_double)]
+
+
+# GFS_STATE_*: the state arrays of a set-up context (Context.debug_sgd_state), with the dtype each reads as
+STATE_POSITIONS, STATE_COUNTERS, STATE_LEAD, STATE_TRACE, STATE_TRACE_COUNTS, STATE_RNG, STATE_ZETAS, STATE_SCHEDULE = range(8)
+STATE_KINDS, STATE_SIZE_OF = 8, 0x100
+ITER_CONSTS_DTYPE = np.dtype([("eta", "<f8"), ("zeta2theta", "<f8"), ("omt_fb", "<f8"), ("alpha_fb", "<f8"), ("omt_e", "<i4"),
+                              ("alpha_e", "<i4"), ("cooling", "<i4"), ("_pad", "<i4")])
+
 PAIR_ERROR_DTYPE = np.dtype([("step_distance", "<u8"), ("pairs", "<u8"), ("sum_rel_sq", "<f8"), ("max_rel_sq", "<f8"),
                              ("sum_abs", "<f8"), ("sum_sq", "<f8")])
 
@@ -148,6 +161,7 @@ EXPORTS = [
     "gfs_batch_upload_coords", "gfs_batch_coords", "gfs_batch_pair_errors",
     "gfs_batch_path_offsets", "gfs_batch_path_errors", "gfs_batch_stretched_pairs", "gfs_batch_node_errors", "gfs_batch_debug_tile_blocks",
     "gfs_ctx_set_plan", "gfs_ctx_set_create", "gfs_ctx_set_size", "gfs_ctx_set_item", "gfs_ctx_set_get_info", "gfs_ctx_set_destroy",
+    "gfs_ctx_set_state_plan", "gfs_ctx_set_setup_1d", "gfs_ctx_set_setup_nd", "gfs_ctx_set_get_setup_info", "gfs_ctx_debug_sgd_state",
 ]
 SEGMENT_SORT_CAP = 8192                # GFS_SEGMENT_SORT_CAP
 
@@ -263,6 +277,11 @@ def lib():
         L.gfs_ctx_set_get_info.argtypes = [C.c_void_p, C.c_void_p]
         L.gfs_ctx_set_destroy.argtypes = [C.c_void_p]
         L.gfs_ctx_set_destroy.restype = None
+        L.gfs_ctx_set_state_plan.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.gfs_ctx_set_setup_1d.argtypes = [C.c_void_p] * 4
+        L.gfs_ctx_set_setup_nd.argtypes = [C.c_void_p] * 4
+        L.gfs_ctx_set_get_setup_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.gfs_ctx_debug_sgd_state.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]
         _lib = L
     return _lib
 
@@ -724,6 +743,18 @@ class Context:
         check(lib().gfs_ctx_debug_step_records(self._h, _ptr(out), C.c_uint64(out.size)))
         return out
 
+    def debug_sgd_state(self, which):
+        """gfs_ctx_debug_sgd_state: state array `which` (STATE_*) of a set-up context as it lies on the device — float64 positions
+        (device order) and zeta table, ITER_CONSTS_DTYPE schedule table, TERM_DTYPE trace, uint64 RNG words [k * n_streams + t] and
+        counters, uint32 team state and trace counts; empty for an array the setup did not make."""
+        dtype = {STATE_POSITIONS: np.float64, STATE_ZETAS: np.float64, STATE_SCHEDULE: ITER_CONSTS_DTYPE, STATE_TRACE: TERM_DTYPE,
+                 STATE_RNG: np.uint64, STATE_COUNTERS: np.uint64, STATE_LEAD: np.uint32, STATE_TRACE_COUNTS: np.uint32}[int(which)]
+        size = C.c_uint64(0)
+        check(lib().gfs_ctx_debug_sgd_state(self._h, C.c_uint32(int(which) | STATE_SIZE_OF), C.byref(size), C.c_uint64(8)))
+        out = np.zeros(int(size.value) // np.dtype(dtype).itemsize, dtype=dtype)
+        check(lib().gfs_ctx_debug_sgd_state(self._h, C.c_uint32(int(which)), _ptr(out), C.c_uint64(out.nbytes)))
+        return out
+
     def kshift(self, set=None):
         """Crowding onset the kernels are handed (needs a set-up context).  set: an int >= 0 overrides it for every
         later launch of this context, -1 restores the policy; None leaves it as it is."""
@@ -751,6 +782,16 @@ def ctx_set_plan(n_nodes, n_steps, n_paths):
     total = C.c_uint64(0)
     check(lib().gfs_ctx_set_plan(_ptr(nn), _ptr(ns), _ptr(npth), C.c_uint64(n), _ptr(off), C.byref(total)))
     return off[:n], int(total.value)
+
+
+def ctx_set_state_plan(nbytes):
+    """gfs_ctx_set_state_plan (host only): nbytes[i][k] = bytes of item i's state array k (STATE_*).  Returns (offsets as a uint64
+    array of shape (items, 8), arena_bytes)."""
+    nb = np.ascontiguousarray(nbytes, dtype=np.uint64).reshape(-1, STATE_KINDS)
+    off = np.zeros((max(nb.shape[0], 1), STATE_KINDS), dtype=np.uint64)
+    total = C.c_uint64(0)
+    check(lib().gfs_ctx_set_state_plan(_ptr(nb), C.c_uint64(nb.shape[0]), _ptr(off), C.byref(total)))
+    return off[:nb.shape[0]], int(total.value)
 
 
 class ContextSet:
@@ -788,6 +829,37 @@ class ContextSet:
     def info(self):
         out = ContextSetInfo()
         check(lib().gfs_ctx_set_get_info(self._h, C.byref(out)))
+        return out
+
+    def _setup(self, entry, make, params, cfgs, dims_of):
+        n = len(self.contexts)
+        params = list(params) if isinstance(params, (list, tuple)) else [params] * n
+        cfgs = list(cfgs) if isinstance(cfgs, (list, tuple)) else [cfgs] * n
+        if len(params) != n or len(cfgs) != n:
+            raise ValueError("params / cfgs: one for all items or one per item")
+        made = [make(p) for p in params]
+        c_params = (type(made[0]) * n)(*made)
+        c_cfgs = None if all(c is None for c in cfgs) else (LaunchConfig * n)(*[c if c is not None else LaunchConfig() for c in cfgs])
+        rcs = np.zeros(n, dtype=np.int32)
+        check(entry(self._h, c_params, c_cfgs, _ptr(rcs)))
+        for ctx, p, c in zip(self.contexts, params, cfgs):
+            ctx.params, ctx.cfg, ctx.dims = p, c, dims_of(p)
+        return rcs.tolist()
+
+    def setup_1d(self, params, cfgs=None):
+        """gfs_ctx_set_setup_1d: every item set up as Context.setup_1d would, in one pass.  params: one PathSGDParams for all items
+        or a sequence of one per item; cfgs likewise (None: defaults).  Returns the per-item codes (OK or NOTHING_TO_DO)."""
+        return self._setup(lib().gfs_ctx_set_setup_1d, make_sgd_params, params, cfgs, lambda p: 0)
+
+    def setup_nd(self, params, cfgs=None):
+        """gfs_ctx_set_setup_nd: the same for layouts (LayoutSGDParams; the items may differ in their dimensions)."""
+        return self._setup(lib().gfs_ctx_set_setup_nd, make_layout_params, params, cfgs, lambda p: p.dimensions)
+
+    @property
+    def setup_info(self):
+        """gfs_ctx_set_setup_info of the last set setup (zeros before the first)."""
+        out = ContextSetSetupInfo()
+        check(lib().gfs_ctx_set_get_setup_info(self._h, C.byref(out)))
         return out
 
 

@@ -86,17 +86,23 @@ def _refused_item(e):
 SET_MAX_NODES = 16384          # graphs of fewer nodes are a batch's candidates under the default policy: created through one ContextSet
 
 
-def _open_set(graphs, cfgs, wanted, device):
+def _open_set(graphs, params, cfgs, wanted, device, layouts):
     """One hip.ContextSet for the graphs a batch can take — wanted(i), fewer than SET_MAX_NODES nodes, and a cfg that asks for
-    bundle 0 (auto) or 1 — so that their contexts cost one build, not one each.  Returns (the set or None, {graph index: its
-    Context}); the caller closes the set after everything made from its contexts."""
+    bundle 0 (auto) or 1 — so that their contexts cost one build, not one each, and one set setup (ContextSet.setup_1d, or
+    setup_nd for layouts), not one setup each.  Returns (the set or None, {graph index: its Context}, {graph index: what its
+    setup returned}); the caller closes the set after everything made from its contexts."""
     def bundle(c):
         return ((int(c.flags) >> 16) & 0xFF) if c is not None else 0
     idx = [i for i, g in enumerate(graphs) if wanted(i) and 0 < g.n_nodes < SET_MAX_NODES and bundle(cfgs[i]) in (0, 1)]
     if not idx:
-        return None, {}
+        return None, {}, {}
     cset = hip.ContextSet([graphs[i] for i in idx], device=device)
-    return cset, dict(zip(idx, cset.contexts))
+    try:
+        rcs = (cset.setup_nd if layouts else cset.setup_1d)([params[i] for i in idx], [cfgs[i] for i in idx])
+    except Exception:
+        cset.close()
+        raise
+    return cset, dict(zip(idx, cset.contexts)), dict(zip(idx, rcs))
 
 
 def _batch_of(held, candidates, max_blocks_per_launch):
@@ -134,7 +140,7 @@ def path_sgd_sort_batch(graphs, params, cfg=None, max_blocks_per_launch: int = 0
 
     out = [None] * len(graphs)
     held = {}                                                  # graph index -> its Context, for the batch's candidates
-    cset, made = _open_set(graphs, cfgs, lambda i: True, device)
+    cset, made, set_up = _open_set(graphs, params, cfgs, lambda i: True, device, layouts=False)
     try:
         for i, (g, p, c) in enumerate(zip(graphs, params, cfgs)):
             out[i] = dict(positions=np.zeros(0), order=np.zeros(0, dtype=np.uint64), stats=None, batched=False)
@@ -142,7 +148,7 @@ def path_sgd_sort_batch(graphs, params, cfg=None, max_blocks_per_launch: int = 0
                 continue
             ctx = made[i] if i in made else hip.Context(g, device=device)
             try:
-                rc = ctx.setup_1d(p, c)
+                rc = set_up[i] if i in set_up else ctx.setup_1d(p, c)     # (a graph that runs alone keeps the single call)
                 if rc != hip.OK:                               # nothing to do
                     out[i]["stats"] = ctx.stats()
                 elif ctx.stats().bundle == 1:                  # a candidate: initialised with the batch (or before its solo run)
@@ -195,7 +201,7 @@ def path_linear_sgd_layout_batch(graphs, params, inits=None, cfg=None, max_block
         out[i] = dict(layout=lay, stats=st, batched=False)
 
     held = {}                                                  # graph index -> its Context, for the batches' candidates
-    cset, made = _open_set(graphs, cfgs, lambda i: params[i].dimensions in (2, 3), device)
+    cset, made, set_up = _open_set(graphs, params, cfgs, lambda i: params[i].dimensions in (2, 3), device, layouts=True)
     try:
         for i, (g, p, c) in enumerate(zip(graphs, params, cfgs)):
             if g.n_nodes == 0 or p.dimensions not in (2, 3):
@@ -203,7 +209,7 @@ def path_linear_sgd_layout_batch(graphs, params, inits=None, cfg=None, max_block
                 continue
             ctx = made[i] if i in made else hip.Context(g, device=device)
             try:
-                rc = ctx.setup_nd(p, c)
+                rc = set_up[i] if i in set_up else ctx.setup_nd(p, c)     # (a graph that runs alone keeps the single call)
                 if rc == hip.OK and ctx.stats().bundle == 1:
                     held[i], ctx = ctx, None
             finally:

@@ -529,6 +529,65 @@ gfs_ctx *gfs_ctx_set_item(gfs_ctx_set *s, uint64_t i);      /* owned by the set;
 int      gfs_ctx_set_get_info(const gfs_ctx_set *s, gfs_ctx_set_info *out);
 void     gfs_ctx_set_destroy(gfs_ctx_set *s);               /* destroys every item */
 
+/* ---- set setup: every item of a context set set up in one pass ----
+ * gfs_ctx_setup_* costs five to eight allocations, two blocking memsets and three blocking copies per context, and computes a zeta
+ * table and seeds every RNG stream on the host.  gfs_ctx_set_setup_1d / _nd set up ALL items of a set in one pass: the state arrays
+ * of every item in ONE arena the set owns (laid out by gfs_ctx_set_state_plan), one memset over everything a setup zeroes, every
+ * zeta table, schedule table and the seeding kernel's tables in ONE pinned staging buffer and up in one copy, every RNG stream
+ * seeded by ONE launch (set_seed_streams_kernel) — so that allocations, copies and launches do not depend on the number of items.
+ * Items that share theta, space_max and space_quantization_step get slices of one zeta running sum.
+ * Contract: item i then holds, bit for bit, what gfs_ctx_setup_1d(item, &params[i], &cfgs[i], NULL, NULL) (or _nd) would have left:
+ * shape, plan, parameters, schedule, the RNG words, the zeta table with its zero padding, the schedule table, zeroed counters,
+ * positions, team state and trace buffers.  Every launch shape the single call accepts is accepted (team kernels, GFS_F_PHASED,
+ * tracing).  There is no caller-supplied etas / zetas variant: an item that needs its own tables is set up alone afterwards.
+ * params: n = gfs_ctx_set_size(s) of them; cfgs: n, or NULL for defaults; item_rc (nullable): n codes, GFS_OK or GFS_NOTHING_TO_DO
+ * exactly as the single call returns (an item of 0 nodes; an item with no path of more than one step, which still gets its zeroed
+ * position replica).  Returns GFS_OK when every item ended in one of the two ways.
+ * Errors: GFS_E_ARG for a null set or params.  Every item's arguments are checked (for _nd: 1..8 dimensions first) before any item
+ * is touched and before any device call; the text begins "set item <i>: " and names the lowest failing item; so does a launch
+ * shape the policy refuses, found before any item is touched as well.  A device failure after that leaves EVERY item not set up,
+ * the arena released, nothing leaked.
+ * Ownership: the arena is the set's; the items borrow from it.  A second set setup drops the items' borrows, then reuses or regrows
+ * the arena.  gfs_ctx_setup_* on one item afterwards gives that item arrays of its own, the others stay in the arena;
+ * gfs_ctx_bind_positions works as before.  gfs_ctx_set_destroy frees the arena after the items.  A gfs_batch made from the items
+ * BEFORE a second set setup reads every item's pointers anew at each gfs_batch_run, so it runs from the new arrays — or, where the
+ * new launch shape no longer fits it, is refused by its "set up again since the batch was created" check; it never reads freed
+ * memory. */
+typedef struct gfs_ctx_set_setup_info {
+    uint64_t items, configured, nothing_to_do;   /* how the items ended: GFS_OK / GFS_NOTHING_TO_DO */
+    uint64_t total_streams, state_bytes;         /* over all items; the one state arena (the seeding tables behind it included) */
+    uint64_t device_allocations, copies, launches; /* of this call, counted as gfs_ctx_set_info counts them: hipMalloc + hipHostMalloc
+                                                    calls (0 once the arena and the staging have grown), hipMemcpys, kernel launches
+                                                    and hipMemsets */
+    double   setup_ms;                           /* wall time inside the call */
+} gfs_ctx_set_setup_info;
+
+/* The state arrays of a set-up context, in the order they lie in a set's state arena. */
+#define GFS_STATE_POSITIONS    0u   /* x_len f64, device order                       */
+#define GFS_STATE_COUNTERS     1u   /* 1024 lines of 8 u64                           */
+#define GFS_STATE_LEAD         2u   /* team kernels: [8][n_streams] u32              */
+#define GFS_STATE_TRACE        3u   /* n_streams * trace_per_stream gfs_term         */
+#define GFS_STATE_TRACE_COUNTS 4u   /* n_streams u32                                 */
+#define GFS_STATE_RNG          5u   /* [4][n_streams] u64: word k of stream t at k * n_streams + t */
+#define GFS_STATE_ZETAS        6u   /* zlen_full f64                                 */
+#define GFS_STATE_SCHEDULE     7u   /* iter_max + 1 records of 48 B (IterConsts)     */
+#define GFS_STATE_KINDS        8
+#define GFS_STATE_SIZE_OF  0x100u   /* or-ed into `which`: the array's size in bytes, as one uint64_t */
+
+/* host only, no device: where item i's state arrays lie in the arena — offsets[8 * i + k] for an array of bytes[8 * i + k] bytes,
+ * k = GFS_STATE_*; by kind, then by item; every array starts 256-byte aligned, arrays of a kind are adjacent, none overlap, an
+ * array of 0 bytes takes no room; *arena_bytes is the end of the last array's room. */
+int      gfs_ctx_set_state_plan(const uint64_t *bytes /*[8*n]*/, uint64_t n, uint64_t *offsets /*[8*n]*/, uint64_t *arena_bytes);
+int      gfs_ctx_set_setup_1d(gfs_ctx_set *s, const gfs_sgd_params *params /*[n]*/,
+                              const gfs_launch_config *cfgs /*[n], NULL = defaults*/, int32_t *item_rc /*[n], nullable*/);
+int      gfs_ctx_set_setup_nd(gfs_ctx_set *s, const gfs_layout_params *params /*[n]*/,
+                              const gfs_launch_config *cfgs /*[n], NULL = defaults*/, int32_t *item_rc /*[n], nullable*/);
+int      gfs_ctx_set_get_setup_info(const gfs_ctx_set *s, gfs_ctx_set_setup_info *out);   /* of the last set setup; zeros before */
+/* test hook, in the style of gfs_ctx_debug_step_records: state array `which` (GFS_STATE_*) of a set-up context — a set's item or
+ * not — as it lies on the device; bytes must equal the array's size (0 for an array the setup did not make: nothing is written).
+ * which | GFS_STATE_SIZE_OF: that size instead, into a uint64_t (bytes must be 8).  Synchronises. */
+int      gfs_ctx_debug_sgd_state(gfs_ctx *ctx, uint32_t which, void *out, uint64_t bytes);
+
 /* ---- multi-device runs (no reference equivalent: the reference is one process, src/sgd.rs:413-593) ----
  * Paths are sharded over `world` ranks, one rank per GPU (one process per GPU, or one host thread per GPU); every rank
  * performs its share of an iteration's term updates on its own replica of the positions; after every window of
