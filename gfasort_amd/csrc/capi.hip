@@ -173,7 +173,10 @@ static hipError_t launch(const gfs_ctx *c, const void *fn, gfs::KArgs &a, const 
 
 // Resolves the plan for the shape as shape_before_residency left it, asks the runtime for the fused team kernel's residency and
 // lets shape_after_residency finish the shape (which may lower n_streams).
-static int plan_launches(int cu_count, gfs::LaunchShape &s, LaunchPlan &pl, std::string *err) {
+// Then the record width (shape_records: the crowding onset follows the final stream count) and, where the kernels have one, the
+// builds for 8-byte trip records.
+static int plan_launches(int cu_count, const gfs::RecordFacts &rec, int32_t kshift_override, uint64_t n_steps, gfs::LaunchShape &s, LaunchPlan &pl,
+                         std::string *err) {
     pl = LaunchPlan{};
     const gfs::KernelShape shape{s.dims, s.bundle, s.lds_tables, s.atomic_loads, s.trace};
     const bool team = s.team, ref = s.bundle == 1;
@@ -189,13 +192,33 @@ static int plan_launches(int cu_count, gfs::LaunchShape &s, LaunchPlan &pl, std:
                " trace=" + std::to_string(s.trace) + " phased=" + std::to_string(s.phased);
         return GFS_E_UNSUPPORTED;
     }
+    // The builds for 8-byte trip records, where this shape has them (what compact_records asks of the kernel is decided by now;
+    // what it asks of the graph waits for the final stream count).  A context may launch either width over its life
+    // (gfs_ctx_debug_kshift moves the onset), so both are resolved here, and the residency is what both can hold.
+    gfs::LaunchShape probe = s;
+    probe.flags &= ~GFS_F_FULL_RECORDS;
+    const bool has_compact = rec.have_trip_rec && gfs::compact_records(probe, gfs::RecordFacts{0, 0, 0, true}, 0);
+    const gfs::KernelShape compact{s.dims, s.bundle, s.lds_tables, s.atomic_loads, s.trace, true};
+    const void *pooled_compact = has_compact ? fused_kernel(compact, true) : nullptr;
+    const void *free_compact = has_compact && free_running ? fused_kernel(compact, false) : nullptr;
+    if (has_compact) pl.iteration_compact = iteration_kernel(compact);
+    if (has_compact && (!pl.iteration_compact || !pooled_compact || (free_running && !free_compact))) {
+        *err = "no kernel is built for 8-byte trip records in this shape"; return GFS_E_UNSUPPORTED;
+    }
     int per_cu = 0;
     if (team) {                                                            // (the measurement behind it: shape_after_residency)
         int rc = resident_blocks_per_cu(s, pooled_kernel, &per_cu, err);
         if (rc) return rc;
+        if (has_compact) {
+            int per_cu_compact = 0;
+            if ((rc = resident_blocks_per_cu(s, pooled_compact, &per_cu_compact, err))) return rc;
+            per_cu = std::min(per_cu, per_cu_compact);
+        }
     }
     gfs::shape_after_residency(per_cu, gfs::DeviceFacts{cu_count}, &s);
     if (s.fused) pl.fused = s.pooled ? pooled_kernel : free_kernel;
+    if (s.fused && has_compact) pl.fused_compact = s.pooled ? pooled_compact : free_compact;
+    gfs::shape_records(rec, kshift_override >= 0 ? kshift_override : gfs::crowd_kshift(n_steps, s.n_streams), &s);
     return GFS_OK;
 }
 
@@ -219,7 +242,7 @@ int gfs::plan_setup(const gfs_ctx *c, const gfs_sgd_params *p, int dims, const g
     const gfs::GraphFacts graph{c->n_nodes, c->n_steps, c->n_paths, c->max_path_steps, c->valid_paths, c->path_counts.data()};
     int rc = gfs::shape_before_residency(graph, gfs::DeviceFacts{c->cu_count}, p, dims, cfg, &sp.shape, err);
     if (rc) return rc;
-    rc = plan_launches(c->cu_count, sp.shape, sp.plan, err);              // (may lower n_streams)
+    rc = plan_launches(c->cu_count, c->record_facts, c->kshift_override, c->n_steps, sp.shape, sp.plan, err);   // (may lower n_streams)
     if (rc) return rc;
     // eta schedule (host, bit-exact) unless supplied
     sp.etas.resize(p->iter_max + 1);
@@ -246,6 +269,11 @@ static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs
     if (rc) return fail(rc, err);
     HIPCHK(hipSetDevice(c->device));
     gfs::free_sgd_state(c);
+    if (dims != 0 && c->d_trip_rec) {                                      // a layout context: no kernel of its reads trip records; a
+        HIPCHK(hipDeviceSynchronize());                                    // later 1D setup of it runs on step records
+        c->d_trip_rec.reset();
+        c->record_facts.have_trip_rec = false;
+    }
     gfs::SetupPlan sp;
     const int planned = gfs::plan_setup(c, p, dims, cfg, etas, &sp, &err);
     uint64_t bytes[GFS_STATE_KINDS];
@@ -446,6 +474,9 @@ void gfs::fill_kargs(const gfs_ctx *c, gfs::KArgs &a) {
     if (const char *e = std::getenv("GFS_DBG_REF_CHUNK")) { const long v = std::atol(e); if (v >= 1 && v <= 4096) a.ref_chunk = (uint32_t)v; }   // probe knob (scripts/ref_fused_probe.py)
     a.n_nodes = (uint32_t)c->n_nodes;
     a.kshift = c->kshift_override >= 0 ? c->kshift_override : gfs::crowd_kshift(c->n_steps, c->shape.n_streams);
+    // (trip_rec shares the trace's word, sgd_device.h KArgs: a compact shape has no trace — compact_records — and is a team shape
+    // at B = 64, which no batch takes: batch_eligible asks for reference streams)
+    if (c->shape.compact) a.trip_rec = c->d_trip_rec;
 }
 
 extern "C" {
@@ -485,7 +516,7 @@ int gfs_ctx_run_iteration(gfs_ctx *c, uint64_t k, void *hip_stream) {
     int rc = next_event_pair(c, ev);
     if (rc) return rc;
     HIPCHK(ev->start(st));
-    hipError_t e = launch(c, window ? c->plan.window_iteration : c->plan.iteration, a, nullptr, 0, nullptr, st);
+    hipError_t e = launch(c, window ? c->plan.window_iteration : c->shape.compact ? c->plan.iteration_compact : c->plan.iteration, a, nullptr, 0, nullptr, st);
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     HIPCHK(ev->stop(st));
     c->iterations++;
@@ -558,7 +589,7 @@ int gfs_ctx_run_range(gfs_ctx *c, const uint64_t *ks, uint64_t n, void *hip_stre
     int rc = next_event_pair(c, ev);
     if (rc) return rc;
     HIPCHK(ev->start(st));                // (the event pair brackets the kernel alone)
-    hipError_t e = launch(c, pl.fused, a, d_slice, (uint32_t)n, pool, st);
+    hipError_t e = launch(c, c->shape.compact ? pl.fused_compact : pl.fused, a, d_slice, (uint32_t)n, pool, st);
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("fused kernel launch: ") + hipGetErrorString(e));
     HIPCHK(ev->stop(st));
     c->iterations += n;
@@ -665,7 +696,11 @@ int gfs_ctx_debug_sgd_state(gfs_ctx *c, uint32_t which, void *out, uint64_t byte
 }
 int gfs_ctx_debug_kshift(gfs_ctx *c, int32_t set, int32_t *kshift_out) {
     if (!c) return fail(GFS_E_ARG, "ctx is null");
-    if (set >= -1) c->kshift_override = set;                              // (set < -1: a query only)
+    if (set >= -1) {
+        c->kshift_override = set;
+        if (c->configured && c->shape.n_streams)                           // the record width follows the onset (launch_policy.h)
+            gfs::shape_records(c->record_facts, set >= 0 ? set : gfs::crowd_kshift(c->n_steps, c->shape.n_streams), &c->shape);
+    }                                                                      // (set < -1: a query only)
     if (kshift_out) {
         if (!c->configured || !c->shape.n_streams) return fail(GFS_E_STATE, "context not set up");
         gfs::KArgs a{};
@@ -673,6 +708,11 @@ int gfs_ctx_debug_kshift(gfs_ctx *c, int32_t set, int32_t *kshift_out) {
         *kshift_out = a.kshift;
     }
     return GFS_OK;
+}
+
+uint32_t gfs_ctx_record_bytes(const gfs_ctx *c) {
+    if (!c || !c->configured || !c->shape.n_streams) return 0;
+    return c->shape.compact ? (uint32_t)sizeof(uint2) : (uint32_t)sizeof(uint4);
 }
 
 int gfs_ctx_phase_window(gfs_ctx *c, int64_t set_begin, int64_t set_end, uint64_t *begin_out, uint64_t *end_out) {

@@ -30,6 +30,9 @@ struct LaunchPlan {
     const void *iteration = nullptr;         // K1 / K1b, K2 / K2b: one iteration per launch
     const void *window_iteration = nullptr;  // GFS_F_PHASED: K1, for the iterations of the window
     const void *fused = nullptr;             // K1c / K1d / K1e / K2c / K2d: a range of iterations per launch; null: one launch per iteration
+    // the same two built for 8-byte trip records, where the shape has such a build (K1b / K1c at B = 64): launched instead of them
+    // while gfs_ctx::shape.compact holds (launch_policy.h compact_records)
+    const void *iteration_compact = nullptr, *fused_compact = nullptr;
 };
 
 struct gfs_ctx {
@@ -45,6 +48,9 @@ struct gfs_ctx {
     // its set's, and then this one stays empty — and borrow from it
     gfs::Buffer arena;                 // (declared before them: it outlives them)
     gfs::Array<uint4> d_step_rec;
+    gfs::Array<uint2> d_trip_rec;      // { slot, pos lo } per step (+ the padding record), the context's own allocation, or null: written
+                                       // by the index build where it could allocate it, kept while record_facts.max_pos < 2^32
+    gfs::RecordFacts record_facts;     // what the index build found in the step records (launch_policy.h)
     gfs::Array<uint4> d_path_rec;
     gfs::Array<uint64_t> d_path_len;
     gfs::Array<uint32_t> d_perm;        // node layout on the device (dense index -> slot)
@@ -148,6 +154,8 @@ struct Laps {
 //   staged     a set: the inputs are gathered in ONE pinned staging copy, and the error texts say "set" and name the item;
 //              else a single graph, which may be tens of GB: its arrays go up straight from the caller's, each with a blocking copy
 // laps (nullable): GFS_TIMING of the caller's entry; the stream is drained before a lap where it is on.
+// A single context also gets its 8-byte trip records and the facts of its records (gfs_ctx::d_trip_rec, record_facts) from the same
+// pass; a set's items keep full records.
 GFS_LOCAL int build_contexts(const gfs_graph_view *const *graphs, gfs_ctx *const *ctxs, uint64_t n, Buffer &arena, const uint32_t *node_perm,
                              bool staged, Laps *laps, gfs_ctx_set_info *info);
 }  // namespace gfs

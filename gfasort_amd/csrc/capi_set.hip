@@ -112,10 +112,19 @@ int gfs::build_contexts(const gfs_graph_view *const *graphs, gfs_ctx *const *ctx
     u.items = reinterpret_cast<const gfs::SetItem *>(d_in + in.at_items);
     u.step_is_rev = d_in + in.at_rev;
     u.arena = d_arena;
+    // A single context: 8-byte trip records beside the step records, written by the same pass (sgd_1d.h TripRec), and the facts that
+    // say whether its trips may read them (launch_policy.h compact_records).  Its launch shape is not known before its setup, so the
+    // array is made here for every graph with steps and given back at once where a position does not fit its 32 bits or a node
+    // repeats within 64 steps (b > 0), and by a layout's setup (capi.hip setup_common); an allocation that fails is no error: the
+    // context keeps full records.
+    gfs_ctx *single = staged || n != 1 ? nullptr : ctxs[0];
+    if (single && S && single->d_trip_rec.grow((S + 1) * sizeof(uint2)) != hipSuccess) (void)hipGetLastError();
+    u.trip = single ? (uint2 *)single->d_trip_rec : nullptr;
     uint32_t bad_item = gfs::SET_NO_BAD_ITEM;
     e = gfs::index_set_layout_device(u, d_in + in.bytes, node_perm != nullptr, &bad_item, &info->launches);
     lap("node layout");
-    if (e == hipSuccess && bad_item == gfs::SET_NO_BAD_ITEM) e = gfs::index_set_records_device(u, d_in + in.bytes, &info->launches);
+    if (e == hipSuccess && bad_item == gfs::SET_NO_BAD_ITEM)
+        e = gfs::index_set_records_device(u, d_in + in.bytes, &info->launches, single ? &single->record_facts : nullptr);
     if (e != hipSuccess || bad_item != gfs::SET_NO_BAD_ITEM) (void)hipDeviceSynchronize();   // (nothing in flight when the buffers go)
     if (e != hipSuccess) return fail(GFS_E_HIP, std::string("build_index_set: ") + hipGetErrorString(e));
     if (bad_item != gfs::SET_NO_BAD_ITEM) return fail(GFS_E_ARG, (staged ? item_prefix(bad_item) : "") + "step_node out of range");
@@ -128,6 +137,11 @@ int gfs::build_contexts(const gfs_graph_view *const *graphs, gfs_ctx *const *ctx
     }
     if ((e = hipDeviceSynchronize()) != hipSuccess) return fail(GFS_E_HIP, std::string("hipDeviceSynchronize: ") + hipGetErrorString(e));
     lap("K3");
+    if (single) {
+        // no onset makes such a graph eligible (launch_policy.h compact_records): a position past 32 bits, a tandem repeat
+        if (single->record_facts.max_pos >= (1ull << 32) || single->record_facts.max_b > 0) single->d_trip_rec.reset();
+        single->record_facts.have_trip_rec = single->d_trip_rec != nullptr;
+    }
     for (uint64_t i = 0; i < n; ++i) {
         gfs_ctx *c = ctxs[i];
         const uint64_t *at = &offsets[KINDS * i];

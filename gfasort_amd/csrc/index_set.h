@@ -3,6 +3,7 @@
 // begins in the union and where its five index arrays lie in the set's arena.  Nothing here is exported from the shared object.
 #pragma once
 #include "index_set_plan.h"
+#include "launch_policy.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -25,6 +26,7 @@ struct SetUnion {
     const uint8_t *step_is_rev;                  // [n_steps]
     const uint64_t *path_first;                  // [n_paths + 1]
     unsigned char *arena;                        // zeroed; every item's node lengths already in place
+    uint2 *trip;                                 // a union of ONE item: its 8-byte trip records, [n_steps + 1]; else null
 };
 
 constexpr uint32_t SET_NO_BAD_ITEM = 0xFFFFFFFFu;
@@ -39,8 +41,10 @@ hipError_t index_set_work_bytes(uint64_t n_nodes, uint64_t n_steps, uint64_t *by
 // layout_given: the perm ranges already hold the caller's layout; only the range check runs.
 hipError_t index_set_layout_device(const SetUnion &u, void *d_work, bool layout_given, uint32_t *bad_item, uint64_t *launches);
 // K3 half, after the layouts are in place: every item's step records (padding record included), path records and path lengths.
-// The arena is complete once the stream has drained.
-hipError_t index_set_records_device(const SetUnion &u, void *d_work, uint64_t *launches);
+// The arena is complete once the stream has drained.  Where u.trip is set the pass that writes the step records writes
+// trip[s] = { slot, pos lo } beside them.  facts (nullable): the largest position and crowding exponents of the records, reduced in
+// that same pass and read back with one blocking copy (have_trip_rec is left to the caller).
+hipError_t index_set_records_device(const SetUnion &u, void *d_work, uint64_t *launches, RecordFacts *facts = nullptr);
 hipError_t warm_module_index_set();
 
 }  // namespace gfs

@@ -184,9 +184,11 @@ __global__ void set_node_stats_kernel(SetUnion u, uint32_t *cnt, uint32_t *rep) 
     }
 }
 // rec[s] = { internal node slot | NO_NODE, path | rev<<31, pos lo, pos hi (23 bits) | a<<23 | b<<29 } with pos = scan[s] -
-// scan[first(path)], the slot and the path id the item's own, into the item's array
-__global__ void set_fill_records_kernel(SetUnion u, const uint64_t *scan, const uint32_t *cnt, const uint32_t *rep) {
+// scan[first(path)], the slot and the path id the item's own, into the item's array.  u.trip (a union of one item): trip[s] =
+// { rec.x, rec.z } as well.  facts (nullable): [0] = the largest pos, [1] / [2] = the largest a / b written, one atomic each per wave.
+__global__ void set_fill_records_kernel(SetUnion u, const uint64_t *scan, const uint32_t *cnt, const uint32_t *rep, unsigned long long *facts) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    unsigned long long max_pos = 0, max_a = 0, max_b = 0;
     for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < u.n_steps; s += stride) {
         const uint32_t p = path_of(u.path_first, (uint32_t)u.n_paths, s);
         const SetItem it = u.items[item_of(u.items, u.n_items, s, &SetItem::step_off)];   // (= the item of path p)
@@ -198,10 +200,24 @@ __global__ void set_fill_records_kernel(SetUnion u, const uint64_t *scan, const 
         if (n != NO_NODE_U32) {
             const uint32_t a = set_ceil_log2(cnt[it.node_off + n]), b = set_ceil_log2(rep[it.node_off + n]);
             crowd = ((a > 63u ? 63u : a) << 23) | ((b > 7u ? 7u : b) << 29);
+            if (a > max_a) max_a = a;
+            if (b > max_b) max_b = b;
         }
+        if (pos > max_pos) max_pos = pos;
         r.y = (uint32_t)(p - it.path_off) | ((uint32_t)(u.step_is_rev[s] & 1) << 31);
         r.z = (uint32_t)pos; r.w = ((uint32_t)(pos >> 32) & 0x7FFFFFu) | crowd;
         reinterpret_cast<uint4 *>(u.arena + it.rec)[s - it.step_off] = r;
+        if (u.trip) u.trip[s] = make_uint2(r.x, r.z);                      // (one item: s is its own step)
+    }
+    if (!facts) return;
+    for (int off = 32; off > 0; off >>= 1) {                               // (every lane arrives here: SET_BLOCK is whole waves)
+        const unsigned long long p = __shfl_xor(max_pos, off, 64), a = __shfl_xor(max_a, off, 64), b = __shfl_xor(max_b, off, 64);
+        max_pos = p > max_pos ? p : max_pos; max_a = a > max_a ? a : max_a; max_b = b > max_b ? b : max_b;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (max_pos) atomicMax(&facts[0], max_pos);
+        if (max_a) atomicMax(&facts[1], max_a);
+        if (max_b) atomicMax(&facts[2], max_b);
     }
 }
 // t < n_paths: path t's record { first step lo, steps, 2^32 mod steps, first step hi } in its item's numbering and its length in
@@ -212,6 +228,7 @@ __global__ void set_paths_kernel(SetUnion u, const uint64_t *scan) {
         if (t >= u.n_paths) {
             const uint32_t i = (uint32_t)(t - u.n_paths);
             reinterpret_cast<uint4 *>(u.arena + u.items[i].rec)[u.items[i + 1].step_off - u.items[i].step_off] = make_uint4(0, 0, 0, 0);
+            if (u.trip) u.trip[u.n_steps] = make_uint2(0, 0);
             continue;
         }
         const SetItem it = u.items[item_of(u.items, u.n_items, t, &SetItem::path_off)];
@@ -230,6 +247,7 @@ struct Work {
     uint32_t *ids_a, *ids_b, *a, *b, *cnt, *rep;
     uint64_t *scan;
     uint32_t *flags;                                                       // [0]: lowest bad item; [1 + round]: a fixpoint round changed something
+    unsigned long long *facts;                                             // [3]: largest position, a and b of the records (set_fill_records_kernel)
     void *tmp;
     size_t tmp_bytes;
     uint64_t cnt_rep_bytes, bytes;                                         // (cnt and rep are adjacent: one memset zeroes both)
@@ -257,6 +275,7 @@ hipError_t plan_work(uint64_t N, uint64_t S, void *d_work, Work &w) {
     w.cnt_rep_bytes = round256(N ? N * 4 : 1) + N * 4;
     take(w.scan, S ? (S + 1) * 8 : 0);
     take(w.flags, (1 + 2 * JUMP_ROUNDS) * sizeof(uint32_t));
+    take(w.facts, 3 * sizeof(unsigned long long));
     w.tmp_bytes = std::max(sort_tmp, scan_tmp);
     take(w.tmp, w.tmp_bytes);
     w.bytes = at;
@@ -335,7 +354,7 @@ hipError_t index_set_layout_device(const SetUnion &u, void *d_work, bool layout_
     return hipGetLastError();
 }
 
-hipError_t index_set_records_device(const SetUnion &u, void *d_work, uint64_t *launches) {
+hipError_t index_set_records_device(const SetUnion &u, void *d_work, uint64_t *launches, RecordFacts *facts) {
     const uint64_t N = u.n_nodes, S = u.n_steps;
     Work w{};
     hipError_t e = plan_work(N, S, d_work, w);
@@ -346,11 +365,20 @@ hipError_t index_set_records_device(const SetUnion &u, void *d_work, uint64_t *l
         if (e != hipSuccess) return e;
         if ((e = hipMemsetAsync(w.cnt, 0, w.cnt_rep_bytes, 0)) != hipSuccess) return e;
         hipLaunchKernelGGL(set_node_stats_kernel, over_steps, block, 0, 0, u, w.cnt, w.rep);
-        hipLaunchKernelGGL(set_fill_records_kernel, over_steps, block, 0, 0, u, w.scan, w.cnt, w.rep);
+        if (facts) {
+            if ((e = hipMemsetAsync(w.facts, 0, 3 * sizeof(unsigned long long), 0)) != hipSuccess) return e;
+            ++*launches;
+        }
+        hipLaunchKernelGGL(set_fill_records_kernel, over_steps, block, 0, 0, u, w.scan, w.cnt, w.rep, facts ? w.facts : (unsigned long long *)nullptr);
         *launches += 4;
     }
     hipLaunchKernelGGL(set_paths_kernel, dim3(SET_PATH_BLOCKS), block, 0, 0, u, S ? w.scan : (const uint64_t *)nullptr);
     ++*launches;
+    if (facts) {
+        unsigned long long h[3] = {0, 0, 0};
+        if (S && (e = hipMemcpy(h, w.facts, sizeof h, hipMemcpyDeviceToHost)) != hipSuccess) return e;
+        facts->max_pos = h[0]; facts->max_a = (uint32_t)h[1]; facts->max_b = (uint32_t)h[2];
+    }
     return hipGetLastError();
 }
 

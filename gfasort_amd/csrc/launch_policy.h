@@ -52,6 +52,15 @@ struct LaunchShape {
     bool fuse_one = false;             // a range of ONE iteration is a fused launch too, in chunks of one_chunk
     bool fuse_one_probe = false;       // ... or would be if GFS_DBG_ONE_CHUNK asked for it
     uint32_t one_chunk = 0;
+    // decided by shape_records
+    bool compact = false;              // the trips of K1b / K1c at B = 64 read the 8-byte trip records instead of the step records
+};
+
+// What the index build found in the step records it wrote (index_set_kernels.hip), and whether the 8-byte array stands beside them.
+struct RecordFacts {
+    uint64_t max_pos = 0;              // largest bp position of a step
+    uint32_t max_a = 0, max_b = 0;     // largest crowding exponents of a step's node (sgd_device.h crowd_shift)
+    bool have_trip_rec = false;        // trip_rec[s] = { slot, pos lo } was written and is still allocated
 };
 
 // "This context has a fused team kernel": K1c (K1e where phased) at the sort's widest bundles, K2c for layouts of 2 and more
@@ -283,6 +292,19 @@ inline int32_t crowd_kshift(uint64_t n_steps, uint64_t n_streams) {
     int lg = 0; while (lg < 63 && (per >> (lg + 1)) != 0) ++lg;            // floor(log2(max(per, 1)))
     return lg + 2;
 }
+
+// Record width of the trips (sgd_1d.h TripRec): 8-byte trip records where a trip reads nothing of the other 8 bytes of a step
+// record.  A trip reads the slot, the position and the crowding exponents.  The high position word is zero on every step iff the
+// largest position is below 2^32.  crowd_shift<true> is max(0, a_i - kshift, a_j - kshift, b_i, b_j) over a term's two records:
+// zero for EVERY pair iff max_a <= kshift and max_b == 0.  The kernels that have a compact build are K1b and K1c at B = 64
+// without a trace (K1e, the phased sampler, keeps full records); GFS_F_FULL_RECORDS forces full records.
+inline bool compact_records(const LaunchShape &s, const RecordFacts &r, int32_t kshift) {
+    const bool kernel = s.dims == 0 && s.bundle == 64 && !s.trace && !s.phased;
+    const bool graph = r.have_trip_rec && r.max_pos < (1ull << 32) && (int64_t)r.max_a <= (int64_t)kshift && r.max_b == 0;
+    return kernel && graph && !(s.flags & GFS_F_FULL_RECORDS);
+}
+// (after shape_after_residency: kshift follows the final stream count)
+inline void shape_records(const RecordFacts &r, int32_t kshift, LaunchShape *shape) { shape->compact = compact_records(*shape, r, kshift); }
 
 // the step index is drawn with 64-bit arithmetic (sgd_device.h sample_step)
 inline bool wide_index(uint64_t n_steps, uint32_t flags) { return n_steps > 0xFFFFFFFFull || (flags & GFS_F_DBG_WIDE_INDEX); }

@@ -99,11 +99,33 @@ struct TeamState {
     uint32_t done = 0, att = 0, ntr = 0;
 };
 
+// The record of a step as a trip reads it: the slot, the bp position, the crowding exponents — of the 16-byte step record, or
+// (COMPACT) of the 8-byte trip record { slot, pos lo } that the index build writes beside it.  The host picks COMPACT only where
+// every step's high position word and every term's crowding shift are zero (launch_policy.h compact_records): then the two
+// widths give the same values bit for bit, from half the record bytes and half the registers (a Trip holds three records).
+// The sampler (sample_leader, draw_partner) needs the path of its step and stays on step records.
+template <bool COMPACT> struct TripRec;
+template <> struct TripRec<false> {
+    uint4 r = make_uint4(0, 0, 0, 0);
+    static __device__ __forceinline__ TripRec load(const KArgs &a, uint64_t s) { TripRec t; t.r = a.step_rec[s]; return t; }
+    __device__ __forceinline__ uint32_t slot() const { return r.x; }
+    __device__ __forceinline__ double pos() const { return rec_pos(r); }
+    static __device__ __forceinline__ int crowd(const KArgs &a, const TripRec &ra, const TripRec &rb) { return crowd_shift<true>(a, ra.r, rb.r); }
+};
+template <> struct TripRec<true> {
+    uint2 r = make_uint2(0, 0);
+    static __device__ __forceinline__ TripRec load(const KArgs &a, uint64_t s) { TripRec t; t.r = a.trip_rec[s]; return t; }
+    __device__ __forceinline__ uint32_t slot() const { return r.x; }
+    __device__ __forceinline__ double pos() const { return (double)r.y; }
+    static __device__ __forceinline__ int crowd(const KArgs &, const TripRec &, const TripRec &) { return 0; }
+};
+
 // One trip = (slot t of the pass, trip seg of its run, partner, colour): what every lane needs to execute it.
+template <bool COMPACT>
 struct Trip {
     uint64_t sa = 0, sb = 0;
-    uint4 ra = make_uint4(0, 0, 0, 0), rb = make_uint4(0, 0, 0, 0);
-    uint4 rc = make_uint4(0, 0, 0, 0);   // twin trip: the record of the second partner's step
+    TripRec<COMPACT> ra, rb;
+    TripRec<COMPACT> rc;       // twin trip: the record of the second partner's step
     bool twin = false;         // wave-uniform: both partners of an aligned leader in ONE trip (twin_trip)
     bool valid = false;        // this lane acts in the trip (fused trip: this lane's partner lies beyond the trip's 64 steps)
     int mshift = 0;            // != 0: merged short-jump trip (sgd_kernel_common.h merged_trip_shift)
@@ -113,8 +135,9 @@ struct Trip {
     uint32_t off = 0;          // wave-uniform: this trip starts `off` steps after the run's first step (run_offset)
 };
 
-template <int B>
-__device__ __forceinline__ void expand_trip(const KArgs &a, const Leader &L, int t, uint32_t seg, uint32_t p, uint32_t colour, int sub, int q, Trip &tr) {
+template <int B, bool COMPACT>
+__device__ __forceinline__ void expand_trip(const KArgs &a, const Leader &L, int t, uint32_t seg, uint32_t p, uint32_t colour, int sub, int q, Trip<COMPACT> &tr) {
+    using Rec = TripRec<COMPACT>;
     constexpr int RUNS = 64 / B;
     const int ll = t * RUNS + q;
     const uint32_t okw = bcast<B>(L.ok, ll), cnt = bcast<B>(L.cnt, ll);
@@ -128,7 +151,7 @@ __device__ __forceinline__ void expand_trip(const KArgs &a, const Leader &L, int
     tr.mshift = merged_trip_shift<B>(ok, cnt, ra0, rb0, tr.off);
     const bool two = !(a.dbg & 0x08u) && two_colour<B>(ok, cnt, ra0, rb0);
     tr.two = B == 64 ? two : (__any(two) != 0);                       // B = 64: the leader is wave-uniform already
-    tr.ra = make_uint4(0, 0, 0, 0); tr.rb = make_uint4(0, 0, 0, 0); tr.rc = make_uint4(0, 0, 0, 0);
+    tr.ra = Rec(); tr.rb = Rec(); tr.rc = Rec();
     tr.fused = B == 64 && tr.mshift != 0 && colour == 0 && two && !(a.dbg & 0x100u);
     // both partners line-aligned long jumps: their a-runs are the same blocks (draw_partner), one trip serves both
     tr.twin = B == 64 && p == 0u && a.partners == 2u && (okw & 3u) == 3u && ((okw >> 8) & 3u) == 3u && !(a.dbg & 0x04u);
@@ -147,7 +170,7 @@ __device__ __forceinline__ void expand_trip(const KArgs &a, const Leader &L, int
         tr.sb = first + rb0 + tr.off + (((uint32_t)sub + ((okw >> 2) & 7u)) & 63u);
         const uint64_t sc = first + rb1 + tr.off + (((uint32_t)sub + ((okw >> 10) & 7u)) & 63u);
         tr.valid = true;
-        tr.ra = a.step_rec[tr.sa]; tr.rb = a.step_rec[tr.sb]; tr.rc = a.step_rec[sc];
+        tr.ra = Rec::load(a, tr.sa); tr.rb = Rec::load(a, tr.sb); tr.rc = Rec::load(a, sc);
         return;
     }
     if (tr.fused) {
@@ -157,12 +180,12 @@ __device__ __forceinline__ void expand_trip(const KArgs &a, const Leader &L, int
         tr.sa = first + merged_trip_base(cnt, ra0, tr.off) + (uint32_t)sub;
         tr.sb = (uint64_t)((int64_t)tr.sa + tr.mshift);
         tr.valid = dst < 0 || dst > 63;
-        tr.ra = a.step_rec[tr.sa];
-        tr.rb = a.step_rec[tr.sb];
+        tr.ra = Rec::load(a, tr.sa);
+        tr.rb = Rec::load(a, tr.sb);
         return;
     }
     tr.valid = expand_run<B>(ok, first, cnt, ra0, rb0, sub, colour, tr.off, tr.sa, tr.sb);
-    if (tr.valid) { tr.ra = a.step_rec[tr.sa]; tr.rb = a.step_rec[tr.sb]; }
+    if (tr.valid) { tr.ra = Rec::load(a, tr.sa); tr.rb = Rec::load(a, tr.sb); }
 }
 
 // The term arithmetic of sgd.rs:518-571 on values already in registers; returns r_x.
@@ -193,8 +216,8 @@ __device__ __forceinline__ double shfl_f64(double v, int src) { return __shfl(v,
 // and a fused trip now costs 8 requests for 64 updates where two trips cost 16 (C3 80.0 -> 87.4 G updates/s, bubble
 // graphs 49.9 -> 53.6 and 52.0 -> 55.8: profiles/r02/fused_trip_one_add.log).  Returns false when the wave's quota filled
 // before the second colour: the caller leaves that colour to the next iteration as a generic trip.
-template <bool ATOMIC_LOADS, bool TRACE>
-__device__ __forceinline__ bool fused_trip(const KArgs &a, TeamState &ts, const Trip &cur, const int lane,
+template <bool ATOMIC_LOADS, bool TRACE, bool COMPACT>
+__device__ __forceinline__ bool fused_trip(const KArgs &a, TeamState &ts, const Trip<COMPACT> &cur, const int lane,
                                            const uint32_t tid, const uint64_t wave_quota, uint64_t &wave_done) {
     double *x = a.x;
     const int s = cur.mshift, z = s < 0 ? -s : s;
@@ -202,14 +225,14 @@ __device__ __forceinline__ bool fused_trip(const KArgs &a, TeamState &ts, const 
     const bool out = cur.valid;                                        // partner beyond the trip's 64 steps
     const int dstc = out ? lane : dst, srcc = (src < 0 || src > 63) ? lane : src;
     const uint32_t grp = ((cur.off + (uint32_t)lane) / (uint32_t)z) & 1u;
-    const uint32_t node = cur.ra.x, pnode = cur.rb.x;
+    const uint32_t node = cur.ra.slot(), pnode = cur.rb.slot();
     double xo = 0.0, xp = 0.0;                                         // my position; my partner's when it is beyond the trip
     if (!(a.dbg & 2u)) {
         if (node != 0xFFFFFFFFu) xo = load_pos<ATOMIC_LOADS>(x + node);
         if (out && pnode != 0xFFFFFFFFu) xp = load_pos<ATOMIC_LOADS>(x + pnode);       // (partners inside: from their lanes)
     } else { xo = (double)node; xp = (double)pnode; }
-    const double term_dist = fabs(rec_pos(cur.ra) - rec_pos(cur.rb));                  // sgd.rs:513
-    const int crowd = crowd_shift<true>(a, cur.ra, cur.rb);
+    const double term_dist = fabs(cur.ra.pos() - cur.rb.pos());                        // sgd.rs:513
+    const int crowd = TripRec<COMPACT>::crowd(a, cur.ra, cur.rb);
     const bool term_ok = term_dist != 0.0 && node != 0xFFFFFFFFu && pnode != 0xFFFFFFFFu;   // :514, :525-538
     double acc = 0.0;
     bool touched = false, second = true;
@@ -251,30 +274,30 @@ __device__ __forceinline__ bool fused_trip(const KArgs &a, TeamState &ts, const 
 // both; the second term computes on what the first left in the register, as it would read it back from memory; a's node
 // takes ONE add, -(r + r'), b and c one each: 3 blocks of 8 requests for 128 updates where two trips take 4.  Returns false
 // when the wave's quota filled before the second term: the caller leaves the second partner's trip to the next iteration.
-template <bool ATOMIC_LOADS, bool TRACE>
-__device__ __forceinline__ bool twin_trip(const KArgs &a, TeamState &ts, const Trip &cur, const int lane,
+template <bool ATOMIC_LOADS, bool TRACE, bool COMPACT>
+__device__ __forceinline__ bool twin_trip(const KArgs &a, TeamState &ts, const Trip<COMPACT> &cur, const int lane,
                                           const uint32_t tid, const uint64_t wave_quota, uint64_t &wave_done) {
     double *x = a.x;
-    const uint32_t node = cur.ra.x, nb = cur.rb.x, nc = cur.rc.x;
+    const uint32_t node = cur.ra.slot(), nb = cur.rb.slot(), nc = cur.rc.slot();
     double xa = 0.0, xb = 0.0, xc = 0.0;
     if (!(a.dbg & 2u)) {
         if (node != 0xFFFFFFFFu) xa = load_pos<ATOMIC_LOADS>(x + node);
         if (nb != 0xFFFFFFFFu) xb = load_pos<ATOMIC_LOADS>(x + nb);
         if (nc != 0xFFFFFFFFu) xc = load_pos<ATOMIC_LOADS>(x + nc);
     } else { xa = (double)node; xb = (double)nb; xc = (double)nc; }
-    const double pa = rec_pos(cur.ra);
+    const double pa = cur.ra.pos();
     double acc = 0.0;
     bool touched = false, second = true;
 #pragma unroll
     for (uint32_t p = 0; p < 2u; ++p) {
         ++ts.att;
-        const uint4 &rp = p ? cur.rc : cur.rb;
+        const TripRec<COMPACT> &rp = p ? cur.rc : cur.rb;
         const uint32_t pn = p ? nc : nb;
-        const double term_dist = fabs(pa - rec_pos(rp));                               // sgd.rs:513
+        const double term_dist = fabs(pa - rp.pos());                                  // sgd.rs:513
         const bool valid = quota_cut(term_dist != 0.0 && node != 0xFFFFFFFFu && pn != 0xFFFFFFFFu,   // :514, :525-538
                                      lane, wave_quota, wave_done);
         if (valid) {
-            const double r_x = term_move(a, term_dist, xa, p ? xc : xb, crowd_shift<true>(a, cur.ra, rp));   // :518-571
+            const double r_x = term_move(a, term_dist, xa, p ? xc : xb, TripRec<COMPACT>::crowd(a, cur.ra, rp));   // :518-571
             ++ts.done;                                                                 // :579
             if (TRACE) record_trace(a, tid, ts.ntr, node, pn, term_dist);
             xa = xa - r_x;                                                             // :575
@@ -288,9 +311,11 @@ __device__ __forceinline__ bool twin_trip(const KArgs &a, TeamState &ts, const T
 }
 
 // One SGD iteration of one wave: passes and trips until the wave's quota is filled.
-template <int B, bool LDS_TABLES, bool ATOMIC_LOADS, bool TRACE>
+// (COMPACT: the trips read 8-byte trip records, TripRec; B = 64 only)
+template <int B, bool LDS_TABLES, bool ATOMIC_LOADS, bool TRACE, bool COMPACT = false>
 __device__ __forceinline__ void team_iteration(const KArgs &a, const uint4 *path_tab, const double *zeta_tab,
                                                TeamState &ts, const uint32_t tid, const uint64_t wave_quota, const IterConsts *itp = nullptr) {
+    static_assert(B == 64 || !COMPACT, "trip records are read by the trips of B = 64 only");
     const int lane = threadIdx.x & 63;
     const int sub = lane & (B - 1);
     const int q = lane / B;
@@ -315,7 +340,7 @@ __device__ __forceinline__ void team_iteration(const KArgs &a, const uint4 *path
         const Leader &L = ts.L;
         int t = B - (int)ts.left;
         uint32_t colour = ts.colour, seg = ts.seg, p = ts.p;
-        Trip cur;
+        Trip<COMPACT> cur;
         expand_trip<B>(a, L, t, seg, p, colour, sub, q, cur);          // expand and request the records of the first trip
         for (;;) {
             // the trip after this one: this trip's second colour (unless fused into it), else the same trip of the run for
@@ -327,7 +352,7 @@ __device__ __forceinline__ void team_iteration(const KArgs &a, const uint4 *path
             else if (seg + 1u < cur.k) { seg_n = seg + 1u; p_n = 0u; }
             else { t_n = t + 1; seg_n = 0u; p_n = 0u; }
             const bool have_n = t_n < B;
-            Trip nxt;
+            Trip<COMPACT> nxt;
             if (have_n) expand_trip<B>(a, L, t_n, seg_n, p_n, colour_n, sub, q, nxt);
             if (B == 64 && cur.twin) {
                 if (!twin_trip<ATOMIC_LOADS, TRACE>(a, ts, cur, lane, tid, wave_quota, wave_done)) {
@@ -356,13 +381,13 @@ __device__ __forceinline__ void team_iteration(const KArgs &a, const uint4 *path
             ts.colour = colour_n; ts.seg = seg_n; ts.p = p_n;
             if (t_n != t) --ts.left;
             bool valid = cur.valid;
-            const uint4 ra = cur.ra, rb = cur.rb;
+            const TripRec<COMPACT> ra = cur.ra, rb = cur.rb;
             const int mshift = cur.mshift;
             double term_dist = 0.0;
             uint32_t i = 0, j = 0;
             if (valid) {
-                term_dist = fabs(rec_pos(ra) - rec_pos(rb));                           // sgd.rs:513
-                i = ra.x; j = rb.x;
+                term_dist = fabs(ra.pos() - rb.pos());                                 // sgd.rs:513
+                i = ra.slot(); j = rb.slot();
                 valid = term_dist != 0.0 && i != 0xFFFFFFFFu && j != 0xFFFFFFFFu;      // :514, :525-538
             }
             valid = quota_cut(valid, lane, wave_quota, wave_done);
@@ -373,7 +398,7 @@ __device__ __forceinline__ void team_iteration(const KArgs &a, const uint4 *path
             }
             double r_x = 0.0;
             if (valid) {
-                r_x = term_move(a, term_dist, xi, xj, crowd_shift<true>(a, ra, rb));   // :518-571
+                r_x = term_move(a, term_dist, xi, xj, TripRec<COMPACT>::crowd(a, ra, rb));   // :518-571
                 ++ts.done;                                                             // :579
                 if (TRACE) record_trace(a, tid, ts.ntr, i, j, term_dist);
             }

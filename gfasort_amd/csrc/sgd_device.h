@@ -84,7 +84,11 @@ struct KArgs {
     double         *x;             // 1D: x[slot]; nD: planes coords[end][dim][slot] (see coord_ptr)
     uint64_t       *rng;           // [4][n_streams] SoA
     unsigned long long *counters;  // [slots][8]: [s][0] successful updates, [s][1] attempts (sgd_kernel_common.h)
-    void           *trace;         // gfs_term[n_streams*trace_per_stream] or null
+    union {                        // (one word: KArgs — which every kernel takes by value and the team samplers re-read whole —
+                                   // keeps its size, and every other kernel its build.  Written by fill_kargs alone.)
+        void       *trace;         // gfs_term[n_streams*trace_per_stream] or null
+        const uint2 *trip_rec;     // COMPACT builds of K1b / K1c, which keep no trace: { step_rec.x, step_rec.z } per step, what
+    };                             // their trips read (sgd_1d.h TripRec)
     uint32_t       *trace_cnt;     // [n_streams]
     uint32_t       *lead;          // [8][n_streams] SoA: leaders a 1D team wave has sampled but not yet expanded
                                    // (first lo, first hi, cnt, ra0, rb0, ok | trips left << 8 | ..., ra1, rb1:

@@ -11,7 +11,8 @@
 namespace gfs {
 
 // What picks a kernel: dims 0 = the 1D sort, 1..8 = layouts; bundle 0 / 1 = reference streams, 4..64 = team kernels.
-struct KernelShape { int dims; uint32_t bundle; bool lds_tables, atomic_loads, trace; };
+// compact: the build of K1b / K1c at B = 64 whose trips read 8-byte trip records (sgd_1d.h TripRec); no other kernel has one.
+struct KernelShape { int dims; uint32_t bundle; bool lds_tables, atomic_loads, trace; bool compact = false; };
 
 template <typename... A> inline const void *kernel_addr(void (*k)(A...)) { return reinterpret_cast<const void *>(k); }
 // a run-time flag as a template argument: f(std::true_type{}) or f(std::false_type{})

@@ -54,7 +54,8 @@ __global__ void sgd1d_fused_kernel(const KArgs a0, const IterConsts *its, const 
 // (4 waves per SIMD = 128 VGPRs: a twin trip keeps three blocks in flight and the next trip's records are on their way; built
 // for 5 waves — 96 VGPRs — the kernel spills 58 registers and is slower: 88.5 against 91.5 G updates/s on C3 with round 1's
 // launch, profiles/r02/two_partners.log.  Before the twin trips a fifth wave was worth +3 %.)
-template <int B, bool LDS_TABLES, bool ATOMIC_LOADS, bool TRACE>
+// (COMPACT, here and in K1c: the trips read the 8-byte trip records — sgd_1d.h TripRec; B = 64 without a trace)
+template <int B, bool LDS_TABLES, bool ATOMIC_LOADS, bool TRACE, bool COMPACT = false>
 __global__ void __attribute__((amdgpu_waves_per_eu(4, 4))) sgd1d_team_kernel(const KArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const uint4 *path_tab; const double *zeta_tab;
@@ -68,7 +69,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 4))) sgd1d_team_kernel(con
     load_pass(a, tid, ts, no_flips);
     const uint64_t wq = wave_quota_of(a, tid & ~63u);                 // worked through in chunks, like a pool (K1c)
     for (uint64_t done = 0; done < wq; done += a.chunk)
-        team_iteration<B, LDS_TABLES, ATOMIC_LOADS, TRACE>(a, path_tab, zeta_tab, ts, tid, wq - done < a.chunk ? wq - done : a.chunk);
+        team_iteration<B, LDS_TABLES, ATOMIC_LOADS, TRACE, COMPACT>(a, path_tab, zeta_tab, ts, tid, wq - done < a.chunk ? wq - done : a.chunk);
     store_rng(a, tid, ts.rng);
     if (TRACE) a.trace_cnt[tid] = ts.ntr;
     store_pass(a, tid, ts, 0u);
@@ -81,7 +82,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 4))) sgd1d_team_kernel(con
 // (POOL is a template parameter so that each build holds ONE inlined copy of the trip machine: with both launch modes in one
 // kernel the pooled path spilled 65 VGPRs into 188 B of scratch per lane — and a first dispatch that needs more scratch than any
 // kernel before it makes the runtime re-size the queue's scratch, the ~0.12 ms "first-dispatch latency" of profiles/r02/launch_gap.log.)
-template <int B, bool LDS_TABLES, bool POOL>
+template <int B, bool LDS_TABLES, bool POOL, bool COMPACT = false>
 __global__ void __attribute__((amdgpu_waves_per_eu(4, 4))) sgd1d_team_fused_kernel(const KArgs a0, const IterConsts *its, const uint32_t n_iters,
                                                                                    uint32_t *pool) {
     constexpr bool ATOMIC_LOADS = true;
@@ -99,7 +100,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 4))) sgd1d_team_fused_kern
         const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));   // (scalar registers)
         pool_walk(a, its, n_iters, pool, pool_share(a0, wave, a0.n_streams >> 6), [&]() __attribute__((always_inline)) { return a0.chunk; },
                   [&](const uint32_t k, const uint32_t m) __attribute__((always_inline)) {
-            team_iteration<B, LDS_TABLES, ATOMIC_LOADS, false>(a, path_tab, zeta_tab, ts, tid, m, its + k);
+            team_iteration<B, LDS_TABLES, ATOMIC_LOADS, false, COMPACT>(a, path_tab, zeta_tab, ts, tid, m, its + k);
         });
     } else {
         // fixed quota per wave and iteration, free-running (GFS_F_DBG_FREE_RUNNING)
@@ -107,7 +108,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(4, 4))) sgd1d_team_fused_kern
         for (uint32_t k = 0; k < n_iters; ++k) {
             a.it = its[k];
             for (uint64_t done = 0; done < wq; done += a.chunk)
-                team_iteration<B, LDS_TABLES, ATOMIC_LOADS, false>(a, path_tab, zeta_tab, ts, tid, wq - done < a.chunk ? wq - done : a.chunk, its + k);
+                team_iteration<B, LDS_TABLES, ATOMIC_LOADS, false, COMPACT>(a, path_tab, zeta_tab, ts, tid, wq - done < a.chunk ? wq - done : a.chunk, its + k);
         }
     }
     store_rng(a, tid, ts.rng);
@@ -165,6 +166,10 @@ static const void *team_fused_kernel_1d(const KernelShape &s, bool pooled) {
     return with_flag(pooled, [&](auto P) { return with_flag(s.lds_tables, [&](auto L) { return kernel_addr(sgd1d_team_fused_kernel<B, L(), P()>); }); });
 }
 const void *fused_kernel_1d(const KernelShape &s, bool pooled) {
+    if (s.compact) {
+        if (s.bundle != 64) return nullptr;
+        return with_flag(pooled, [&](auto P) { return with_flag(s.lds_tables, [&](auto L) { return kernel_addr(sgd1d_team_fused_kernel<64, L(), P(), true>); }); });
+    }
     switch (s.bundle) {
         case 16: return team_fused_kernel_1d<16>(s, pooled);
         case 32: return team_fused_kernel_1d<32>(s, pooled);
@@ -182,6 +187,10 @@ static const void *team_kernel_1d(const KernelShape &s) {
     }); }); });
 }
 const void *iteration_kernel_1d(const KernelShape &s) {
+    if (s.compact) {
+        if (s.bundle != 64 || s.trace) return nullptr;
+        return with_flag(s.lds_tables, [&](auto L) { return with_flag(s.atomic_loads, [&](auto A) { return kernel_addr(sgd1d_team_kernel<64, L(), A(), false, true>); }); });
+    }
     switch (s.bundle) {
         case 0: case 1:
             return with_flag(s.lds_tables, [&](auto L) { return with_flag(s.atomic_loads, [&](auto A) { return with_flag(s.trace, [&](auto T) {

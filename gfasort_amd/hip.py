@@ -18,6 +18,7 @@ F_PLAIN_LOADS, F_NO_LDS_TABLES, F_NO_FUSE = 1, 2, 4
 F_DBG_NO_ATOMICS, F_DBG_NO_XLOADS, F_DBG_ONE_COLOUR = 0x100, 0x200, 0x800
 F_DBG_NO_ALIGN, F_DBG_ALIGN_FIRST, F_DBG_WIDE_INDEX, F_DBG_NO_FUSED_TRIP = 0x1000, 0x2000, 0x4000, 0x8000
 F_ONE_PARTNER, F_DBG_NO_TWIN_TRIP, F_DBG_FREE_RUNNING = 0x10, 0x400, 0x20
+F_FULL_RECORDS = 0x80      # GFS_F_FULL_RECORDS: the 1D team kernels' trips read 16-byte step records even where 8-byte trip records would do
 F_PHASED = 0x40            # GFS_F_PHASED: the 1D sort's phased sampler (reference streams in a window of iterations)
 
 
@@ -152,7 +153,7 @@ EXPORTS = [
     "gfs_rank_positions_changed", "gfs_rank_get_positions", "gfs_rank_exchange_count", "gfs_rank_exchange_buffer",
     "gfs_rank_bind_exchange_buffer", "gfs_rank_window_begin", "gfs_rank_window_end", "gfs_rank_finish_begin",
     "gfs_rank_finish_buffer", "gfs_rank_finish_end", "gfs_rank_run",
-    "gfs_ctx_debug_step_records", "gfs_ctx_debug_kshift", "gfs_phase_window", "gfs_ctx_phase_window",
+    "gfs_ctx_debug_step_records", "gfs_ctx_debug_kshift", "gfs_ctx_record_bytes", "gfs_phase_window", "gfs_ctx_phase_window",
     "gfs_ctx_pair_errors", "gfs_stress_sample_pairs", "gfs_ctx_stress_of_pairs", "gfs_ctx_sort_quality", "gfs_pair_errors",
     "gfs_sort_quality_of", "gfs_batch_sort_quality",
     "gfs_ctx_path_errors", "gfs_ctx_stretched_pairs", "gfs_ctx_node_errors", "gfs_diagnose",
@@ -207,6 +208,8 @@ def lib():
         L.gfs_ctx_node_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.gfs_ctx_debug_step_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.gfs_ctx_debug_kshift.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.gfs_ctx_record_bytes.argtypes = [C.c_void_p]
+        L.gfs_ctx_record_bytes.restype = C.c_uint32
         L.gfs_phase_window.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.gfs_ctx_phase_window.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
         L.gfs_ctx_setup_1d.argtypes = [C.c_void_p] + [C.c_void_p] * 4
@@ -761,6 +764,11 @@ class Context:
         v = C.c_int32(0)
         check(lib().gfs_ctx_debug_kshift(self._h, C.c_int32(-2 if set is None else int(set)), C.byref(v)))
         return int(v.value)
+
+    def record_bytes(self):
+        """Bytes of the per-step record the trips of the next launch read: 8 (trip records) or 16 (step records); 0 where the
+        context is not set up or has no work."""
+        return int(lib().gfs_ctx_record_bytes(self._h))
 
     def phase_window(self, set_begin=-1, set_end=-1):
         """GFS_F_PHASED's effective window (begin, end) of this context; set_begin, set_end >= 0 replace it for later launches

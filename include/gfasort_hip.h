@@ -130,6 +130,11 @@ typedef struct gfs_launch_config {
  * Refused (GFS_E_ARG) with gfs_ctx_setup_nd, with a GFS_F_BUNDLE other than 0 or 64, and with gfs_rank_create.  Default
  * window: gfs_phase_window.  DESIGN.md §3 (K1e) and §5. */
 #define GFS_F_PHASED        0x40u
+/* Record width of the 1D team kernels' trips at B = 64.  Beside the 16-byte step records a context keeps 8-byte trip records
+ * { slot, low position word } (8 B per step more), and the trips read those where nothing is lost by it: every step position of
+ * the graph is below 2^32 bp and no node is crowded at the context's stream count (gfasort_amd/csrc/launch_policy.h
+ * compact_records).  Same terms, same bits, half the record bytes.  This flag keeps the trips on the 16-byte records. */
+#define GFS_F_FULL_RECORDS  0x80u
 #define GFS_F_DBG_NO_TWIN_TRIP 0x400u /* diagnostic: the two partners of a leader as two trips even where one would do   */
 #define GFS_F_DBG_FREE_RUNNING 0x20u   /* diagnostic: fused launches with a fixed quota per wave and iteration and no pacing
                                          (round 1's launch; the waves drift apart in the schedule) instead of work pools */
@@ -258,6 +263,11 @@ int   gfs_ctx_debug_step_records(const gfs_ctx *ctx, uint32_t *out, uint64_t n_w
 /* crowding onset: set >= 0 overrides the kshift of every later launch of this context, set = -1 restores the policy,
  * set < -1 changes nothing; *kshift_out (nullable) receives the value the kernels are handed (the context must be set up) */
 int   gfs_ctx_debug_kshift(gfs_ctx *ctx, int32_t set, int32_t *kshift_out);
+/* Bytes of the per-step record the trips of this context's next launch read: 8 (trip records) or 16 (step records; every kernel
+ * but the 1D team kernels at B = 64, GFS_F_FULL_RECORDS, a graph that is not eligible).  0: the context is not set up or has no
+ * work.  Follows gfs_ctx_debug_kshift.  The 8-byte records are made when a context is created (not for the items of a context
+ * set) and given up for good by gfs_ctx_setup_nd.  A batch (gfs_batch_*) takes reference-stream contexts only: always 16. */
+uint32_t gfs_ctx_record_bytes(const gfs_ctx *ctx);
 /* GFS_F_PHASED's window: set_begin, set_end >= 0 replace it for later launches (0 <= begin <= end <= iter_max + 1, else
  * GFS_E_ARG), both < 0 only query; *begin_out / *end_out (nullable) receive the effective window — the whole schedule where the
  * flag is a no-op (reference streams picked), on which a window cannot be set (GFS_E_STATE).  GFS_E_STATE on a context not set
