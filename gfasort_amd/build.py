@@ -10,7 +10,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libgfasort_hip.so")
 SOURCES = ["sgd_kernels_1d.hip", "sgd_kernels_1d_phased.hip", "sgd_kernels_nd.hip", "sgd_kernels_nd_team.hip", "sgd_kernels_nd_team_wide.hip", "sgd_kernels_batch.hip", "batch_readout_kernels.hip", "batch_quality_kernels.hip", "batch_diagnosis_kernels.hip", "batch_sort_quality_kernels.hip", "index_kernels.hip", "index_set_kernels.hip", "set_setup_kernels.hip", "quality_kernels.hip",
            "capi.hip", "capi_batch.hip", "capi_set.hip", "host_tables.hip", "multi.hip"]
-HEADERS = ["sgd_device.h", "sgd_kernel_common.h", "sgd_1d.h", "sgd_nd.h", "sgd_nd_team.h", "sgd_batch.h", "batch_plan.h", "batch_readout_plan.h", "readout_region.h", "quality_device.h", "segment_sort.h", "segment_device.h", "sort_key.h", "sgd_limits.h", "launch_policy.h", "capi_error.h", "device_memory.h", "sgd_host.h", "capi_ctx.h", "index_set.h", "index_set_plan.h", "set_seed.h", "set_state_plan.h", os.path.join("..", "..", "include", "gfasort_hip.h")]
+HEADERS = ["sgd_device.h", "sgd_kernel_common.h", "sgd_1d.h", "sgd_nd.h", "sgd_nd_team.h", "sgd_batch.h", "batch_plan.h", "batch_readout_plan.h", "readout_region.h", "quality_device.h", "segment_sort.h", "segment_device.h", "sort_key.h", "sgd_limits.h", "launch_policy.h", "capi_error.h", "device_memory.h", "sgd_host.h", "capi_ctx.h", "index_set.h", "index_set_plan.h", "set_seed.h", "set_seed_tables.h", "set_state_plan.h", os.path.join("..", "..", "include", "gfasort_hip.h")]
 
 # -ffp-contract=off : the reference (Rust) never fuses a*b+c; device and host tables must match it
 # -munsafe-fp-atomics: native global_atomic_add_f64 on hipMalloc'ed (coarse-grained) memory

@@ -4,8 +4,6 @@
 // launch_policy.h; the host tables are host_tables.hip's; batches of contexts are capi_batch.hip's (capi_ctx.h is what the two share).
 #include "capi_ctx.h"
 #include "index_set.h"
-#include "set_seed.h"
-#include "set_state_plan.h"
 
 #include <algorithm>
 #include <chrono>
@@ -85,44 +83,10 @@ void gfs::free_sgd_state(gfs_ctx *c) {
     c->d_its.reset();
     c->d_its_all.reset();
     c->d_pool.reset();
+    c->d_seed_item.reset();
+    c->d_seed_blocks.reset();
+    c->state_arena.reset();                                               // (after the arrays that borrowed from it)
     c->configured = false;
-}
-
-static int seed_streams(gfs_ctx *c) {
-    // stream t <- Xoshiro256Plus::seed_from_u64(seed + stream_base + t)   (sgd.rs:431-432)
-    const uint64_t T = c->shape.n_streams;
-    std::vector<uint64_t> st(4 * T);
-    for (uint64_t t = 0; t < T; ++t) {
-        uint64_t sm = c->params.seed + c->cfg.stream_base + t;
-        for (int k = 0; k < 4; ++k) st[(uint64_t)k * T + t] = gfs::splitmix64(sm);
-    }
-    HIPCHK(hipMemcpy(c->d_rng, st.data(), st.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(c->d_counters, 0, kCounterBytes));
-    if (c->d_trace_cnt) HIPCHK(hipMemset(c->d_trace_cnt, 0, T * sizeof(uint32_t)));
-    c->events_used = 0; c->kernel_ms_harvested = 0.0; c->iterations = 0; c->total_ms = 0.0;
-    return GFS_OK;
-}
-
-// The zeta table of sgd.rs:311-331 on the device.  Only indices reachable from
-// jump <= min(space, max_path_steps-1) are ever read (sgd.rs:462-469: shape.zlen_staged of them); when the table is computed here
-// the running sum — which is order-dependent and must be accumulated exactly as the reference does —
-// stops at the largest i that feeds a reachable entry (space is the longest path in bp: 1.3e6 for C3,
-// of which 1.6e5 matter).
-static int upload_zeta_table(gfs_ctx *c, const gfs_sgd_params *p, const double *zetas) {
-    const uint64_t zlen_full = c->shape.zlen_full;
-    std::vector<double> ztab;
-    if (!zetas) {
-        gfs_sgd_params q = *p;
-        q.space = gfs::zeta_clamped_space(*p, c->shape.zlen_staged);
-        std::vector<double> part(gfs_zeta_table_len(&q));
-        gfs_zeta_table(&q, part.data());
-        ztab.assign(zlen_full, 0.0);
-        std::copy(part.begin(), part.begin() + std::min<size_t>(part.size(), ztab.size()), ztab.begin());
-        zetas = ztab.data();
-    }
-    HIPCHK(c->d_zetas.grow(zlen_full * 8));
-    HIPCHK(hipMemcpy(c->d_zetas, zetas, zlen_full * 8, hipMemcpyHostToDevice));
-    return GFS_OK;
 }
 
 gfs::IterConsts gfs::iter_consts(const gfs_ctx *c, uint64_t k) { return gfs::iter_consts(c->params, c->etas, c->shape, k); }
@@ -261,54 +225,13 @@ void gfs::commit_setup(gfs_ctx *c, gfs::SetupPlan &&sp) {
     c->events_used = 0; c->kernel_ms_harvested = 0.0; c->iterations = 0; c->total_ms = 0.0;
 }
 
+// A single context's setup: a set setup of one item (capi_set.hip setup_contexts; capi_ctx.h says what is its own)
 static int setup_common(gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs_launch_config *cfg,
                         const double *etas, const double *zetas) {
     if (!c) return fail(GFS_E_ARG, "ctx is null");
-    std::string err;
-    int rc = gfs::check_setup_args(p, dims, cfg, &err);                    // (refused before the context is touched)
-    if (rc) return fail(rc, err);
-    HIPCHK(hipSetDevice(c->device));
-    gfs::free_sgd_state(c);
-    if (dims != 0 && c->d_trip_rec) {                                      // a layout context: no kernel of its reads trip records; a
-        HIPCHK(hipDeviceSynchronize());                                    // later 1D setup of it runs on step records
-        c->d_trip_rec.reset();
-        c->record_facts.have_trip_rec = false;
-    }
-    gfs::SetupPlan sp;
-    const int planned = gfs::plan_setup(c, p, dims, cfg, etas, &sp, &err);
-    uint64_t bytes[GFS_STATE_KINDS];
-    for (uint32_t k = 0; k < GFS_STATE_KINDS; ++k) bytes[k] = gfs::state_bytes(sp, k);
-    gfs::commit_setup(c, std::move(sp));                                   // (a refused shape leaves no shape, plan or schedule behind)
-    if (c->x_len) {                                                        // (before the policy's verdict: a refused shape keeps its replica)
-        HIPCHK(c->d_x.grow(bytes[GFS_STATE_POSITIONS]));
-        HIPCHK(hipMemset(c->d_x, 0, bytes[GFS_STATE_POSITIONS]));
-    }
-    if (planned < 0) return fail(planned, err);
-    if (planned == GFS_NOTHING_TO_DO) { c->configured = true; return GFS_NOTHING_TO_DO; }
-
-    // zeta table (host, bit-exact) unless supplied
-    rc = upload_zeta_table(c, p, zetas);
-    if (rc) return rc;
-    HIPCHK(c->d_rng.grow(bytes[GFS_STATE_RNG]));
-    if (bytes[GFS_STATE_LEAD]) {
-        HIPCHK(c->d_lead.grow(bytes[GFS_STATE_LEAD]));
-        HIPCHK(hipMemset(c->d_lead, 0, bytes[GFS_STATE_LEAD]));             // trips left = 0: no pass yet
-    }
-    HIPCHK(c->d_counters.grow(bytes[GFS_STATE_COUNTERS]));
-    if (bytes[GFS_STATE_TRACE]) {
-        HIPCHK(c->d_trace.grow(bytes[GFS_STATE_TRACE]));
-        HIPCHK(hipMemset(c->d_trace, 0, bytes[GFS_STATE_TRACE]));
-        HIPCHK(c->d_trace_cnt.grow(bytes[GFS_STATE_TRACE_COUNTS]));
-    }
-    rc = seed_streams(c);
-    if (rc) return rc;
-    if (bytes[GFS_STATE_SCHEDULE]) {
-        HIPCHK(c->d_its_all.grow(bytes[GFS_STATE_SCHEDULE]));
-        rc = upload_schedule(c);
-        if (rc) return rc;
-    }
-    c->configured = true;
-    return GFS_OK;
+    int32_t rc = GFS_OK;                                                   // GFS_OK or GFS_NOTHING_TO_DO
+    const int bad = gfs::setup_contexts(&c, &p, &dims, cfg, 1, c->state_arena, nullptr, etas, zetas, &rc, nullptr);
+    return bad ? bad : rc;
 }
 
 extern "C" {
@@ -438,8 +361,16 @@ int gfs_ctx_reset_streams(gfs_ctx *c) {
     if (!c || !c->d_rng) return fail(GFS_E_STATE, "context not set up");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipDeviceSynchronize());
-    if (c->d_lead) HIPCHK(hipMemset(c->d_lead, 0, 8 * c->shape.n_streams * sizeof(uint32_t)));
-    return seed_streams(c);
+    // Counters, team state and trace counts back to zero — a memset each: the traces, which stay, lie between them, and in a set's
+    // arena other items' arrays — and the setup's seeding launch for this context alone, from the tables the setup left in the arena.
+    const uint64_t T = c->shape.n_streams;
+    HIPCHK(hipMemsetAsync(c->d_counters, 0, kCounterBytes, 0));
+    if (c->d_lead) HIPCHK(hipMemsetAsync(c->d_lead, 0, 8 * T * sizeof(uint32_t), 0));
+    if (c->d_trace_cnt) HIPCHK(hipMemsetAsync(c->d_trace_cnt, 0, T * sizeof(uint32_t), 0));
+    HIPCHK(gfs::seed_streams_device(c->d_seed_item, c->d_seed_blocks, (uint32_t)((T + gfs::SEED_BLOCK - 1) / gfs::SEED_BLOCK), 0));
+    HIPCHK(hipDeviceSynchronize());
+    c->events_used = 0; c->kernel_ms_harvested = 0.0; c->iterations = 0; c->total_ms = 0.0;
+    return GFS_OK;
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include "launch_policy.h"
 #include "sgd_host.h"
 #include "readout_region.h"
+#include "set_seed.h"
 
 #include <chrono>
 #include <cstdio>
@@ -24,7 +25,7 @@ static_assert(sizeof(gfs_node_error) == 3 * 8, "K7f / K7j write gfs_node_error a
 
 static constexpr size_t kCounterBytes = gfs::COUNTER_SLOTS * 8 * sizeof(unsigned long long);   // lines of 64 B
 
-// The kernels of a configured context, resolved once by setup_common for the shape the policy decided (gfs_ctx::shape,
+// The kernels of a configured context, resolved once by its setup (plan_setup) for the shape the policy decided (gfs_ctx::shape,
 // launch_policy.h): everything of gfs_ctx_run_iteration / gfs_ctx_run_range that does not depend on the call.
 struct LaunchPlan {
     const void *iteration = nullptr;         // K1 / K1b, K2 / K2b: one iteration per launch
@@ -55,7 +56,10 @@ struct gfs_ctx {
     gfs::Array<uint64_t> d_path_len;
     gfs::Array<uint32_t> d_perm;        // node layout on the device (dense index -> slot)
     gfs::Array<uint32_t> d_node_len;    // node lengths by dense index (K4: initial positions)
-    // SGD state
+    // SGD state: every array but the positions lies in one arena and borrows from it — the context's own (gfs_ctx_setup_*: a set
+    // setup of one item, freed by the next setup and by destroy), or its set's, and then this one stays empty.  The positions of a
+    // context set up alone are an allocation of their own: they outlive a refused setup and go when a caller binds its own.
+    gfs::Buffer state_arena;           // (declared before them: it outlives them)
     int dims = 0;                      // 0 = 1D
     bool configured = false;
     gfs_sgd_params params{};
@@ -67,6 +71,7 @@ struct gfs_ctx {
     gfs::Array<uint32_t> d_lead;     // team kernels: the waves' partly expanded passes, [8][n_streams]
     gfs::Array<unsigned long long> d_counters;
     gfs::Array<gfs_term> d_trace; gfs::Array<uint32_t> d_trace_cnt;
+    gfs::Array<gfs::SeedItem> d_seed_item; gfs::Array<uint32_t> d_seed_blocks;   // gfs_ctx_reset_streams: the tables of a seeding launch of this context alone
     gfs::Buffer d_its;                                        // schedule slice of a fused launch (arbitrary lists), grown on demand
     gfs::Array<gfs::IterConsts> d_its_all;                    // constants of iterations 0..=iter_max, resident
     gfs::Buffer d_pool;                // fused launch: per-iteration work pool counters (sgd_kernels_1d.hip), grown on demand
@@ -160,7 +165,7 @@ GFS_LOCAL int build_contexts(const gfs_graph_view *const *graphs, gfs_ctx *const
                              bool staged, Laps *laps, gfs_ctx_set_info *info);
 }  // namespace gfs
 
-// capi.hip, for capi_set.hip: the ONE text of a setup's host half, which gfs_ctx_setup_* and gfs_ctx_set_setup_* share.
+// capi.hip, for capi_set.hip: the host half of a setup, which the driver (setup_contexts, below) calls for every item.
 namespace gfs {
 // What a setup decides on the host before it touches its context: the launch shape and the kernels (launch_policy.h, the
 // residency query in the middle), the eta schedule, the length of the position vector.  rc: GFS_OK, or GFS_NOTHING_TO_DO for a
@@ -177,11 +182,11 @@ struct SetupPlan {
     std::vector<double> etas;
 };
 // Reads c's facts, writes nothing of c.  p, dims and cfg have passed check_setup_args.  A refusal returns its code with its text
-// in *err; out->x_len is set by then (the single call allocates its positions before the policy runs).
+// in *err; out->x_len is set by then (a single context gets its zeroed replica whatever the policy says).
 GFS_LOCAL int plan_setup(const gfs_ctx *c, const gfs_sgd_params *p, int dims, const gfs_launch_config *cfg, const double *etas,
                          SetupPlan *out, std::string *err);
-// Bytes of state array `kind` (GFS_STATE_*) that a setup of this shape makes, 0 for one it does not: the sizes gfs_ctx_setup_*
-// allocates, a set's arena is planned with and gfs_ctx_debug_sgd_state reads.  has_work: the setup returned GFS_OK.
+// Bytes of state array `kind` (GFS_STATE_*) that a setup of this shape makes, 0 for one it does not: the sizes the state arena is
+// planned with and gfs_ctx_debug_sgd_state reads.  has_work: the setup returned GFS_OK.
 inline uint64_t state_bytes(uint32_t kind, bool has_work, uint64_t x_len, const LaunchShape &s, const gfs_sgd_params &p, const gfs_launch_config &cfg) {
     if (kind == GFS_STATE_POSITIONS) return x_len * 8;
     if (!has_work) return 0;
@@ -205,6 +210,27 @@ GFS_LOCAL void schedule_table(const gfs_sgd_params &p, const std::vector<double>
 GFS_LOCAL void free_sgd_state(gfs_ctx *c);
 // c's host fields from the plan, and the run's statistics back to zero; the state arrays are the caller's to put in place
 GFS_LOCAL void commit_setup(gfs_ctx *c, SetupPlan &&sp);
+
+// capi_set.hip, for capi.hip: the ONE driver of a setup (K3c), for a set's items and for a single context, which is a set of one.
+// Every ctxs[i] set up as gfs_ctx_setup_1d / _nd would (dims[i] = 0 / 1..8; < 0: refused, "dimensions must be 1..8"): its state
+// arrays laid out in `arena` by gfs_ctx_set_state_plan and borrowed from it, the seeding tables behind them; one memset, one copy,
+// one seeding launch.  item_rc[i] (nullable): GFS_OK or GFS_NOTHING_TO_DO.  What tells a single context from a set's items, and
+// nothing else:
+//   arena     whose it is — the set's, kept across setups and regrown where too small, or the single context's own
+//             (gfs_ctx::state_arena), which free_sgd_state releases at every setup
+//   pinned    a set: its pinned staging, kept like the arena, which mirrors the uploaded range; the error texts name the item
+//             ("set item <i>: "), a refusal names the lowest and leaves EVERY item as it was, and the positions lie in the arena.
+//             null: a single context (n == 1).  Its range is staged in pageable memory (no hipHostMalloc per setup) and goes up in
+//             one blocking copy; its positions are an allocation of its own (gfs_ctx::state_arena says why); and its refusals keep
+//             their order: the arguments are checked before the context is touched, then it is let go (free_sgd_state; a layout
+//             gives its trip records back), planned, committed and given its zeroed replica, and only then is a refusal of the
+//             launch policy returned — the context not set up, the replica kept.
+//   etas      a caller's schedule, iter_max + 1 doubles, into the plan (single only; null: computed)
+//   zetas     a caller's zeta table, zlen_full doubles, in the place of the zeta slice in what goes up (single only; null: computed)
+//   info      (nullable) what the call allocated, copied and launched: a set keeps it for gfs_ctx_set_get_setup_info
+GFS_LOCAL int setup_contexts(gfs_ctx *const *ctxs, const gfs_sgd_params *const *params, const int *dims, const gfs_launch_config *cfgs,
+                             uint64_t n, Buffer &arena, Buffer *pinned, const double *etas, const double *zetas, int32_t *item_rc,
+                             gfs_ctx_set_setup_info *info);
 }  // namespace gfs
 
 // capi.hip, for capi_batch.hip

@@ -1,11 +1,12 @@
 // capi_set.hip — the context sets of the C ABI (include/gfasort_hip.h, gfs_ctx_set_*): many gfs_ctx (capi.hip, capi_ctx.h) built
 // from many graph views in ONE pass over their disjoint union (K3b, index_set_kernels.hip), and the driver of that build, which
 // gfs_ctx_create shares: a single context is a set of one.  The items' index arrays live in one arena the set owns, the items
-// borrow them.  What gfs_ctx_setup_* allocates stays each item's own; gfs_ctx_set_setup_* sets every item up in one pass (K3c,
-// set_setup_kernels.hip), their state arrays in a second arena of the set's.
+// borrow them.  gfs_ctx_set_setup_* sets every item up in one pass (K3c, set_setup_kernels.hip), their state arrays in a second
+// arena of the set's; the driver of that setup is here too, and gfs_ctx_setup_* shares it: again a set of one, with an arena of the
+// context's own.
 #include "capi_ctx.h"
 #include "index_set.h"
-#include "set_seed.h"
+#include "set_seed_tables.h"
 #include "set_state_plan.h"
 
 #include <algorithm>
@@ -115,7 +116,7 @@ int gfs::build_contexts(const gfs_graph_view *const *graphs, gfs_ctx *const *ctx
     // A single context: 8-byte trip records beside the step records, written by the same pass (sgd_1d.h TripRec), and the facts that
     // say whether its trips may read them (launch_policy.h compact_records).  Its launch shape is not known before its setup, so the
     // array is made here for every graph with steps and given back at once where a position does not fit its 32 bits or a node
-    // repeats within 64 steps (b > 0), and by a layout's setup (capi.hip setup_common); an allocation that fails is no error: the
+    // repeats within 64 steps (b > 0), and by a layout's setup (setup_contexts); an allocation that fails is no error: the
     // context keeps full records.
     gfs_ctx *single = staged || n != 1 ? nullptr : ctxs[0];
     if (single && S && single->d_trip_rec.grow((S + 1) * sizeof(uint2)) != hipSuccess) (void)hipGetLastError();
@@ -160,25 +161,49 @@ int gfs::build_contexts(const gfs_graph_view *const *graphs, gfs_ctx *const *ctx
     return GFS_OK;
 }
 
-// ---- set setup (K3c) -------------------------------------------------------------------------------------------------------------
-// Every item set up as gfs_ctx_setup_1d / _nd would (dims[i] = 0 / 1..8), in one pass: the host half of each (capi.hip plan_setup,
-// the single call's own text) before anything is touched; then one arena, one memset, one copy, one launch.
-static int set_setup(gfs_ctx_set *s, const std::vector<const gfs_sgd_params *> &params, const std::vector<int> &dims,
-                     const gfs_launch_config *cfgs, int32_t *item_rc) {
+// ---- setup (K3c) -----------------------------------------------------------------------------------------------------------------
+// (capi_ctx.h says what the parameters mean)
+int gfs::setup_contexts(gfs_ctx *const *ctxs, const gfs_sgd_params *const *params, const int *dims, const gfs_launch_config *cfgs, uint64_t n,
+                        gfs::Buffer &arena, gfs::Buffer *pinned, const double *etas, const double *zetas, int32_t *item_rc,
+                        gfs_ctx_set_setup_info *info_out) {
     const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t n = s->items.size();
+    const bool single = pinned == nullptr;
+    const std::string set = single ? "" : "set ";
+    auto named = [single](uint64_t i, const std::string &text) { return single ? text : item_prefix(i) + text; };
     std::string err;
     for (uint64_t i = 0; i < n; ++i) {                                     // (no item is touched, no device call is made, before all pass)
-        if (dims[i] < 0) return fail(GFS_E_UNSUPPORTED, item_prefix(i) + "dimensions must be 1..8");   // as gfs_ctx_setup_nd: before its other arguments
-        if (int rc = gfs::check_setup_args(params[i], dims[i], cfgs ? &cfgs[i] : nullptr, &err)) return fail(rc, item_prefix(i) + err);
+        if (dims[i] < 0) return fail(GFS_E_UNSUPPORTED, named(i, "dimensions must be 1..8"));   // as gfs_ctx_setup_nd: before its other arguments
+        if (int rc = gfs::check_setup_args(params[i], dims[i], cfgs ? &cfgs[i] : nullptr, &err)) return fail(rc, named(i, err));
     }
-    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipSetDevice(ctxs[0]->device));
+    // What a context holds of an earlier setup goes: borrows dropped, an arena of its own freed; a layout context gives its 8-byte
+    // trip records back, which no kernel of its reads (a set's items have none; a later 1D setup runs on step records).
+    auto let_go = [&]() {
+        // (nothing of an earlier run in flight on what goes or is written over; a single context waits as it always did: where it
+        // gives trip records back, and else in the hipFree of what it owns)
+        const hipError_t e = single && !(dims[0] != 0 && ctxs[0]->d_trip_rec) ? hipSuccess : hipDeviceSynchronize();
+        for (uint64_t i = 0; i < n; ++i) {
+            gfs::free_sgd_state(ctxs[i]);
+            if (dims[i] != 0) { ctxs[i]->d_trip_rec.reset(); ctxs[i]->record_facts.have_trip_rec = false; }
+        }
+        return e;
+    };
+    // A single context is let go BEFORE it is planned: the plan reads have_trip_rec, and a refusal leaves the context not set up.
+    if (single) HIPCHK(let_go());
 
     // 1. host: every item's launch shape, kernels and schedule; then where its state arrays lie
     std::vector<gfs::SetupPlan> plans(n);
+    int refused = GFS_OK;                                                  // a single context's: returned once its replica is there; its plan is one of nothing to do
     for (uint64_t i = 0; i < n; ++i) {
-        const int rc = gfs::plan_setup(s->items[i].get(), params[i], dims[i], cfgs ? &cfgs[i] : nullptr, nullptr, &plans[i], &err);
-        if (rc < 0) return fail(rc, item_prefix(i) + err);
+        const int rc = gfs::plan_setup(ctxs[i], params[i], dims[i], cfgs ? &cfgs[i] : nullptr, etas, &plans[i], &err);
+        if (rc < 0 && !single) return fail(rc, item_prefix(i) + err);
+        if (rc < 0) refused = rc;
+    }
+    if (single && plans[0].x_len) {                                        // its zeroed replica, whatever the policy said: a refused shape keeps it.
+        gfs_ctx *c = ctxs[0];                                              // Before the tables: the memset runs under the host's zeta sum
+        hipError_t e = c->d_x.grow(plans[0].x_len * 8);
+        if (e == hipSuccess) e = hipMemset(c->d_x, 0, plans[0].x_len * 8);
+        if (e != hipSuccess) { gfs::commit_setup(c, std::move(plans[0])); return fail(GFS_E_HIP, std::string("positions: ") + hipGetErrorString(e)); }   // (the plan committed, as it always was)
     }
     constexpr int K = gfs::SET_STATE_KINDS;
     std::vector<uint64_t> bytes(K * n), offsets(K * n);
@@ -186,107 +211,123 @@ static int set_setup(gfs_ctx_set *s, const std::vector<const gfs_sgd_params *> &
     info.items = n;
     std::vector<gfs::SeedItem> seeds;                                      // the items with streams (rng: filled in once the arena is there)
     std::vector<uint64_t> seed_of;                                         // ... and which items they are
-    uint64_t total_blocks = 0;
+    uint64_t total_blocks = 0, most_blocks = 0;
     for (uint64_t i = 0; i < n; ++i) {
         const gfs::SetupPlan &sp = plans[i];
         for (int k = 0; k < K; ++k) bytes[K * i + k] = gfs::state_bytes(sp, (uint32_t)k);
+        if (single) bytes[K * i + GFS_STATE_POSITIONS] = 0;                // (an allocation of its own, above)
         if (sp.rc != GFS_OK) { ++info.nothing_to_do; continue; }
         ++info.configured;
         info.total_streams += sp.shape.n_streams;
+        const uint64_t nb = (sp.shape.n_streams + gfs::SEED_BLOCK - 1) / gfs::SEED_BLOCK;
         seeds.push_back(gfs::SeedItem{nullptr, sp.params.seed + sp.cfg.stream_base, (uint32_t)sp.shape.n_streams, (uint32_t)total_blocks});
         seed_of.push_back(i);
-        total_blocks += (sp.shape.n_streams + gfs::SEED_BLOCK - 1) / gfs::SEED_BLOCK;
+        total_blocks += nb;
+        most_blocks = std::max(most_blocks, nb);
         if (total_blocks > 0x7FFFFFFFull) return fail(GFS_E_UNSUPPORTED, "set items 0.." + std::to_string(i) + " have more streams together than one seeding launch holds");
     }
-    // the arena: [positions, counters, team state, traces, trace counts | RNG words | zeta tables, schedule tables, seeding tables]
+    // the arena: [positions, counters, team state, traces, trace counts | RNG words | zeta tables, schedule tables, seeding tables
+    // (set_seed_tables.h)]
     const uint64_t arrays_end = gfs::set_state_plan(bytes.data(), n, offsets.data());
     const uint64_t zero_end = gfs::set_state_kind_begin(offsets.data(), GFS_STATE_RNG);
     const uint64_t upload_begin = gfs::set_state_kind_begin(offsets.data(), GFS_STATE_ZETAS);
-    const uint64_t seeds_at = arrays_end, blocks_at = seeds_at + gfs::round256(seeds.size() * sizeof(gfs::SeedItem));
-    const uint64_t arena_bytes = blocks_at + gfs::round256(total_blocks * sizeof(uint32_t)), stage_bytes = arena_bytes - upload_begin;
+    const gfs::SeedTables tables = gfs::seed_tables_plan(arrays_end, seeds.size(), sizeof(gfs::SeedItem), total_blocks, most_blocks);
+    const uint64_t arena_bytes = tables.end, stage_bytes = arena_bytes - upload_begin;
     info.state_bytes = arena_bytes;
 
-    // ---- from here on the items are touched: a failure leaves every one of them not set up and the arena released ----
-    HIPCHK(hipDeviceSynchronize());                                        // (nothing of an earlier run in flight on what goes or is written over)
-    for (auto &c : s->items) gfs::free_sgd_state(c.get());                 // borrows dropped, arrays of an item's own setup freed
+    // ---- from here on a set's items are touched: a failure leaves every context not set up and the arena released ----
+    if (!single) HIPCHK(let_go());                                         // (a set only AFTER every item is planned: a refusal above left all as they were)
     int rc = GFS_OK;
-    auto ok = [&rc, s](const char *what, hipError_t e) {                   // false: rc holds the reported error, the arena is gone
+    auto ok = [&rc, &arena](const std::string &what, hipError_t e) {       // false: rc holds the reported error, the arena is gone
         if (e == hipSuccess) return true;
         (void)hipDeviceSynchronize();
-        s->state_arena.reset();
-        rc = fail(GFS_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+        arena.reset();
+        rc = fail(GFS_E_HIP, what + ": " + hipGetErrorString(e));
         return false;
     };
-    if (s->state_arena.bytes < arena_bytes) {
+    if (arena.bytes < arena_bytes) {
         ++info.device_allocations;
-        if ((rc = s->state_arena.reserve(arena_bytes, "hipMalloc set state arena"))) return rc;
+        if ((rc = arena.reserve(arena_bytes, ("hipMalloc " + set + "state arena").c_str()))) return rc;
     }
-    if (s->h_stage.bytes < stage_bytes) {
+    std::vector<unsigned char> pageable(single ? stage_bytes : 0);         // a single context's staging: no hipHostMalloc per setup
+    if (!single && pinned->bytes < stage_bytes) {
         ++info.device_allocations;
-        if ((rc = s->h_stage.reserve(stage_bytes, "hipHostMalloc set state staging"))) { s->state_arena.reset(); return rc; }
+        if ((rc = pinned->reserve(stage_bytes, "hipHostMalloc set state staging"))) { arena.reset(); return rc; }
     }
-    unsigned char *d_arena = s->state_arena.as<unsigned char>(), *h = s->h_stage.as<unsigned char>();
+    unsigned char *d_arena = arena.as<unsigned char>(), *h = single ? pageable.data() : pinned->as<unsigned char>();
     auto staged = [h, upload_begin](uint64_t arena_offset) { return h + (arena_offset - upload_begin); };
 
-    // 2. zeta tables: items that share (theta, space_max, step) get slices of one running sum;  3. staging: the tables, the schedule
-    // tables and the seeding kernel's two tables, where the arena has them
-    if (stage_bytes) std::memset(h, 0, stage_bytes);                       // (the zero padding of every zeta table up to zlen_full)
+    // 2. zeta tables: items that share (theta, space_max, step) get slices of one running sum — or the caller's table as it is;
+    // 3. staging: the tables, the schedule tables and the seeding kernel's tables, where the arena has them
+    if (stage_bytes && !single) std::memset(h, 0, stage_bytes);            // (the zero padding of every zeta table up to zlen_full; pageable: zeroed when made)
     {
         std::vector<gfs_sgd_params> clamped(n);
-        std::vector<uint8_t> needed(n, 0);
+        std::vector<uint8_t> has_work(n, 0), summed(n, 0);
         for (uint64_t i = 0; i < n; ++i) {
             if (plans[i].rc != GFS_OK) continue;
             clamped[i] = plans[i].params;
             clamped[i].space = gfs::zeta_clamped_space(plans[i].params, plans[i].shape.zlen_staged);
-            needed[i] = 1;
+            has_work[i] = 1; summed[i] = zetas == nullptr;
         }
-        const gfs::SharedZetaTables shared = gfs::shared_zeta_tables(clamped.data(), needed.data(), n);
+        const gfs::SharedZetaTables shared = gfs::shared_zeta_tables(clamped.data(), summed.data(), n);
         for (uint64_t i = 0; i < n; ++i) {
-            if (!needed[i]) continue;
+            if (!has_work[i]) continue;
             const gfs::SetupPlan &sp = plans[i];
-            gfs::zeta_slice(shared.tables[shared.table_of[i]], clamped[i], sp.shape.zlen_full, reinterpret_cast<double *>(staged(offsets[K * i + GFS_STATE_ZETAS])));
+            double *table = reinterpret_cast<double *>(staged(offsets[K * i + GFS_STATE_ZETAS]));
+            if (zetas) std::memcpy(table, zetas, sp.shape.zlen_full * sizeof(double));
+            else gfs::zeta_slice(shared.tables[shared.table_of[i]], clamped[i], sp.shape.zlen_full, table);
             if (bytes[K * i + GFS_STATE_SCHEDULE])
                 gfs::schedule_table(sp.params, sp.etas, sp.shape, reinterpret_cast<gfs::IterConsts *>(staged(offsets[K * i + GFS_STATE_SCHEDULE])));
         }
     }
-    uint32_t *h_block_item = reinterpret_cast<uint32_t *>(staged(blocks_at));
-    for (size_t k = 0; k < seeds.size(); ++k) {
-        seeds[k].rng = reinterpret_cast<uint64_t *>(d_arena + offsets[K * seed_of[k] + GFS_STATE_RNG]);
-        const uint64_t nb = (seeds[k].n_streams + gfs::SEED_BLOCK - 1) / gfs::SEED_BLOCK;
-        for (uint64_t b = 0; b < nb; ++b) h_block_item[seeds[k].first_block + b] = (uint32_t)k;
-    }
-    if (!seeds.empty()) std::memcpy(staged(seeds_at), seeds.data(), seeds.size() * sizeof(gfs::SeedItem));
+    for (size_t k = 0; k < seeds.size(); ++k) seeds[k].rng = reinterpret_cast<uint64_t *>(d_arena + offsets[K * seed_of[k] + GFS_STATE_RNG]);
+    if (!seeds.empty()) gfs::fill_seed_tables(tables, seeds.data(), seeds.size(), gfs::SEED_BLOCK, staged(tables.items_at));
 
-    // 4. one memset over everything a setup zeroes; one copy; 5. one launch over the concatenated streams
+    // 4. one memset over everything a setup zeroes; one copy (blocking from pageable staging); 5. one launch over the concatenated streams
     if (zero_end) {
-        if (!ok("hipMemset set state", hipMemsetAsync(d_arena, 0, zero_end, 0))) return rc;
+        if (!ok("hipMemset " + set + "state", hipMemsetAsync(d_arena, 0, zero_end, 0))) return rc;
         ++info.launches;
     }
     if (stage_bytes) {
-        if (!ok("hipMemcpy set state", hipMemcpyAsync(d_arena + upload_begin, h, stage_bytes, hipMemcpyHostToDevice, 0))) return rc;
+        if (!ok("hipMemcpy " + set + "state", single ? hipMemcpy(d_arena + upload_begin, h, stage_bytes, hipMemcpyHostToDevice)
+                                                     : hipMemcpyAsync(d_arena + upload_begin, h, stage_bytes, hipMemcpyHostToDevice, 0))) return rc;
         ++info.copies;
     }
     if (total_blocks) {
-        if (!ok("set_seed_streams_kernel", gfs::seed_streams_device(reinterpret_cast<const gfs::SeedItem *>(d_arena + seeds_at),
-                                                                    reinterpret_cast<const uint32_t *>(d_arena + blocks_at), (uint32_t)total_blocks, 0))) return rc;
+        if (!ok("set_seed_streams_kernel", gfs::seed_streams_device(reinterpret_cast<const gfs::SeedItem *>(d_arena + tables.items_at),
+                                                                    reinterpret_cast<const uint32_t *>(d_arena + tables.blocks_at), (uint32_t)total_blocks, 0))) return rc;
         ++info.launches;
     }
     if (!ok("hipDeviceSynchronize", hipDeviceSynchronize())) return rc;     // (the staging is free again; a fault shows here)
 
-    for (uint64_t i = 0; i < n; ++i) {
-        gfs_ctx *c = s->items[i].get();
+    for (uint64_t i = 0, k = 0; i < n; ++i) {
+        gfs_ctx *c = ctxs[i];
         const uint64_t *at = &offsets[K * i], *size = &bytes[K * i];
         auto lend = [d_arena, at, size](gfs::Buffer &b, uint32_t kind) { if (size[kind]) (void)b.borrow(d_arena + at[kind]); };
+        const bool has_work = plans[i].rc == GFS_OK;
         if (item_rc) item_rc[i] = plans[i].rc;
         gfs::commit_setup(c, std::move(plans[i]));
         lend(c->d_x, GFS_STATE_POSITIONS); lend(c->d_counters, GFS_STATE_COUNTERS); lend(c->d_lead, GFS_STATE_LEAD);
         lend(c->d_trace, GFS_STATE_TRACE); lend(c->d_trace_cnt, GFS_STATE_TRACE_COUNTS); lend(c->d_rng, GFS_STATE_RNG);
         lend(c->d_zetas, GFS_STATE_ZETAS); lend(c->d_its_all, GFS_STATE_SCHEDULE);
-        c->configured = true;
+        if (has_work) {
+            (void)c->d_seed_item.borrow(d_arena + tables.alone_at + k++ * sizeof(gfs::SeedItem));
+            (void)c->d_seed_blocks.borrow(d_arena + tables.zeros_at);
+        }
+        c->configured = refused == GFS_OK;
     }
+    if (refused) return fail(refused, err);
     info.setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    s->setup_info = info;
+    if (info_out) *info_out = info;
     return GFS_OK;
+}
+
+static int set_setup(gfs_ctx_set *s, const std::vector<const gfs_sgd_params *> &params, const std::vector<int> &dims,
+                     const gfs_launch_config *cfgs, int32_t *item_rc) {
+    std::vector<gfs_ctx *> ctxs;
+    for (auto &c : s->items) ctxs.push_back(c.get());
+    return gfs::setup_contexts(ctxs.data(), params.data(), dims.data(), cfgs, ctxs.size(), s->state_arena, &s->h_stage, nullptr, nullptr, item_rc,
+                               &s->setup_info);
 }
 
 extern "C" {

@@ -183,7 +183,7 @@ inline int shape_before_residency(const GraphFacts &g, const DeviceFacts &dev, c
 
     // The zeta table of sgd.rs:311-331 on the device.  Only indices reachable from
     // jump <= min(space, max_path_steps-1) are ever read (sgd.rs:462-469): those are staged (and, where the table is computed
-    // by the library, summed: capi.hip upload_zeta_table).
+    // by the library, summed: set_state_plan.h zeta_clamped_space).
     s.zlen_full = gfs_zeta_table_len(p);
     if (s.zlen_full > 0xFFFFFFFFull) { *err = "zeta table too long"; return GFS_E_UNSUPPORTED; }
     const uint64_t maxjump = std::min<uint64_t>(p->space, g.max_path_steps ? g.max_path_steps - 1 : 0);

@@ -1,6 +1,6 @@
-// set_setup_kernels.hip — K3c: the RNG streams of every item of a context set, seeded in ONE launch (gfs_ctx_set_setup_*,
-// capi_set.hip).  gfs_ctx_setup_* seeds a context's streams on the host and copies them up (capi.hip seed_streams); for a set that
-// is a loop of splitmix64 over every stream of every item and one blocking copy per item.  Here the grid is the concatenation of
+// set_setup_kernels.hip — K3c: the RNG streams of every item of a context set, seeded in ONE launch (capi_set.hip setup_contexts:
+// gfs_ctx_set_setup_*, and gfs_ctx_setup_* and gfs_ctx_reset_streams with a set of one).  On the host that is a loop of splitmix64
+// over every stream of every item and a blocking copy per item.  Here the grid is the concatenation of
 // the items' grids, as in the batch kernels (sgd_kernels_batch.hip): a workgroup looks its item up and never straddles two.
 // 64-bit wrapping integer arithmetic throughout: the words are bit for bit the host's.
 #include "set_seed.h"

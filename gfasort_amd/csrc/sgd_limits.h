@@ -32,8 +32,8 @@ inline int32_t h_sat_i32(double v) {
     return (int32_t)v;
 }
 
-// rand_core's seed_from_u64: how every Xoshiro256+ state is seeded, the kernels' streams (capi.hip seed_streams, sgd.rs:431-432)
-// and the host's generators (host_tables.hip) alike; on the device for a set's streams (set_setup_kernels.hip).
+// rand_core's seed_from_u64: how every Xoshiro256+ state is seeded, the kernels' streams (sgd.rs:431-432), which are seeded on
+// the device (set_setup_kernels.hip), and the host's generators (host_tables.hip) alike.
 GFS_HOST_DEVICE uint64_t splitmix64(uint64_t &s) {
     uint64_t z = (s += 0x9E3779B97F4A7C15ull);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

@@ -1,5 +1,6 @@
-"""Set setup (gfs_ctx_set_setup_*, csrc/capi_set.hip) on the host: the state arena's plan, the refusals made before any device
-call, the zeta tables that items of like parameters share, and the seeding rule the device kernel restates.  No GPU needed; the
+"""Setup (gfs_ctx_set_setup_* and gfs_ctx_setup_*, csrc/capi_set.hip) on the host: the state arena's plan, the refusals made before
+any device call, the zeta tables that items of like parameters share, the seeding kernel's tables for a set and for one item alone,
+and the seeding rule the device kernel restates.  No GPU needed; the
 setup itself is held to gfs_ctx_setup_* byte for byte in tests/test_gpu_set_setup.py."""
 import ctypes as C
 import os
@@ -126,6 +127,7 @@ def test_numpy_seeding_is_the_rule_of_seed_streams(seed, stream_base):
 # ---- the plan and the zeta slices in a program of their own, under sanitizers -----------------------------------------------------
 SANITIZED_MAIN = r"""
 #include "set_state_plan.h"
+#include "set_seed_tables.h"
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -199,6 +201,46 @@ int main() {
         std::vector<uint8_t> none(clamped.size(), 0);
         CHECK(shared_zeta_tables(clamped.data(), none.data(), clamped.size()).tables.empty());
         CHECK(shared_zeta_tables(nullptr, nullptr, 0).tables.empty());
+    }
+    // ---- the seeding tables behind the state arrays (set_seed_tables.h), in a mirror that holds exactly their range: a set of
+    // items of 255, 256, 257, 1 and 70000 streams, and the set of one that a single context is
+    {
+        struct Item { uint64_t *rng; uint64_t first; uint32_t n_streams, first_block; };
+        static_assert(sizeof(Item) == 24, "as set_seed.h SeedItem");
+        const uint32_t B = 256;
+        for (const std::vector<uint32_t> &streams : std::vector<std::vector<uint32_t>>{{255, 256, 257, 1, 70000}, {257}, {1}}) {
+            std::vector<Item> items;
+            uint64_t total = 0, most = 0;
+            for (uint32_t T : streams) {
+                const uint64_t nb = (T + B - 1) / B;
+                items.push_back(Item{reinterpret_cast<uint64_t *>(uintptr_t(0x1000 * (items.size() + 1))), 7 + T, T, (uint32_t)total});
+                total += nb; most = std::max(most, nb);
+            }
+            const uint64_t begin = 256 * 5;
+            const SeedTables t = seed_tables_plan(begin, items.size(), sizeof(Item), total, most);
+            CHECK(t.items_at == begin && t.blocks_at % 256 == 0 && t.alone_at % 256 == 0 && t.zeros_at % 256 == 0 && t.end % 256 == 0);
+            CHECK(t.blocks_at - t.items_at >= items.size() * sizeof(Item) && t.alone_at - t.blocks_at >= total * 4);
+            CHECK(t.zeros_at - t.alone_at >= items.size() * sizeof(Item) && t.end - t.zeros_at >= most * 4);
+            std::vector<unsigned char> mirror(t.end - begin, 0);
+            fill_seed_tables(t, items.data(), items.size(), B, mirror.data());
+            const uint32_t *block_item = reinterpret_cast<const uint32_t *>(mirror.data() + (t.blocks_at - begin));
+            const uint32_t *zeros = reinterpret_cast<const uint32_t *>(mirror.data() + (t.zeros_at - begin));
+            uint64_t b = 0;
+            for (size_t k = 0; k < items.size(); ++k) {
+                Item all, alone;
+                std::memcpy(&all, mirror.data() + k * sizeof(Item), sizeof(Item));
+                std::memcpy(&alone, mirror.data() + (t.alone_at - begin) + k * sizeof(Item), sizeof(Item));
+                CHECK(std::memcmp(&all, &items[k], sizeof(Item)) == 0);
+                CHECK(alone.rng == items[k].rng && alone.first == items[k].first && alone.n_streams == items[k].n_streams && alone.first_block == 0);
+                const uint64_t nb = (items[k].n_streams + B - 1) / B;
+                CHECK(all.first_block == b);
+                for (uint64_t j = 0; j < nb; ++j, ++b) CHECK(block_item[b] == k);   // every workgroup of the launch over all finds its item
+                for (uint64_t j = 0; j < nb; ++j) CHECK(zeros[j] == 0);            // ... and every workgroup of the item's own launch item 0
+            }
+            CHECK(b == total);
+        }
+        const SeedTables none = seed_tables_plan(512, 0, sizeof(Item), 0, 0);       // nothing to do: no room
+        CHECK(none.end == 512);
     }
     std::printf("%d failures\n", failures);
     return failures ? 1 : 0;
